@@ -101,6 +101,16 @@ def integrator_case(n=4000):
         print("wrote", f"ref_integrator_{scheme}_{n}.npz")
 
 
+def vs_ref_case():
+    """The reference's side of tests/test_oracle_vs_ref.py, recorded for machines without the compiled reference."""
+    import tempfile
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    from test_oracle_vs_ref import RECORDING, record
+    with tempfile.TemporaryDirectory() as tmp:
+        np.savez_compressed(RECORDING, **record(O, tmp))
+    print("wrote", os.path.basename(RECORDING))
+
+
 if __name__ == "__main__":
     if not O.have_ref():
         O.build(ref=True)
@@ -110,3 +120,4 @@ if __name__ == "__main__":
     small_case(2049, "galaxy", 3)
     integrator_case()
     bench_case()
+    vs_ref_case()

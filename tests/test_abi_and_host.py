@@ -364,6 +364,35 @@ def test_bench_host_facts_and_roofline_arithmetic():
     assert abs(many["interactions_per_launch"] - 25000.0 * 200000.0 / 3) < 1 and many["launches_per_step"] == 3
 
 
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs without a GPU: float32 arrays as written; above 64 MB in all, the same seeded sample of
+    bodies from every array with its indices (float64), and the same sample from run to run."""
+    code = (
+        "import json, os, sys\n"
+        "import numpy as np\n"
+        "sys.path.insert(0, %r)\n"
+        "import bench\n"
+        "out = {}\n"
+        "for n, d in ((1000, 'small'), (3000000, 'large'), (3000000, 'again')):\n"
+        "    arrays = {k: np.arange(n, dtype=np.float32) * (i + 1) for i, k in enumerate(('qx', 'qy', 'qz', 'vx', 'vy', 'vz', 'ax', 'ay', 'az'))}\n"
+        "    out[d] = bench.dump_outputs(os.path.join(%r, d), arrays)\n"
+        "print(json.dumps(out))\n"
+    ) % (ROOT, str(tmp_path))
+    import sys
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    import json
+    names = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(names["small"]) == 9 and "sample_index" not in names["small"]
+    small = np.load(tmp_path / "small" / "vy.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, np.arange(1000, dtype=np.float32) * 5)
+    assert names["large"] == names["again"] and "sample_index" in names["large"]
+    assert sum(os.path.getsize(tmp_path / "large" / f"{k}.npy") for k in names["large"]) <= 64 * 10 ** 6 + 4096
+    idx = np.load(tmp_path / "large" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "again" / "sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "large" / "qz.npy"), (idx * 3).astype(np.float32))
+
+
 def test_planner_selftest_under_sanitizers():
     """The host-side planner (csrc/murb_plan.h, murb_schedule.h: item tables and partial-row layouts, no HIP in them)
     compiled with g++ under AddressSanitizer + UBSan and swept over a few thousand plans (sizes 1 … 60 001, 1-8 ranks, splits,

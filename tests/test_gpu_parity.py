@@ -710,8 +710,8 @@ def test_bench_contract(gpu):
     import subprocess
     import sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "30000", "--steps", "20", "--warmup", "2"],
-                       capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "30000", "--steps", "20", "--warmup", "2",
+                        "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -765,6 +765,42 @@ def test_bench_contract(gpu):
         assert e["acc_vs_fp64"]["max"] <= e["cpu_optim_acc_vs_fp64"]["max"]   # closer to the truth than the reference's CPU path
 
 
+def test_bench_plain_run_and_its_outputs(gpu, tmp_path):
+    """bench.py without --full: the headline figure only (no extras in the line), exactly --steps timed steps, and
+    --dump-outputs writes what the last timed step left: the same state and accelerations as the same number of steps
+    run here through the C ABI from the same initial conditions."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "30000", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == "body-interactions/s" and d["unit"] == "interactions/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 30000.0 ** 2 * 7 / (d["ms_per_step"] * 7e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "parity", "parity_gate_n30000", "cpu_baseline", "other_configs", "ms_per_step_sync_each_iteration"):
+        assert k not in d, k
+    names = ("qx", "qy", "qz", "vx", "vy", "vz", "ax", "ay", "az")
+    assert sorted(d["dumped_outputs"]) == sorted(names)
+    got = {k: np.load(out / f"{k}.npy") for k in names}
+    assert all(a.dtype == np.float32 and a.shape == (30000,) for a in got.values())
+    s = gpu.init_bodies(30000, "galaxy")
+    with gpu.Simulation(30000, soft=SOFT) as sim:
+        sim.upload(s)
+        sim.steps(DT, d["prewarm_steps"] + 2 + 7)
+        sim.sync()
+        want = dict(sim.state(), **dict(zip(("ax", "ay", "az"), sim.acc())))
+    for group in (("qx", "qy", "qz"), ("vx", "vy", "vz"), ("ax", "ay", "az")):
+        scale = max(float(np.abs(want[k]).max()) for k in group)
+        for k in group:
+            np.testing.assert_allclose(got[k], want[k], rtol=0, atol=1e-6 * scale, err_msg=k)
+
+
 def test_bench_multi_pass_roofline(gpu):
     """A size evaluated in several passes (forced with a small "sym_pass_mb"): one launch covers N^2 / passes interactions,
     and the roofline must be priced with that, not with N^2 (it would exceed the peak)."""
@@ -773,7 +809,7 @@ def test_bench_multi_pass_roofline(gpu):
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "60000", "--steps", "10", "--warmup", "2",
-                        "--opt", "sym_pass_mb=8", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--opt", "sym_pass_mb=8", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
     passes = d["config"]["sym_passes"]
@@ -794,7 +830,7 @@ def test_bench_under_torchrun_one_rank(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--bodies", "30000", "--steps", "20",
-           "--warmup", "2", "--no-cpu-baseline"]
+           "--warmup", "2", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

@@ -169,7 +169,7 @@ def test_bench_py_with_several_ranks(gpu, world, n):
         env["MURB_BENCH_NO_ONE_PROCESS"] = "1"                # process more on GPU 0 than the test box allows (6)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--bodies",
-           str(n), "--steps", "10", "--warmup", "2"]
+           str(n), "--steps", "10", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -227,7 +227,7 @@ def test_bench_py_launches_its_own_ranks(gpu):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6",
-                        "--warmup", "1", "--cu-reserve", "8", "--no-other-configs"], capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--cu-reserve", "8", "--no-other-configs", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -235,6 +235,31 @@ def test_bench_py_launches_its_own_ranks(gpu):
     assert d["n_gpus"] == 2 and d["steps"] == 6 and d["tuned"]["cu_reserve"] == 8
     chk = d["rank_mode_check"]
     assert chk["positions_identical_on_all_ranks"] and chk["finite"] and chk["max_position_diff_rel"] < 1e-5, chk
+
+
+def test_bench_py_plain_run_with_several_ranks(gpu, tmp_path):
+    """N > 1 without --full: the untimed tuning and the timed steps only — no check, no diagnostics, no other sizes in the
+    line — and --dump-outputs writes the gathered positions after the last timed step, finite and moved from the start."""
+    import json
+    env = dict(os.environ, MURBHIP_RCCL_LIBRARY=MOCK, MURB_BENCH_BACKEND="gloo", MURB_BENCH_SHARE_GPU="1", MURB_BENCH_UNTIMED_SCALE="0.1",
+               HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, (r.stdout, r.stderr[-1500:])
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["n_gpus"] == 2 and d["steps"] == 6 and d["tuned"]["tri_first_pct"] in (0, 25, 50, 75, 100)
+    for k in ("rank_mode_check", "exchange", "one_sided_plan", "p2p_plan", "one_process_plan", "other_configs", "roofline"):
+        assert k not in d, k
+    assert d["dumped_outputs"] == ["qx", "qy", "qz"]
+    s = gpu.init_bodies(40000, "galaxy")
+    for k in ("qx", "qy", "qz"):
+        a = np.load(out / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == (40000,) and np.isfinite(a).all() and not np.array_equal(a, s[k])
 
 
 def test_bench_py_watchdog_reports_a_stuck_phase(gpu):
@@ -265,7 +290,8 @@ def test_bench_py_keeps_the_measurement_when_an_extra_fails(gpu):
                MURB_BENCH_OTHER_CONFIGS="30000:10", MURB_BENCH_FAIL_IN="other config")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, (r.stdout, r.stderr[-1500:])
@@ -284,7 +310,8 @@ def test_bench_py_takes_the_one_sided_plan_when_it_wins(gpu):
                MURB_BENCH_OTHER_CONFIGS="30000:10", MURB_BENCH_TAKE_ONE_SIDED="1", MURB_BENCH_NO_ONE_PROCESS="1", MURB_BENCH_NO_P2P="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -307,7 +334,8 @@ def test_bench_py_keeps_the_measurement_when_rank_0_is_killed(gpu):
                MURB_BENCH_OTHER_CONFIGS="30000:10", MURB_BENCH_ABORT_IN="other config", MURB_BENCH_PHASE_LIMIT_S="60")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "40000", "--steps", "6", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, (r.stdout, r.stderr[-1500:])
