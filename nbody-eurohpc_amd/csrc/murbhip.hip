@@ -1478,6 +1478,17 @@ int murbhip_destroy(murbhip_ctx* c)
     return 0;
 }
 
+namespace {
+// The body state was replaced from outside the force evaluation (upload, device initialisation, an update from host
+// accelerations): neither the remembered forces nor the remembered pair potential, nor the metric sums, belong to it.
+void invalidate_cached_forces(murbhip_ctx* c)
+{
+    c->acc_current = false;
+    c->pe_current = false;
+    ++c->state_serial;
+}
+}  // namespace
+
 int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float* qz, const float* vx, const float* vy,
                    const float* vz, const float* m)
 {
@@ -1510,8 +1521,7 @@ int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float
     c->gather_pending = false;
     c->uploaded = true;
     c->lf_half = false;
-    c->acc_current = false;
-    ++c->state_serial;
+    invalidate_cached_forces(c);
     return 0;
 }
 
@@ -1589,8 +1599,7 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
     c->gather_pending = false;
     c->uploaded = true;
     c->lf_half = false;
-    c->acc_current = false;
-    ++c->state_serial;
+    invalidate_cached_forces(c);
     return 0;
 }
 
@@ -1776,8 +1785,7 @@ int murbhip_integrate_host_acc(murbhip_ctx* c, const float* ax, const float* ay,
         c->gather_pending = true;
     }
     c->cur ^= 1;
-    c->acc_current = false;
-    ++c->state_serial;
+    invalidate_cached_forces(c);
     return 0;
 }
 

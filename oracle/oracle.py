@@ -68,6 +68,11 @@ def lib():
         L.oracle_accel_f64_subset.argtypes = [C.c_ulong, C.c_ulong, _ul, _f, _f, _f, _f, C.c_float, _d, _d, _d]
         L.oracle_energy_f64.restype = None
         L.oracle_energy_f64.argtypes = [C.c_ulong] + [_f] * 7 + [C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.oracle_accel_f64_sources.restype = None
+        L.oracle_accel_f64_sources.argtypes = [C.c_ulong, C.c_ulong, _ul, _f, _f, _f, _f, C.c_float] + [_d] * 5
+        L.oracle_potential_f64_sources.restype = None
+        L.oracle_potential_f64_sources.argtypes = [C.c_ulong, _ul, _f, _f, _f, _f, C.c_float, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -129,6 +134,123 @@ def accel_f64_subset(s, idx, soft=SOFT):
     ax, ay, az = (np.zeros(len(idx), np.float64) for _ in range(3))
     lib().oracle_accel_f64_subset(n, len(idx), idx, s["qx"], s["qy"], s["qz"], s["m"], soft, ax, ay, az)
     return ax, ay, az
+
+
+# ----------------------------------------------------------------------------- sparse-mass probes
+# Acceleration is linear in the masses and the force plans depend on n and the options only: a probe keeps a problem's
+# positions and gives mass to a few "source" bodies.  Its fp64 truth costs O(n K), so every body is checked, and each
+# source's term is a visible share of every body's sum: a pair the kernels skip, count twice or misroute shows.
+PROBE_MASS = 1e20                   # kg: sources get masses in [1, 2) x this (comparable shares, none alike)
+PROBE_OFFSETS = (0, 1, 2, 3, 63, 64, 127, 128, 255, 256, 257, 511, 512, 513, 767, 1023)   # slot offsets in a block
+
+
+def probe_state(base, src, seed=0, zero_velocities=True):
+    """`base`'s positions with mass only on the bodies `src` (distinct indices), velocities zeroed unless asked not to."""
+    src = np.asarray(src, np.int64)
+    assert len(np.unique(src)) == len(src), "duplicate sources"
+    s = {k: np.array(v, np.float32) for k, v in base.items()}
+    s["m"] = np.zeros_like(s["m"])
+    s["m"][src] = (PROBE_MASS * np.random.default_rng(seed).uniform(1.0, 2.0, len(src))).astype(np.float32)
+    if zero_velocities:
+        for k in ("vx", "vy", "vz"):
+            s[k] = np.zeros_like(s[k])
+    return s
+
+
+def accel_f64_sources(s, src, soft=SOFT):
+    """((ax, ay, az), abs_sum, min_term) of every body due to the sources `src` alone: fp64 accelerations, the sum of the
+    magnitudes of each body's source terms, and the smallest of those terms (s != i; inf without one)."""
+    n = len(s["qx"])
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    out = [np.zeros(n, np.float64) for _ in range(5)]
+    lib().oracle_accel_f64_sources(n, len(src), src, s["qx"], s["qy"], s["qz"], s["m"], soft, *out)
+    return tuple(out[:3]), out[3], out[4]
+
+
+def potential_f64_sources(s, src, soft=SOFT):
+    """(potential, min_pair): the fp64 potential energy of a probe (pairs of sources only) and its smallest pair term."""
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    pe, mn = C.c_double(), C.c_double()
+    lib().oracle_potential_f64_sources(len(src), src, s["qx"], s["qy"], s["qz"], s["m"], soft, C.byref(pe), C.byref(mn))
+    return pe.value, mn.value
+
+
+def probe_err(test, truth, abs_sum):
+    """Per-body |a_test - a_true| / sum_s |c_is|: against the sum of the term magnitudes, not the net value, so that bodies
+    whose terms cancel do not fail on rounding noise."""
+    t = np.stack([np.asarray(c, np.float64) for c in test])
+    r = np.stack([np.asarray(c, np.float64) for c in truth])
+    return np.sqrt(((t - r) ** 2).sum(0)) / np.maximum(abs_sum, np.finfo(np.float64).tiny)
+
+
+def probe_power(abs_sum, min_term):
+    """Per body: the share of its smallest source term, min_{s != i} |c_is| / sum_s |c_is| (inf where there is none).
+    A probe sees one missing or doubled term on every body whose share is well above the tolerance."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(np.isfinite(min_term), min_term / np.maximum(abs_sum, np.finfo(np.float64).tiny), np.inf)
+
+
+def probe_sources(n, firsts, counts, slice_slots, probes=1, k_max=256, per_block=8, block=1024):
+    """Source sets (body indices) for at least `probes` consecutive probes of one problem, chosen in slot space.
+
+    Slots are the bodies after per-shard padding: shard r owns slots [r slice_slots, (r+1) slice_slots), its bodies
+    [firsts[r], firsts[r] + counts[r]) fill the first counts[r] of them.  Each block of `block` slots offers its sources
+    at the offsets PROBE_OFFSETS (a padding slot stands for the block's last real one), rotated block by block; the
+    first and last body of every shard and the last three bodies of the problem go first.  Up to `per_block` sources per
+    block and probe, at most `k_max` per probe: when the blocks do not fit, probe p takes the blocks b = p mod P, and there
+    are at least P probes.  Every block holds a source in one of the first P probes, and no probe repeats a slot of the
+    probe before it."""
+    world = len(firsts)
+    nblocks = world * slice_slots // block
+    specials = set()
+    for f, c in zip(firsts, counts):
+        if c:
+            specials.update((f, f + c - 1))
+    specials.update(range(max(0, n - 3), n))
+    slot_of = {}
+    for r, (f, c) in enumerate(zip(firsts, counts)):
+        for b in specials:
+            if f <= b < f + c:
+                slot_of[b] = r * slice_slots + (b - f)
+    per_block_special = {}
+    for b, sl in slot_of.items():
+        per_block_special.setdefault(sl // block, []).append(sl)
+    # candidate slots of every block, specials first
+    cand = []
+    for b in range(nblocks):
+        r, lo = divmod(b * block, slice_slots)
+        real = min(block, max(0, counts[r] - lo))
+        rot = (3 * b) % len(PROBE_OFFSETS)
+        offs = [min(o, real - 1) for o in PROBE_OFFSETS[rot:] + PROBE_OFFSETS[:rot]] if real else []
+        seen, lst = set(), []
+        for sl in sorted(per_block_special.get(b, [])) + [b * block + o for o in offs]:
+            if sl not in seen:
+                seen.add(sl)
+                lst.append(sl)
+        cand.append(lst)
+    nspecial = len(slot_of)
+    budget = k_max - nspecial
+    assert budget > 0
+    c = max(1, min(per_block, budget // max(nblocks, 1)))
+    P = max(1, -(-nblocks * c // budget))
+    out, prev = [], set()
+    for p in range(max(probes, P)):
+        rnd, sel = p // P, []
+        for b in range(p % P, nblocks, P):
+            L = cand[b]
+            if not L:
+                continue
+            take = max(1, min(c, len(L) // 2))
+            if rnd == 0:
+                take = max(take, len(per_block_special.get(b, [])))
+            sel.extend(L[(rnd * take + j) % len(L)] for j in range(take))
+        sel = [sl for sl in dict.fromkeys(sel) if sl not in prev]
+        prev = set(sel)
+        slots = np.array(sorted(sel), np.int64)
+        r, off = np.divmod(slots, slice_slots)
+        out.append(np.asarray(firsts, np.int64)[r] + off)
+    assert all(len(x) <= k_max for x in out)
+    return out
 
 
 def integrate(s, acc, dt=DT):

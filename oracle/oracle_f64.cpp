@@ -77,4 +77,57 @@ void oracle_energy_f64(unsigned long n, const float* qx, const float* qy, const 
     *potential = pe;
 }
 
+// Sparse-mass probes (tests/test_pair_coverage.py): the accelerations of ALL n bodies due to the nsrc bodies src[] alone,
+// O(n nsrc).  Per body also the sum of the magnitudes of its source terms c_is = G m_s d_is / (|d_is|^2 + soft^2)^(3/2)
+// (the scale the probe's error is measured against) and the smallest magnitude among them, s != i (what one missing or
+// doubled term would change; +inf when i has no other source).  The self term is exactly 0 and counted nowhere.
+void oracle_accel_f64_sources(unsigned long n, unsigned long nsrc, const unsigned long* src, const float* qx,
+                              const float* qy, const float* qz, const float* m, float soft, double* ax, double* ay,
+                              double* az, double* abs_sum, double* min_term)
+{
+    const double G = (double)6.67384e-11f;
+    const double soft2 = (double)soft * (double)soft;
+#pragma omp parallel for schedule(static)
+    for (unsigned long i = 0; i < n; ++i) {
+        const double xi = qx[i], yi = qy[i], zi = qz[i];
+        double sx = 0.0, sy = 0.0, sz = 0.0, sa = 0.0, mn = HUGE_VAL;
+        for (unsigned long k = 0; k < nsrc; ++k) {
+            const unsigned long j = src[k];
+            if (j == i) continue;
+            const double dx = (double)qx[j] - xi, dy = (double)qy[j] - yi, dz = (double)qz[j] - zi;
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            const double inv = 1.0 / std::sqrt(d2 + soft2);
+            const double f = G * (double)m[j] * inv * inv * inv;
+            const double mag = f * std::sqrt(d2);
+            sx += f * dx; sy += f * dy; sz += f * dz;
+            sa += mag;
+            mn = mag < mn ? mag : mn;
+        }
+        ax[i] = sx; ay[i] = sy; az[i] = sz;
+        abs_sum[i] = sa;
+        min_term[i] = mn;
+    }
+}
+
+// The potential energy of the same probes: only pairs of sources carry mass, so the sum of oracle_energy_f64 reduces to
+// -sum_{s < t} G m_s m_t / sqrt(r_st^2 + soft^2) over the nsrc bodies src[] (distinct indices).  min_pair: the smallest
+// magnitude of one pair's term.
+void oracle_potential_f64_sources(unsigned long nsrc, const unsigned long* src, const float* qx, const float* qy,
+                                  const float* qz, const float* m, float soft, double* potential, double* min_pair)
+{
+    const double G = (double)6.67384e-11f;
+    const double soft2 = (double)soft * (double)soft;
+    double pe = 0.0, mn = HUGE_VAL;
+    for (unsigned long a = 0; a < nsrc; ++a)
+        for (unsigned long b = a + 1; b < nsrc; ++b) {
+            const unsigned long i = src[a], j = src[b];
+            const double dx = (double)qx[j] - qx[i], dy = (double)qy[j] - qy[i], dz = (double)qz[j] - qz[i];
+            const double t = G * (double)m[i] * (double)m[j] / std::sqrt(dx * dx + dy * dy + dz * dz + soft2);
+            pe -= t;
+            mn = t < mn ? t : mn;
+        }
+    *potential = pe;
+    *min_pair = mn;
+}
+
 }  // extern "C"
