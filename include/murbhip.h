@@ -171,6 +171,23 @@ int murbhip_download_acc(murbhip_ctx* ctx, float* ax, float* ay, float* az);
  * the forces instead of evaluating them again (one shard; bit-identical either way). */
 int murbhip_compute_acc(murbhip_ctx* ctx);
 
+/* Accelerations AND their time derivatives ("jerks") in one all-pairs sweep, fp32, for the current positions and
+ * velocities; no integration.  Enqueue only.  With d = q_j - q_i, w = v_j - v_i, r2 = |d|^2 + soft^2:
+ *     a_i = sum_j G m_j d r2^(-3/2)          j_i = sum_j G m_j (w - 3 (d.w) d / r2) r2^(-3/2)
+ * (csrc/murb_kernels_hermite.h; one shard only: MURBHIP_E_STATE otherwise, see "integrator" 2).  The result is remembered
+ * like murbhip_compute_acc's: a second call without a state change in between costs nothing, and a Hermite step that
+ * follows directly starts from it as its (a0, j0) — bit-identical either way.  After a Hermite step the remembered
+ * evaluation is that step's own (a1, j1, taken at its predicted state: what the next step starts from), and the call
+ * leaves it as it is.  murbhip_download_acc returns the accelerations (also when a force evaluation — murbhip_compute_acc,
+ * murbhip_energy — used that buffer in between: the call then puts them back), murbhip_download_jerk the jerks. */
+int murbhip_compute_acc_jerk(murbhip_ctx* ctx);
+
+/* Jerks of the remembered acceleration + jerk evaluation (murbhip_compute_acc_jerk, or the last Hermite step), n entries
+ * each; waits for enqueued work first.  Test hook, like murbhip_download_acc.  MURBHIP_E_STATE when no such evaluation is
+ * current (none yet, or the bodies changed since: upload, device initialisation, murbhip_integrate_host_acc, a step of
+ * another integrator). */
+int murbhip_download_jerk(murbhip_ctx* ctx, float* jx, float* jy, float* jz);
+
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
  * §4.5) — as long as the reference's whole 200-iteration run at N = 30 000.  Construction is outside the reference's timing
@@ -271,7 +288,17 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    the force taken at the positions it belongs to: one force evaluation per step, the
  *                    device keeps v_{n-1/2}, murbhip_download_state applies the closing half kick (one
  *                    extra force evaluation; a collective in rank mode).  Cannot be changed between a
- *                    leapfrog step and the next murbhip_upload (MURBHIP_E_STATE)
+ *                    leapfrog step and the next murbhip_upload (MURBHIP_E_STATE); 2 = 4th-order Hermite
+ *                    predictor-corrector (Makino & Aarseth 1992) in place of Bodies.cpp:260-278: predict q, v from
+ *                    the remembered accelerations and jerks, ONE acceleration + jerk sweep at the predicted state
+ *                    (murbhip_compute_acc_jerk's kernel, about twice the arithmetic of a force evaluation), correct;
+ *                    the first step after a change of the bodies evaluates (a0, j0) at the current state first.
+ *                    dt may change from step to step.  Device velocities are whole-step values: no closing kick, and
+ *                    the option may be switched away from 2 at any time.  Single shard only: the sweep reads the
+ *                    velocities of ALL bodies, which sharded and rank-mode contexts keep for their own slice alone
+ *                    (they exchange positions, never velocities), so on a context of several shards or ranks, or
+ *                    with "force_exchange" set, the value 2 is refused with MURBHIP_E_STATE (and "force_exchange"
+ *                    is refused while the value is 2)
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real

@@ -41,6 +41,7 @@
 #include "../../include/murbhip.h"
 #include "murb_crew.h"
 #include "murb_init.h"
+#include "murb_kernels_hermite.h"
 #include "murb_kernels_sym.h"
 #include "murb_plan.h"
 #include "murb_rccl.h"
@@ -121,6 +122,13 @@ struct Shard {
     std::vector<hipEvent_t> prof;   // pool of timing events ("profile"): two per recorded span
     size_t prof_used = 0;
     std::vector<int> prof_kind;     // what span k (events 2k, 2k+1) brackets: ProfKind
+    // Hermite integrator ("integrator" 2; one shard), allocated on first use (ensure_hermite)
+    float4* herm_rec = nullptr;     // predicted positions + GM, all slots
+    float4* herm_vel = nullptr;     // predicted velocities
+    float* herm_a0 = nullptr;       // ax | ay | az of the remembered evaluation
+    float* herm_j0 = nullptr;       // jx | jy | jz of it
+    float4* herm_part = nullptr;    // partial rows of the sweep: herm_rows rows of accelerations, then as many of jerks
+    int herm_rows = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -167,7 +175,9 @@ struct murbhip_ctx {
     int tri_first_pct = 50;   // overlap 1: share of the own-slice triangle launched BEFORE the rectangles (under the
                               // position gather); the rest runs under the reduce-scatter
     int xcd_order = 0;        // pair-symmetric kernel: 1 = item table interleaved into one run per XCD (measured worse)
-    int integrator = 0;       // 0 the reference's update (Bodies.cpp:260-278), 1 kick-drift-kick leapfrog
+    int integrator = 0;       // 0 the reference's update (Bodies.cpp:260-278), 1 kick-drift-kick leapfrog, 2 4th-order Hermite
+    bool herm_current = false;// Hermite: herm_a0 / herm_j0 hold the evaluation the next step starts from
+    bool herm_in_acc_out = false;   // ... and acc_out still holds its accelerations (no force evaluation has run since)
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)
@@ -184,8 +194,8 @@ struct murbhip_ctx {
     long sym_pass_mb = 0;     // ... one GPU: budget (MiB) for the partial rows of one pass; 0 = a quarter of the device memory
     int sym_red = -1;         // ... i-side reduction in registers (0) or through LDS (1) (-1 = the plan's default)
     int init_libm_fma = -1;   // murbhip_init_bodies: which build of glibc's sincosf to reproduce (-1 = what this host's libm picks)
-    int energy_sweep = 0;
-    int fuse_integrate = 1;   // "fuse_integrate": one-sided plan, the state update in the tail of the step's last force launch     // murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 (kept for the A/B)
+    int energy_sweep = 0;     // murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 (kept for the A/B)
+    int fuse_integrate = 1;   // "fuse_integrate": one-sided plan, the state update in the tail of the step's last force launch
     int exchange_p2p = 0;     // RCCL exchange by grouped ncclSend/ncclRecv instead of ncclReduceScatter / ncclAllGather
     int tri_div = 0;          // ... exchange pipeline: the own-slice triangle's items cut into this many parts more (0 = the plan's choice)
     int pad_aware = 1;        // ... 1: padding slots are not walked (murb_schedule.h, sym_orient); 0: every block as if full (A/B)
@@ -1130,11 +1140,23 @@ int shard_iteration_plain(murbhip_ctx* c, Shard& sh, const Plan& p, float dt, in
     return rc;
 }
 
+// The body state changed (upload, device initialisation, an update from host accelerations, a step of any integrator):
+// neither the remembered forces, nor the remembered pair potential, nor the Hermite integrator's remembered (a0, j0), nor
+// the metric sums (state_serial) belong to the new one.  Every change of the bodies goes through here.
+void invalidate_cached_forces(murbhip_ctx* c)
+{
+    c->acc_current = false;
+    c->pe_current = false;
+    c->herm_current = false;
+    ++c->state_serial;
+}
+
 int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
 {
     const Plan p = make_plan(c);
     c->last_parts = p.parts_local + p.parts_remote;
     c->plan_waves = p.symmetric ? p.waves : 4;
+    c->herm_in_acc_out = false;   // acc_out is the force plan's from here on
     // forces at the current positions are already in acc_out (compute_acc, or a leapfrog read-out, just ran): an
     // evaluation needs nothing at all, a state update (one shard, no exchange) only the integrate launch
     const bool have_acc = c->acc_current;
@@ -1158,11 +1180,145 @@ int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
     if (update_state) {
         if (exchanging) c->gather_pending = true;
         c->cur ^= 1;
-        ++c->state_serial;
+        invalidate_cached_forces(c);
     } else {
         c->acc_current = true;
         c->pe_current = c->want_pe && p.symmetric;
     }
+    return 0;
+}
+
+// ---- 4th-order Hermite predictor-corrector ("integrator" 2, murb_kernels_hermite.h) ------------------------------------------
+// One shard only.  A step is predictor, ONE acceleration + jerk sweep at the predicted state, corrector; the first step after
+// a change of the bodies evaluates (a0, j0) at the current state first.  One launch shape for every N: 4 i bodies per wave,
+// 4 waves per workgroup, 2 position + 2 velocity tiles per stage (32 KiB of LDS, like the one-sided force kernel).
+constexpr int kHermiteR = 4, kHermiteWaves = 4, kHermiteStage = 2;
+
+// j chunks of the sweep: the one-sided kernels' rule ("jsplit" overrides), for i groups of 16 bodies
+int hermite_parts(const murbhip_ctx* c)
+{
+    const unsigned long tiles = c->slots / MURB_TILE_BODIES;
+    if (c->jsplit > 0) return (int)std::min<unsigned long>((unsigned long)c->jsplit, std::min<unsigned long>(tiles, kMaxParts / 2));
+    return auto_parts(c, kOneSidedFewBodies, c->slots, tiles);
+}
+
+int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
+{
+    // each buffer under its own guard: a failed allocation leaves its pointer null and the next call tries again
+    const size_t rec_bytes = c->slots * sizeof(float4), plane_bytes = 3 * c->slots * sizeof(float);
+    for (float4** p : {&sh.herm_rec, &sh.herm_vel}) {
+        if (*p) continue;
+        HIP_TRY(hipMalloc((void**)p, rec_bytes));
+        sh.bytes += rec_bytes;
+    }
+    for (float** p : {&sh.herm_a0, &sh.herm_j0}) {
+        if (*p) continue;
+        HIP_TRY(hipMalloc((void**)p, plane_bytes));
+        sh.bytes += plane_bytes;
+        const int rc = hip_rc(hipMemsetAsync(*p, 0, plane_bytes, sh.compute));
+        if (rc) return rc;
+    }
+    if (rows > sh.herm_rows) {   // more chunks than before ("jsplit"): the rows in flight are read by an enqueued corrector
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        release(sh.herm_part);
+        sh.herm_part = nullptr;
+        sh.bytes -= (size_t)2 * sh.herm_rows * c->slots * sizeof(float4);
+        sh.herm_rows = 0;
+        const size_t bytes = (size_t)2 * rows * c->slots * sizeof(float4);
+        HIP_TRY(hipMalloc((void**)&sh.herm_part, bytes));
+        HIP_TRY(hipMemsetAsync(sh.herm_part, 0, bytes, sh.compute));   // slots past the last i group have no writer: they read as 0
+        sh.herm_rows = rows;
+        sh.bytes += bytes;
+    }
+    return 0;
+}
+
+MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, float dt, int update_state)
+{
+    MurbHermiteArgs a{};
+    a.rec_in = sh.rec[c->cur];
+    a.vel = sh.vel;
+    a.a0 = sh.herm_a0;
+    a.j0 = sh.herm_j0;
+    a.part_a = sh.herm_part;
+    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
+    a.acc_out = sh.acc_out;
+    a.nparts = parts;
+    a.count = (int)sh.count;
+    a.stride = (unsigned int)c->slots;
+    a.dt = dt;
+    a.update_state = update_state;
+    return a;
+}
+
+// accelerations and jerks of the state (rec, vel) into the partial rows
+int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts)
+{
+    MurbJerkArgs a{};
+    a.rec = rec;
+    a.vel = vel;
+    a.part_a = sh.herm_part;
+    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
+    a.tiles = (int)(c->slots / MURB_TILE_BODIES);
+    a.nchunks = parts;
+    a.stride = (unsigned int)c->slots;
+    a.soft2 = c->soft2;
+    constexpr int group = kHermiteWaves * kHermiteR;
+    const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);   // whole i groups: the extra slots hold mass 0
+    int rc = 0;
+    const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
+    RC_TRY(rc);
+    hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a);
+    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(span_end(sh, sp, sh.compute));
+    note_interactions(c, sh, (double)sh.count * (double)c->slots);
+    return 0;
+}
+
+// update_state 0: make sure (a0, j0) of the current state are remembered; 1: one step.
+int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
+{
+    if (c->world != 1 || c->shards.size() != 1 || c->force_exchange) return MURBHIP_E_STATE;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const int parts = hermite_parts(c);
+    c->last_parts = parts;
+    RC_TRY(ensure_hermite(c, sh, parts));
+    if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
+    const unsigned pairs = (unsigned)(c->slots / 2);
+    if (!c->herm_current) {
+        RC_TRY(enqueue_hermite_sweep(c, sh, sh.rec[c->cur], sh.vel, parts));
+        const MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 0);
+        hipLaunchKernelGGL(murb_hermite_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+        RC_TRY(hip_rc(hipGetLastError()));
+        c->acc_current = false;   // acc_out now holds this sweep's accelerations, not the force plan's
+        c->pe_current = false;
+        c->herm_current = true;
+        c->herm_in_acc_out = true;
+    }
+    if (!update_state) {
+        if (!c->herm_in_acc_out) {   // a force evaluation has used acc_out since: murbhip_download_acc is to return THIS evaluation's
+            HIP_TRY(hipMemcpyAsync(sh.acc_out, sh.herm_a0, 3 * c->slots * sizeof(float), hipMemcpyDeviceToDevice, sh.compute));
+            c->acc_current = false;
+            c->pe_current = false;
+            c->herm_in_acc_out = true;
+        }
+        return 0;
+    }
+    MurbHermiteArgs a = hermite_args(c, sh, parts, dt, 1);
+    a.rec_out = sh.herm_rec;
+    a.vel_out = sh.herm_vel;
+    hipLaunchKernelGGL(murb_hermite_predict_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(enqueue_hermite_sweep(c, sh, sh.herm_rec, sh.herm_vel, parts));
+    a.rec_out = sh.rec[c->cur ^ 1];
+    a.vel_out = nullptr;
+    hipLaunchKernelGGL(murb_hermite_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    RC_TRY(hip_rc(hipGetLastError()));
+    c->cur ^= 1;
+    invalidate_cached_forces(c);
+    c->herm_current = true;   // (a1, j1) of this step are the next step's (a0, j0)
+    c->herm_in_acc_out = true;
     return 0;
 }
 
@@ -1471,23 +1627,13 @@ int murbhip_destroy(murbhip_ctx* c)
         for (hipStream_t* q : {&sh.compute_low, &sh.compute, &sh.comm}) release_stream(*q);
         release(sh.rec[0], sh.rec[1], sh.vel, sh.accp, sh.acc_out, sh.phi_out, sh.mass, sh.radius, sh.metrics);
         if (sh.metrics_host) (void)hipHostFree(sh.metrics_host);
+        release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
         free_sym_set(sh.sym_main); free_sym_set(sh.sym_tri);
     }
     delete c;
     return 0;
 }
-
-namespace {
-// The body state was replaced from outside the force evaluation (upload, device initialisation, an update from host
-// accelerations): neither the remembered forces nor the remembered pair potential, nor the metric sums, belong to it.
-void invalidate_cached_forces(murbhip_ctx* c)
-{
-    c->acc_current = false;
-    c->pe_current = false;
-    ++c->state_serial;
-}
-}  // namespace
 
 int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float* qz, const float* vx, const float* vy,
                    const float* vz, const float* m)
@@ -1727,6 +1873,28 @@ int murbhip_compute_acc(murbhip_ctx* c)
     return enqueue_iteration(c, 0.f, 0);
 }
 
+int murbhip_compute_acc_jerk(murbhip_ctx* c)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->lf_half) return MURBHIP_E_STATE;   // a leapfrog run in flight has half-step velocities
+    return enqueue_hermite(c, 0.f, 0);
+}
+
+int murbhip_download_jerk(murbhip_ctx* c, float* jx, float* jy, float* jz)
+{
+    if (!c || !jx || !jy || !jz) return MURBHIP_E_INVALID;
+    if (!c->uploaded || !c->herm_current) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    std::vector<float> j(3 * c->slots);
+    HIP_TRY(hipSetDevice(sh.device));
+    HIP_TRY(hipMemcpy(j.data(), sh.herm_j0, j.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::memcpy(jx, j.data(), c->n * sizeof(float));
+    std::memcpy(jy, j.data() + c->slots, c->n * sizeof(float));
+    std::memcpy(jz, j.data() + 2 * c->slots, c->n * sizeof(float));
+    return 0;
+}
+
 int murbhip_warmup(murbhip_ctx* c, double milliseconds)
 {
     if (!c || !(milliseconds >= 0.0) || milliseconds > 10000.0) return MURBHIP_E_INVALID;
@@ -1748,6 +1916,7 @@ int murbhip_step(murbhip_ctx* c, float dt)
 {
     if (!c) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
+    if (c->integrator == 2) return enqueue_hermite(c, dt, 1);
     RC_TRY(enqueue_iteration(c, dt, 1));
     if (c->integrator == 1) { c->lf_half = true; c->lf_last_dt = dt; }
     return 0;
@@ -1758,6 +1927,7 @@ int murbhip_steps(murbhip_ctx* c, float dt, int iterations)
     if (!c || iterations < 0) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
     for (int i = 0; i < iterations; ++i) {
+        if (c->integrator == 2) { RC_TRY(enqueue_hermite(c, dt, 1)); continue; }
         RC_TRY(enqueue_iteration(c, dt, 1));
         if (c->integrator == 1) { c->lf_half = true; c->lf_last_dt = dt; }
     }
@@ -2002,8 +2172,9 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "sym_waves") { if (value != 0 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->sym_waves = (int)value; }
     else if (k == "overlap") { if (value < 0 || value > 2) return MURBHIP_E_INVALID; c->overlap = (int)value; }
     else if (k == "integrator") {
-        if (value < 0 || value > 1) return MURBHIP_E_INVALID;
+        if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
+        if (value == 2 && (c->world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
         c->integrator = (int)value;
     }
     else if (k == "solo_shard") c->solo_shard = (int)value;
@@ -2022,6 +2193,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     }
     else if (k == "force_exchange") {
         if (value && c->exchange == 1 && !c->shards[0].comm_rccl) return MURBHIP_E_STATE;
+        if (value && c->integrator == 2) return MURBHIP_E_STATE;   // the Hermite integrator has no exchange
         c->force_exchange = value ? 1 : 0;
     }
     else if (k == "profile") {

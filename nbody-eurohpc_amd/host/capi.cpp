@@ -73,7 +73,7 @@ void *murbhost_sim_create(unsigned long n, const char *scheme, float soft, float
     h->sim->setDt(dt);
     return h;
 }
-// --im hip+tracking (leapfrog = 0) / hip+leapfrog (1)
+// --im hip+tracking (leapfrog = 0) / hip+leapfrog (1) / hip+hermite (2): the value is murbhip's option "integrator"
 void *murbhost_tracking_create(unsigned long n, const char *scheme, float soft, float dt, int leapfrog, int ndev,
                                const int *devices, int exchange)
 {
@@ -81,7 +81,7 @@ void *murbhost_tracking_create(unsigned long n, const char *scheme, float soft, 
     h->scheme = scheme;
     h->history = std::make_shared<SimulationHistory<double>>();
     HIPBodiesAllocator<float> alloc(n, h->scheme);
-    h->sim = new SimulationNBodyHIPTracking<float, double>(alloc, h->history, soft, leapfrog != 0,
+    h->sim = new SimulationNBodyHIPTracking<float, double>(alloc, h->history, soft, leapfrog,
                                                            std::vector<int>(devices, devices + ndev), exchange);
     h->sim->setDt(dt);
     return h;

@@ -7,13 +7,13 @@
 template <typename T, typename Q>
 SimulationNBodyHIPTracking<T, Q>::SimulationNBodyHIPTracking(const BodiesAllocatorInterface<T> &allocator,
                                                              std::shared_ptr<SimulationHistory<Q>> history, const T soft,
-                                                             const bool leapfrog, const std::vector<int> &devices,
+                                                             const int integrator, const std::vector<int> &devices,
                                                              int exchange)
     : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}
 {
     if (!this->history) this->history = std::make_shared<SimulationHistory<Q>>();
-    if (leapfrog)
-        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", 1), "murbhip_set_option(integrator)");
+    if (integrator)
+        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", integrator), "murbhip_set_option(integrator)");
 }
 
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::computeMetrics()

@@ -1,7 +1,7 @@
-// `--im hip+tracking` and `--im hip+leapfrog`: the MI355X path with a per-iteration metrics history —
+// `--im hip+tracking`, `--im hip+leapfrog` and `--im hip+hermite`: the MI355X path with a per-iteration metrics history —
 // the counterparts of the reference's gpu+tracking (SimulationNBodyCUDAPropertyTracking.hpp, energy of
 // the state each iteration starts from, computeOneIteration() at .cu:121-133) and gpu+leapfrog
-// (SimulationNBodyCUDALeapfrog.hpp: same history, leapfrog integrator).
+// (SimulationNBodyCUDALeapfrog.hpp: same history, leapfrog integrator); hip+hermite has no counterpart there.
 //
 // Filled per iteration: energy (kinetic + potential, reference definitions), |angular momentum| and the
 // centre of mass — the reference reserves the last two columns but never computes them
@@ -21,9 +21,10 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     int currentIteration = 0;
 
   public:
-    // leapfrog = true: kick-drift-kick instead of the reference's update (murbhip option "integrator")
+    // integrator: murbhip option "integrator" — 0 (false) the reference's update, 1 (true) kick-drift-kick leapfrog,
+    // 2 4th-order Hermite.  The parameter used to be `bool leapfrog`: callers that pass a bool get 0 / 1 as before.
     SimulationNBodyHIPTracking(const BodiesAllocatorInterface<T> &allocator, std::shared_ptr<SimulationHistory<Q>> history,
-                               const T soft = 0.035f, const bool leapfrog = false, const std::vector<int> &devices = {0},
+                               const T soft = 0.035f, const int integrator = 0, const std::vector<int> &devices = {0},
                                int exchange = 1);
     virtual ~SimulationNBodyHIPTracking() = default;
 

@@ -40,7 +40,7 @@ bool ShowGFlops = false;
 int NDevices = 0;        // --ngpu, hip+tile+multi only (0 = all visible)
 bool FreeRunning = false;   // --free: sync once at the end instead of once per iteration
 bool DeviceInit = false;    // --dinit: generate the initial conditions on the device (bit-identical to the host's)
-std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog save their history
+std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+hermite save their history
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -72,6 +72,8 @@ static std::vector<Option> optionTable()
          "\t\t\t - \"hip+tile+multi\"  bodies partitioned over --ngpu MI355X, RCCL position exchange\n"
          "\t\t\t - \"hip+tracking\"    hip+tile + energy / angular momentum / centre of mass per iteration\n"
          "\t\t\t - \"hip+leapfrog\"    hip+tracking with a kick-drift-kick leapfrog integrator\n"
+         "\t\t\t - \"hip+hermite\"     hip+tracking with a 4th-order Hermite integrator (its sweep also computes the jerks:\n"
+         "\t\t\t                      about twice the arithmetic of the 20 N^2 flops per iteration reported)\n"
          "\t\t\t ----"},
         {"-soft", "softeningFactor", false, "softening factor."},
         {"s", "bodies scheme", false, "bodies scheme (initial conditions can be \"galaxy\" or \"random\")."},
@@ -79,7 +81,7 @@ static std::vector<Option> optionTable()
         {"-ngpu", "nGpus", false, "number of GPUs for hip+tile+multi (default: all visible)."},
         {"-free", "", false, "free-running timing: one device sync at the end, not one per iteration."},
         {"-dinit", "", false, "generate the initial conditions on the device (same bodies, bit for bit)."},
-        {"-csv", "file", false, "hip+tracking / hip+leapfrog: save the metrics history as CSV."},
+        {"-csv", "file", false, "hip+tracking / hip+leapfrog / hip+hermite: save the metrics history as CSV."},
     };
 }
 
@@ -151,10 +153,11 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
         return new SimulationNBodyHIP<T>(hipAllocator, Softening, devices, /*exchange: RCCL when distinct GPUs*/
                                          use <= visible ? 1 : 0);
     }
-    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog") {   // shaped like main.cpp:245-261
+    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite") {   // shaped like main.cpp:245-261
         HIPBodiesAllocator<T> hipAllocator(NBodies, BodiesScheme);
         History = std::make_shared<SimulationHistory<double>>((int)NIterations);
-        return new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening, ImplTag == "hip+leapfrog");
+        return new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening,
+                                                         ImplTag == "hip+leapfrog" ? 1 : (ImplTag == "hip+hermite" ? 2 : 0));
     }
     std::cout << "Implementation '" << ImplTag << "' does not exist... Exiting." << std::endl;
     exit(-1);

@@ -62,6 +62,8 @@ def lib():
         L.murbhip_download_state.argtypes = [C.c_void_p] + [_fp] * 6
         L.murbhip_download_acc.argtypes = [C.c_void_p] + [_fp] * 3
         L.murbhip_compute_acc.argtypes = [C.c_void_p]
+        L.murbhip_compute_acc_jerk.argtypes = [C.c_void_p]
+        L.murbhip_download_jerk.argtypes = [C.c_void_p] + [_fp] * 3
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -79,6 +81,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_schedule_items murbhip_schedule_layout "
            "murbhip_device_count murbhip_create murbhip_create_sharded murbhip_unique_id murbhip_create_rank "
            "murbhip_destroy murbhip_upload murbhip_init_bodies murbhip_download_mass murbhip_download_state murbhip_download_acc murbhip_compute_acc "
+           "murbhip_compute_acc_jerk murbhip_download_jerk "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -205,6 +208,15 @@ class Simulation:
     # -- compute (enqueue only; sync() waits)
     def compute_acc(self):
         _check(lib().murbhip_compute_acc(self._h), "murbhip_compute_acc")
+
+    def compute_acc_jerk(self):
+        """Accelerations and jerks in one sweep (include/murbhip.h: murbhip_compute_acc_jerk); read with acc() / jerk()."""
+        _check(lib().murbhip_compute_acc_jerk(self._h), "murbhip_compute_acc_jerk")
+
+    def jerk(self):
+        j = [np.zeros(self.n, np.float32) for _ in range(3)]
+        _check(lib().murbhip_download_jerk(self._h, *[_ptr(x) for x in j]), "murbhip_download_jerk")
+        return tuple(j)
 
     def warmup(self, milliseconds=50.0):
         """Untimed force evaluations on the current state (include/murbhip.h: murbhip_warmup); syncs."""
@@ -345,13 +357,16 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False):
-        """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`)."""
+                 leapfrog=False, integrator=None):
+        """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
+        0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`)."""
+        if integrator is None:
+            integrator = int(bool(leapfrog))
         arr = (C.c_int * len(devices))(*devices)
         self.H = host_lib()
         ex = {"copy": 0, "rccl": 1}[exchange]
-        if tracking or leapfrog:
-            self.h = self.H.murbhost_tracking_create(n, scheme.encode(), soft, dt, int(leapfrog), len(devices), arr, ex)
+        if tracking or integrator:
+            self.h = self.H.murbhost_tracking_create(n, scheme.encode(), soft, dt, int(integrator), len(devices), arr, ex)
         else:
             self.h = self.H.murbhost_sim_create(n, scheme.encode(), soft, dt, len(devices), arr, ex)
         self.n = int(self.H.murbhost_sim_n(self.h))

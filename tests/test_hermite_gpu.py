@@ -1,0 +1,347 @@
+"""GPU: the 4th-order Hermite integrator (option "integrator" 2, `--im hip+hermite`) through the C ABI.
+
+Yardsticks: the oracle's fp64 direct sum for the accelerations, tests/helpers/hermite_ref.py (numpy fp64, pinned against
+itself by test_hermite_host.py) for jerks and trajectories, oracle.leapfrog (the CPU kick-drift-kick restatement) for
+what a 4th-order scheme is for.  PARITY UNPINNED by the reference, which has no such integrator.
+
+The jerk bound.  A body's jerk sum cancels far more than its acceleration sum, so the error of a body is scaled by the
+sum of the magnitudes of its terms (oracle.probe_err's convention) and bounded by C * 2^-24 with C = 4 x what a plain
+numpy float32 evaluation of the same formula (128 partial sums per body, then added: hermite_ref.acc_jerk_f32) attains
+against fp64 on the same inputs — computed on the CPU inside the test, never from the GPU's output.  The factor 4 covers
+v_rsq_f32's 1 ulp against numpy's correctly rounded 1/sqrt and a different summation tree.  Measured on the CPU, in units
+of 2^-24 (numpy float32 -> C): galaxy N = 2 048, 2 049, 4 000, 12 001, 30 000: 17.6, 18.0, 15.2, 14.4, 9.9 -> 39-72;
+random, same sizes: 2.9, 2.7, 3.1, 3.2, 3.5 -> 11-14; galaxy N = 3 000 at soft 1e3, 1e6, 1e7, 1e10: 13.9, 18.2, 14.8, 12.6
+-> 50-73; random N = 2, 3, 63, 513: 2.8, 5.4, 3.6, 3.5 -> 11-22.  (The galaxy's figures are larger because one term, the
+central mass's, carries most of a body's sum and its fp32 rounding is not averaged down.)  Every test prints the GPU's
+figure beside its bound (pytest -s)"""
+import os
+import subprocess
+import sys
+from functools import lru_cache
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import hermite_ref as H   # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SOFT, DT = np.float32(2e8), np.float32(3600.0)
+TOL_F64_MAX = 2e-6      # accelerations vs fp64: the bound of test_gpu_parity.test_acceleration_vs_oracles
+TOL_POS = 2e-6          # positions, of the position scale (test_gpu_parity)
+TOL_VEL = {"galaxy": 2e-5, "random": 2e-4}   # velocities, of the velocity scale (test_leapfrog_vs_restatement)
+JERK_MARGIN = 4.0
+Q, V = ("qx", "qy", "qz"), ("vx", "vy", "vz")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def gpu_acc_jerk(gpu, s, soft=SOFT, **opts):
+    with gpu.Simulation(len(s["qx"]), soft=soft) as sim:
+        for k, v in opts.items():
+            sim.set_option(k, v)
+        sim.upload(s)
+        sim.compute_acc_jerk()
+        sim.sync()
+        return sim.acc(), sim.jerk()
+
+
+@lru_cache(maxsize=None)
+def _case(scheme, n, soft=float(SOFT)):
+    """(state, fp64 a, fp64 j, sum of |jerk terms|, C of the jerk bound in units of 2^-24): CPU only."""
+    import oracle as O
+    s = O.init_bodies(n, scheme)
+    a, j, abs_j = H.acc_jerk_f64(s, np.float32(soft), want_abs=True)
+    _, j32 = H.acc_jerk_f32(s, np.float32(soft))
+    c32 = H.scaled_err(j32, j, abs_j).max() * 2.0 ** 24
+    return s, a, j, abs_j, JERK_MARGIN * c32
+
+
+def check_acc_jerk(O, got, s, a, j, abs_j, c, what, acc_tol=TOL_F64_MAX):
+    ga, gj = got
+    assert all(np.isfinite(x).all() for x in ga + gj), what
+    ea = O.rel_err(ga, a).max()
+    ej = H.scaled_err(gj, j, abs_j).max() * 2.0 ** 24
+    print(f"{what}: acc max rel {ea:.3e} (bound {acc_tol:.1e}); jerk max scaled {ej:.2f} x 2^-24 (bound C = {c:.2f})")
+    return ea, ej
+
+
+@pytest.mark.parametrize("scheme", ["galaxy", "random"])
+@pytest.mark.parametrize("n", [2048, 2049, 4000, 12001, 30000])
+def test_sweep_accelerations_vs_fp64(gpu, O, scheme, n):
+    s, a, j, abs_j, c = _case(scheme, n)
+    ea, _ = check_acc_jerk(O, gpu_acc_jerk(gpu, s), s, a, j, abs_j, c, f"{scheme} {n}")
+    assert O.rel_err(a, O.accel_f64(s, SOFT)).max() < 1e-12     # the yardstick is the oracle's direct sum
+    assert ea <= TOL_F64_MAX
+
+
+@pytest.mark.parametrize("scheme", ["galaxy", "random"])
+@pytest.mark.parametrize("n", [2048, 2049, 4000, 12001, 30000])
+def test_sweep_jerks_vs_fp64(gpu, O, scheme, n):
+    s, a, j, abs_j, c = _case(scheme, n)
+    _, ej = check_acc_jerk(O, gpu_acc_jerk(gpu, s), s, a, j, abs_j, c, f"{scheme} {n}")
+    assert ej <= c
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 63, 513])
+def test_tiny_and_ragged_sizes(gpu, O, n):
+    s, a, j, abs_j, c = _case("random", n)
+    got = gpu_acc_jerk(gpu, s)
+    if n == 1:
+        assert all(float(x[0]) == 0.0 for x in got[0] + got[1])     # the self term is exactly 0 in both sums
+        return
+    ea, ej = check_acc_jerk(O, got, s, a, j, abs_j, c, f"random {n}")
+    assert ea <= TOL_F64_MAX and ej <= c
+    with gpu.Simulation(n, soft=SOFT) as sim:      # and a few steps run
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        sim.steps(DT, 3)
+        st = sim.state()
+    ref = H.hermite_f64(s, 3, SOFT, DT, state32=True)
+    scale = max(np.abs(ref[k]).max() for k in Q)
+    assert all(np.abs(st[k] - ref[k]).max() <= TOL_POS * scale for k in Q)
+
+
+def test_massless_bodies_pull_nothing_and_add_no_jerk(gpu, O):
+    n = 1500
+    s = O.init_bodies(n, "galaxy")
+    s2 = {k: np.concatenate([v, O.init_bodies(7, "random")[k]]) for k, v in s.items()}
+    s2["m"][n:] = 0
+    (a, j), (a2, j2) = gpu_acc_jerk(gpu, s), gpu_acc_jerk(gpu, s2)
+    assert all(np.array_equal(bits(x), bits(y[:n])) for x, y in zip(a + j, a2 + j2))
+
+
+@pytest.mark.parametrize("soft", [1e3, 1e6, 1e7, 1e10])
+def test_other_softening_lengths(gpu, O, soft):
+    """The softening lengths of test_gpu_parity.test_other_softening_lengths; both bounds as for the default one:
+    accelerations within 2e-6 of fp64, jerks within C * 2^-24."""
+    n = 3000
+    s, a, j, abs_j, c = _case("galaxy", n, float(np.float32(soft)))
+    soft = np.float32(soft)
+    ea, ej = check_acc_jerk(O, gpu_acc_jerk(gpu, s, soft), s, a, j, abs_j, c, f"soft {soft:.0e}")
+    assert ea <= TOL_F64_MAX
+    assert ej <= c
+
+
+@pytest.mark.parametrize("scheme", ["random", "galaxy"])
+def test_corrector_bit_exact(gpu, O, scheme):
+    """The integrator alone (the standard of test_integrator_bit_exact): with the device's own fp32 a0, j0, a1, j1 the
+    numpy fp64 restatement of the corrector reproduces q and v bit for bit; the predictor, which only feeds the sweep,
+    is pinned through a1 = the device's evaluation at the restated prediction (second context)."""
+    n = 4000
+    s = O.init_bodies(n, scheme)
+    with gpu.Simulation(n, soft=SOFT) as sim:
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        q = np.stack([s[k] for k in Q]).astype(np.float64)
+        v = np.stack([s[k] for k in V]).astype(np.float64)
+        for step in range(3):
+            sim.compute_acc_jerk()
+            a0, j0 = np.stack(sim.acc()), np.stack(sim.jerk())
+            sim.step(DT)
+            a1, j1 = np.stack(sim.acc()), np.stack(sim.jerk())
+            st = sim.state()
+            q1, v1 = H.correct(q, v, a0, j0, a1, j1, DT)
+            for i, (qk, vk) in enumerate(zip(Q, V)):
+                assert np.array_equal(bits(st[qk]), bits(q1[i])), f"{qk} differs at step {step}"
+                assert np.array_equal(bits(st[vk]), bits(v1[i])), f"{vk} differs at step {step}"
+            if step == 0:   # the sweep saw exactly the restated prediction
+                qp, vp = H.predict(q, v, a0, j0, DT)
+                p = dict(s, **{k: qp[i].astype(np.float32) for i, k in enumerate(Q)}, **{k: vp[i].astype(np.float32) for i, k in enumerate(V)})
+                pa, pj = gpu_acc_jerk(gpu, p)
+                assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(pa + pj, tuple(a1) + tuple(j1)))
+            q, v = q1, v1
+
+
+@pytest.mark.parametrize("scheme,n", [("galaxy", 2048), ("random", 2049), ("galaxy", 4000), ("galaxy", 30000)])
+def test_trajectory_vs_restatement(gpu, O, scheme, n):
+    steps = 5 if n <= 5000 else 2
+    s = O.init_bodies(n, scheme)
+    ref = H.hermite_f64(s, steps, SOFT, DT, state32=True)
+    with gpu.Simulation(n, soft=SOFT) as sim:
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        sim.steps(DT, steps)
+        st = sim.state()
+        st2 = sim.state()
+    assert all(np.array_equal(bits(st[k]), bits(st2[k])) for k in st)
+    scale = max(np.abs(ref[k]).max() for k in Q)
+    vscale = max(np.abs(ref[k]).max() for k in V)
+    eq = max(np.abs(st[k] - ref[k]).max() for k in Q) / scale
+    ev = max(np.abs(st[k] - ref[k]).max() for k in V) / vscale
+    print(f"{scheme} {n}: {steps} steps, positions off by {eq:.3e} of the scale, velocities by {ev:.3e}")
+    assert eq <= TOL_POS and ev <= TOL_VEL[scheme]
+
+
+def test_hermite_conserves_energy(gpu, O):
+    """Same inputs, span and bounds as test_gpu_parity.test_leapfrog_conserves_energy: 100 one-hour steps of the
+    30 000-body galaxy, energy within 2e-5, angular momentum within 1e-5."""
+    n = 30000
+    s = O.init_bodies(n, "galaxy")
+    with gpu.Simulation(n, soft=SOFT) as sim:
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        e0 = sum(sim.energy())
+        L0 = sim.moments()["L"]
+        sim.steps(DT, 100)
+        e1 = sum(sim.energy())
+        L1 = sim.moments()["L"]
+    de, dL = abs(e1 - e0) / abs(e0), np.linalg.norm(L1 - L0) / np.linalg.norm(L0)
+    print(f"N = 30000, 100 x 3600 s: relative energy drift {de:.3e}, angular momentum drift {dL:.3e}")
+    assert de < 2e-5 and dL < 1e-5
+
+
+@pytest.mark.parametrize("steps,dt", [(100, 3600.0), (25, 14400.0)])
+def test_hermite_beats_the_leapfrog_restatement(gpu, O, steps, dt):
+    """The order: N = 2 048 galaxy over 360 000 s.  The GPU Hermite run's relative energy drift is at most 1/20 of the
+    drift of the CPU leapfrog restatement (oracle.leapfrog) on the same inputs at the same dt; energies of both from
+    the states, with oracle.energy_f64.  (A numpy experiment at N = 1 024, fp32 state: 2.0e-6 vs 9.1e-9 at 3600 s,
+    3.2e-5 vs 2.1e-8 at 14 400 s; the factor 20 leaves a tenfold margin for the other N and the GPU's force rounding.)"""
+    n, dt = 2048, np.float32(dt)
+    s = O.init_bodies(n, "galaxy")
+    e0 = sum(O.energy_f64(s, SOFT))
+    lf = {k: v.copy() for k, v in s.items()}
+    O.leapfrog(lf, steps, SOFT, dt)
+    drift_lf = abs(sum(O.energy_f64(lf, SOFT)) - e0) / abs(e0)
+    with gpu.Simulation(n, soft=SOFT) as sim:
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        sim.steps(dt, steps)
+        st = sim.state()
+    h = dict(s, **st)
+    drift_h = abs(sum(O.energy_f64(h, SOFT)) - e0) / abs(e0)
+    print(f"N = 2048, {steps} x {float(dt):.0f} s: energy drift CPU leapfrog {drift_lf:.3e}, GPU Hermite {drift_h:.3e}, "
+          f"ratio {drift_lf / max(drift_h, 1e-300):.1f}")
+    assert drift_h <= drift_lf / 20.0
+
+
+@pytest.mark.parametrize("n", [4000, 20000])
+def test_remembered_evaluation_changes_nothing(gpu, O, n):
+    """compute_acc_jerk + step == step, bit for bit, whatever else is asked in between; and the ADVICE sequence
+    energy -> upload -> energy returns the energy of the NEW bodies."""
+    s = O.init_bodies(n, "galaxy")
+    with gpu.Simulation(n, soft=SOFT) as plain, gpu.Simulation(n, soft=SOFT) as mixed:
+        for sim in (plain, mixed):
+            sim.set_option("integrator", 2)
+            sim.upload(s)
+        plain.steps(DT, 4)
+        for k in range(4):
+            mixed.compute_acc_jerk(); mixed.compute_acc_jerk()
+            aj = mixed.acc() + mixed.jerk()
+            mixed.energy(); mixed.moments(); mixed.state(); mixed.compute_acc()
+            again = mixed.jerk()
+            assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(aj[3:], again))
+            mixed.compute_acc_jerk()             # acc() is this evaluation's again, whatever used the buffer in between
+            assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(aj[:3], mixed.acc()))
+            mixed.step(DT)
+        a, b = plain.state(), mixed.state()
+        for k in a:
+            assert np.array_equal(bits(a[k]), bits(b[k])), k
+        # energy -> upload -> energy: nothing remembered may survive the upload
+        s2 = O.init_bodies(n, "random")
+        e_old = sum(mixed.energy())
+        mixed.upload(s2)
+        with pytest.raises(gpu.MurbHipError):
+            mixed.jerk()                         # no acc + jerk evaluation is current after an upload
+        e_new = sum(mixed.energy())
+        want = sum(O.energy_f64(s2, SOFT))
+        assert abs(e_new - want) <= 1e-5 * abs(want) and abs(e_old - want) > 1e-3 * abs(want)
+        mixed.integrate_host_acc(mixed.acc(), DT)
+        with pytest.raises(gpu.MurbHipError):
+            mixed.jerk()
+
+
+def test_switching_integrators_mid_run(gpu, O):
+    n = 3000
+    s = O.init_bodies(n, "galaxy")
+    with gpu.Simulation(n, soft=SOFT) as sim, gpu.Simulation(n, soft=SOFT) as other:
+        sim.set_option("integrator", 2)
+        sim.upload(s)
+        sim.steps(DT, 2)
+        mid = sim.state()
+        sim.set_option("integrator", 0)          # whole-step velocities: allowed at any time
+        sim.steps(DT, 2)
+        with pytest.raises(gpu.MurbHipError):
+            sim.jerk()                           # the other integrator's steps dropped (a0, j0)
+        mid2 = sim.state()
+        sim.set_option("integrator", 2)
+        sim.steps(DT, 2)
+        end = sim.state()
+        # the same in pieces, each from an upload of the previous piece's state
+        other.upload(dict(s, **mid))
+        other.steps(DT, 2)
+        got = other.state()
+        assert all(np.array_equal(bits(got[k]), bits(mid2[k])) for k in got)
+        other.set_option("integrator", 2)
+        other.upload(dict(s, **mid2))
+        other.steps(DT, 2)
+        got = other.state()
+        assert all(np.array_equal(bits(got[k]), bits(end[k])) for k in got)
+        with pytest.raises(gpu.MurbHipError):
+            sim.set_option("integrator", 3)
+
+
+def test_sharded_context_refuses_hermite(gpu, O):
+    n = 3000
+    s = O.init_bodies(n, "galaxy")
+    ref = {k: v.copy() for k, v in s.items()}
+    O.simulate(ref, 2, "cpu+optim", SOFT, DT)
+    with gpu.Simulation(n, soft=SOFT, devices=[0, 0, 0]) as sim:
+        sim.upload(s)
+        with pytest.raises(gpu.MurbHipError) as err:
+            sim.set_option("integrator", 2)
+        assert err.value.code == -2001
+        with pytest.raises(gpu.MurbHipError):
+            sim.compute_acc_jerk()
+        sim.set_option("integrator", 0)          # the context stays usable
+        sim.steps(DT, 2)
+        st = sim.state()
+    for k in Q:
+        np.testing.assert_allclose(st[k], ref[k], rtol=TOL_POS, atol=1.0)
+
+
+def test_plugin_matches_the_c_abi(gpu, O, tmp_path):
+    """`hip+hermite` through murbhost_tracking_create (metrics every iteration, warm-up in the constructor) lands on the
+    bits of a bare C-ABI run."""
+    n, iters = 2048, 4
+    with gpu.HostSim(n, "galaxy", SOFT, DT, tracking=True, integrator=2) as sim:
+        sim.step(iters)
+        hist = sim.history()
+        got = sim.state()
+        sim.save_history_csv(tmp_path / "m.csv")
+    assert len(hist["energy"]) == iters and len((tmp_path / "m.csv").read_text().splitlines()) == iters + 1
+    s = gpu.init_bodies(n, "galaxy")
+    with gpu.Simulation(n, soft=SOFT) as ref:
+        ref.set_option("integrator", 2)
+        ref.upload(s)
+        ref.steps(DT, iters)
+        want = ref.state()
+    for k in want:
+        assert np.array_equal(bits(got[k]), bits(want[k])), k
+    assert abs(hist["energy"][-1] - hist["energy"][0]) < 1e-5 * abs(hist["energy"][0])
+    # the old keyword still selects the leapfrog
+    with gpu.HostSim(n, "galaxy", SOFT, DT, tracking=True, leapfrog=True) as lf:
+        lf.step(1)
+        assert len(lf.history()["energy"]) == 1
+
+
+def test_murb_hip_cli_hermite(gpu, tmp_path):
+    import re
+    exe = os.path.join(ROOT, "nbody-eurohpc_amd", "bin", "murb-hip")
+    csv = tmp_path / "m.csv"
+    r = subprocess.run([exe, "-n", "2048", "-i", "5", "--nv", "--im", "hip+hermite", "--gf", "--csv", str(csv)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert "  -> implementation    (--im  ): hip+hermite" in r.stdout
+    assert re.search(r"Entire simulation took ([0-9.e+]+) ms \(([0-9.e+]+) FPS, +([0-9.]+) Gflop/s\)", r.stdout), r.stdout
+    rows = csv.read_text().splitlines()
+    assert len(rows) == 6
+    e = [float(x.split(",")[1]) for x in rows[1:]]
+    assert abs(e[-1] - e[0]) < 1e-5 * abs(e[0])
+    h = subprocess.run([exe, "-h"], capture_output=True, text=True, timeout=60)
+    assert "hip+hermite" in h.stdout + h.stderr
