@@ -188,6 +188,33 @@ int murbhip_compute_acc_jerk(murbhip_ctx* ctx);
  * another integrator). */
 int murbhip_download_jerk(murbhip_ctx* ctx, float* jx, float* jy, float* jz);
 
+/* Advance the bodies by `duration` seconds of model time with Hermite steps ("integrator" 2) whose common size the device
+ * chooses (Makino & Aarseth 1992; Aarseth's criterion).  All bodies take the same step.  With |x| the Euclidean norm, (a0, j0)
+ * and (a1, j1) the evaluations at both ends of the step of size dt just taken, for every real body (massless ones included)
+ *     a2 = (-6 (a0 - a1) - dt (4 j0 + 2 j1)) / dt^2     a3 = (12 (a0 - a1) + 6 dt (j0 + j1)) / dt^3     a2 += dt a3
+ *     dt_i = sqrt( eta (|a1| |a2| + |j1|^2) / (|j1| |a3| + |a2|^2) )
+ * and the next step is min_i dt_i clamped to [dt_min, dt_max]; a dt_i that is not a finite positive number (0/0 for a lone
+ * body) counts as +inf.  The first step of a call that finds no proposal — the remembered (a0, j0) were not left by an
+ * adaptive step — is eta_start * min_i |a0| / |j0|, clamped likewise.  A candidate >= duration - t becomes
+ * (float)(duration - t): that step is the last, and the clock is set to `duration` exactly.  No growth limiter.  The
+ * criterion is evaluated in fp64 without contraction in the order fixed in csrc/murb_kernels_hermite.h
+ * (murb_evolve_body_step), and the chosen step is rounded once to fp32; the steps themselves are murbhip_step's,
+ * bit for bit.  Step size, clock and the end of the run live on the device: the host enqueues batches of steps and looks
+ * at the control block once per batch (one stream sync), so the call returns after a sync.
+ *   out5 = { model time advanced, steps taken, smallest step, largest step, the clamped step proposed for the next one }.
+ * max_steps ends the run early with code 0 and out5[0] < duration.  The remembered (a1, j1) serve the next step or the
+ * next call like a Hermite step's (murbhip_download_acc / murbhip_download_jerk return them), together with the proposal;
+ * any other change of the bodies drops all three.  murbhip_step and murbhip_evolve may be mixed.
+ * MURBHIP_E_STATE unless "integrator" is 2 and the context has one shard; MURBHIP_E_INVALID for duration <= 0, eta <= 0,
+ * eta_start <= 0, a dt_max that is not finite or <= 0, dt_min < 0, dt_min > dt_max, max_steps == 0. */
+int murbhip_evolve(murbhip_ctx* ctx, double duration, double eta, double eta_start, float dt_min, float dt_max,
+                   unsigned long max_steps, double* out5);
+
+/* The step sizes the last murbhip_evolve used, oldest first.  The device keeps the last 4096 of a call; *count = how many
+ * are kept (dts may be NULL to ask for the count alone; MURBHIP_E_INVALID when capacity is smaller).  Waits for enqueued
+ * work. */
+int murbhip_evolve_dts(murbhip_ctx* ctx, float* dts, unsigned long capacity, unsigned long* count);
+
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
  * §4.5) — as long as the reference's whole 200-iteration run at N = 30 000.  Construction is outside the reference's timing
@@ -227,7 +254,10 @@ int murbhip_sync(murbhip_ctx* ctx);
  * schedule, the kinetic energy its own bodies: sum both over the ranks; the call is a collective (the force evaluation
  * contains the reduce-scatter) unless the forces of the current positions are already remembered.
  * One-sided plan (below 2 049 bodies; few bodies per rank) or option "energy_sweep" 1: one N^2 potential sweep on the device
- * (phi_i = sum_j G m_j / r), then -1/2 sum m_i phi_i; values cover the caller's own bodies.
+ * (phi_i = sum_j G m_j / r), then -1/2 sum m_i phi_i; values cover the caller's own bodies.  On the one-sided plan the
+ * sweep leaves a body's own term G m_i / soft out of its sum (by slot), instead of removing it from the fp32 total as the
+ * reference does (.cu:287-294): with a small softening that term is orders of magnitude above the others (1e4 x for two
+ * bodies of 1e30 kg 1e10 m apart at soft = 1e6 m) and took the low bits of the pair terms with it.
  * The per-body terms are summed in fp64 on the device (256-body block sums in a fixed order; the host adds the few hundred
  * block rows); waits for enqueued steps. */
 int murbhip_energy(murbhip_ctx* ctx, double* kinetic, double* potential);
@@ -298,7 +328,11 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    velocities of ALL bodies, which sharded and rank-mode contexts keep for their own slice alone
  *                    (they exchange positions, never velocities), so on a context of several shards or ranks, or
  *                    with "force_exchange" set, the value 2 is refused with MURBHIP_E_STATE (and "force_exchange"
- *                    is refused while the value is 2)
+ *                    is refused while the value is 2).  murbhip_evolve drives the same steps with sizes the device chooses
+ *   "evolve_batch"   murbhip_evolve: steps enqueued between two looks at the device's control block.  0 (default) = as
+ *                    many as the remaining time takes at the step last seen, 64 at the most; 1..64 = exactly that many
+ *                    (timing aid: a batch longer than the run needs ends in launches that find the done flag set and do
+ *                    nothing, which tools/hermite_adaptive_rate.py times).  The results do not depend on it
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real

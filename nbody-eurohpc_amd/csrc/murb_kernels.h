@@ -208,8 +208,18 @@ __device__ __forceinline__ void murb_force_body(const MurbForceArgs& a, float4* 
                             murb_interact_pk(xj, yj, zj, gj, xi[r], yi[r], zi[r], soft2, ax[r], ay[r], az[r]);
                     } else if (MODE == MURB_MODE_PHI) {
                         const murb_f2 xj = {A.x, A.y}, yj = {A.z, A.w}, zj = {B.x, B.y}, gj = {B.z, B.w};
+                        // A body's own term G m_i / soft stays out of its sum (by slot, not by distance): with a small
+                        // softening it is orders of magnitude above all the others and would take their low bits in fp32
+                        const int jp = murb_actual_tile(a.tiles, vs + t) * MURB_TILE_PAIRS + q + lane;   // the lane's pair of j slots
 #pragma unroll
-                        for (int r = 0; r < R; ++r) murb_interact_phi(xj, yj, zj, gj, xi[r], yi[r], zi[r], soft2, ax[r]);
+                        for (int r = 0; r < R; ++r) {
+                            murb_f2 g = gj;
+                            if (jp == ((i_slot + r) >> 1)) {
+                                if ((i_slot + r) & 1) g.y = 0.f;
+                                else g.x = 0.f;
+                            }
+                            murb_interact_phi(xj, yj, zj, g, xi[r], yi[r], zi[r], soft2, ax[r]);
+                        }
                     } else {
 #pragma unroll
                         for (int r = 0; r < R; ++r) {
@@ -524,7 +534,7 @@ __global__ __launch_bounds__(WAVES * 64) void murb_force_integrate_kernel(const 
 // Tracked metrics: the O(N) sums of murbhip_energy / murbhip_moments on the device (the reference reduces
 // its per-body energy with cub::DeviceReduce::Sum, SimulationNBodyCUDAPropertyTracking.cu:330-356).
 // Per body, in fp64:  kinetic 1/2 m v^2 ; potential -1/2 m (phi - G m / soft) (self term of the sweep
-// removed, .cu:287-294) ; m v ; m q x v ; m q ; m.  One block = 256 consecutive slots of the rank's slice;
+// removed, .cu:287-294; g_over_soft = 0 where the sweep left it out itself) ; m v ; m q x v ; m q ; m.  One block = 256 consecutive slots of the rank's slice;
 // the 12 block sums are written in a fixed order (wave shuffle tree, then the 4 waves through LDS) and the
 // host adds the few hundred block rows in index order: bit-reproducible.
 #define MURB_METRIC_VALUES 12
@@ -538,7 +548,7 @@ struct MurbMetricsArgs {
     int i_first_slot, count;
     unsigned int acc_stride;
     float half_dt;          // leapfrog read-out: v_n = v_{n-1/2} + a * half_dt (0: velocities are current)
-    double g_over_soft;     // G / soft
+    double g_over_soft;     // G / soft where phi contains the bodies' own terms, 0 where the sweep left them out
 };
 
 __global__ __launch_bounds__(256) void murb_metrics_kernel(const MurbMetricsArgs a)

@@ -129,6 +129,8 @@ struct Shard {
     float* herm_j0 = nullptr;       // jx | jy | jz of it
     float4* herm_part = nullptr;    // partial rows of the sweep: herm_rows rows of accelerations, then as many of jerks
     int herm_rows = 0;
+    MurbEvolveCtl* herm_ctl = nullptr;        // murbhip_evolve's control block (device), allocated on first use
+    MurbEvolveCtl* herm_ctl_host = nullptr;   // pinned copy of its head (everything in front of the ring)
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -175,9 +177,12 @@ struct murbhip_ctx {
     int tri_first_pct = 50;   // overlap 1: share of the own-slice triangle launched BEFORE the rectangles (under the
                               // position gather); the rest runs under the reduce-scatter
     int xcd_order = 0;        // pair-symmetric kernel: 1 = item table interleaved into one run per XCD (measured worse)
+    int evolve_batch = 0;     // murbhip_evolve: steps per batch; 0 = from the remaining time over the step last seen
     int integrator = 0;       // 0 the reference's update (Bodies.cpp:260-278), 1 kick-drift-kick leapfrog, 2 4th-order Hermite
     bool herm_current = false;// Hermite: herm_a0 / herm_j0 hold the evaluation the next step starts from
     bool herm_in_acc_out = false;   // ... and acc_out still holds its accelerations (no force evaluation has run since)
+    bool herm_proposal = false;     // ... and the control block's `raw` is the step murbhip_evolve's criterion proposes from it
+    unsigned long evolve_steps = 0; // steps of the last murbhip_evolve (what murbhip_evolve_dts reads from the ring)
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)
@@ -1148,6 +1153,7 @@ void invalidate_cached_forces(murbhip_ctx* c)
     c->acc_current = false;
     c->pe_current = false;
     c->herm_current = false;
+    c->herm_proposal = false;
     ++c->state_serial;
 }
 
@@ -1319,6 +1325,44 @@ int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
     invalidate_cached_forces(c);
     c->herm_current = true;   // (a1, j1) of this step are the next step's (a0, j0)
     c->herm_in_acc_out = true;
+    return 0;
+}
+
+// ---- shared adaptive steps (murbhip_evolve; control block and kernels: murb_kernels_hermite.h) --------------------------
+constexpr int kEvolveBatch = 64;                              // steps enqueued between two looks at the control block
+constexpr size_t kEvolveHead = offsetof(MurbEvolveCtl, ring);   // what the host reads back after a batch
+
+// One adaptive step: enqueue_hermite's three launches in their control-block form, and the bookkeeping launch.  Whether
+// the device still takes the step or has finished, the records end up in the other position buffer.
+int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
+{
+    const unsigned pairs = (unsigned)(c->slots / 2);
+    MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 1);
+    a.rec_out = sh.herm_rec;
+    a.vel_out = sh.herm_vel;
+    hipLaunchKernelGGL(murb_hermite_predict_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
+    RC_TRY(hip_rc(hipGetLastError()));
+    MurbJerkArgs j{};
+    j.rec = sh.herm_rec;
+    j.vel = sh.herm_vel;
+    j.part_a = sh.herm_part;
+    j.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
+    j.tiles = (int)(c->slots / MURB_TILE_BODIES);
+    j.nchunks = parts;
+    j.stride = (unsigned int)c->slots;
+    j.soft2 = c->soft2;
+    constexpr int group = kHermiteWaves * kHermiteR;
+    const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);
+    hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0,
+                       sh.compute, j, sh.herm_ctl);
+    RC_TRY(hip_rc(hipGetLastError()));
+    a.rec_out = sh.rec[c->cur ^ 1];
+    a.vel_out = nullptr;
+    hipLaunchKernelGGL(murb_hermite_correct_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
+    RC_TRY(hip_rc(hipGetLastError()));
+    hipLaunchKernelGGL(murb_evolve_book_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl);
+    RC_TRY(hip_rc(hipGetLastError()));
+    c->cur ^= 1;
     return 0;
 }
 
@@ -1627,7 +1671,8 @@ int murbhip_destroy(murbhip_ctx* c)
         for (hipStream_t* q : {&sh.compute_low, &sh.compute, &sh.comm}) release_stream(*q);
         release(sh.rec[0], sh.rec[1], sh.vel, sh.accp, sh.acc_out, sh.phi_out, sh.mass, sh.radius, sh.metrics);
         if (sh.metrics_host) (void)hipHostFree(sh.metrics_host);
-        release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part);
+        release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part, sh.herm_ctl);
+        if (sh.herm_ctl_host) (void)hipHostFree(sh.herm_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
         free_sym_set(sh.sym_main); free_sym_set(sh.sym_tri);
     }
@@ -1895,6 +1940,94 @@ int murbhip_download_jerk(murbhip_ctx* c, float* jx, float* jy, float* jz)
     return 0;
 }
 
+int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start, float dt_min, float dt_max,
+                   unsigned long max_steps, double* out5)
+{
+    if (!c || !out5) return MURBHIP_E_INVALID;
+    if (!(duration > 0.0) || !std::isfinite(duration) || !(eta > 0.0) || !(eta_start > 0.0) || !std::isfinite(dt_max) ||
+        !(dt_max > 0.f) || !(dt_min >= 0.f) || dt_min > dt_max || max_steps == 0)
+        return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->integrator != 2) return MURBHIP_E_STATE;
+    RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
+    Shard& sh = c->shards[0];
+    if (!sh.herm_ctl) {
+        HIP_TRY(hipMalloc((void**)&sh.herm_ctl, sizeof(MurbEvolveCtl)));
+        sh.bytes += sizeof(MurbEvolveCtl);
+    }
+    if (!sh.herm_ctl_host) HIP_TRY(hipHostMalloc((void**)&sh.herm_ctl_host, kEvolveHead, hipHostMallocDefault));
+    const int parts = hermite_parts(c);
+    const unsigned pairs = (unsigned)(c->slots / 2);
+    const int fresh = c->herm_proposal ? 0 : 1;
+    hipLaunchKernelGGL(murb_evolve_begin_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl, duration, eta, dt_min, dt_max,
+                       (unsigned long long)max_steps, fresh);
+    RC_TRY(hip_rc(hipGetLastError()));
+    if (fresh) {
+        const MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 0);
+        hipLaunchKernelGGL(murb_evolve_first_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl, eta_start);
+        RC_TRY(hip_rc(hipGetLastError()));
+        hipLaunchKernelGGL(murb_evolve_start_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl);
+        RC_TRY(hip_rc(hipGetLastError()));
+    }
+    c->evolve_steps = 0;
+    // Batches: as many steps as the remaining time takes at the step last seen, kEvolveBatch at the most; a step that
+    // grows leaves a tail of no-op launches, one that shrinks another batch.  The first batch of a call without a
+    // proposal knows no step yet and is short.
+    MurbEvolveCtl& head = *sh.herm_ctl_host;
+    unsigned long batch = 4;
+    if (!fresh) {
+        HIP_TRY(hipMemcpyAsync(&head, sh.herm_ctl, kEvolveHead, hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        batch = 0;
+    }
+    for (;;) {
+        if (batch == 0) {   // from the head just read
+            const double est = std::ceil((head.duration - head.t) / (double)std::max(head.dt, 1e-30f));
+            batch = (unsigned long)std::min<double>(std::max(est, 1.0), (double)kEvolveBatch);
+            batch = (unsigned long)std::min<unsigned long long>(batch, head.max_steps - head.steps);
+        }
+        batch = std::min<unsigned long>(batch, max_steps);
+        if (c->evolve_batch > 0) batch = (unsigned long)c->evolve_batch;   // timing aid: fixed length, no-op tail and all
+        int rc = 0;
+        for (unsigned long k = 0; k < batch && rc == 0; ++k) rc = enqueue_hermite_adaptive(c, sh, parts);
+        // the bodies changed whatever happens next; (a1, j1) of the last step taken and its proposal stay with them
+        invalidate_cached_forces(c);
+        c->herm_current = true;
+        c->herm_in_acc_out = true;
+        c->herm_proposal = true;
+        RC_TRY(rc);
+        HIP_TRY(hipMemcpyAsync(&head, sh.herm_ctl, kEvolveHead, hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (c->async_error) return c->async_error;
+        if (head.done) break;
+        batch = 0;
+    }
+    c->evolve_steps = (unsigned long)head.steps;
+    out5[0] = head.t;
+    out5[1] = (double)head.steps;
+    out5[2] = (double)head.used_min;
+    out5[3] = (double)head.used_max;
+    out5[4] = (double)head.prop;
+    return 0;
+}
+
+int murbhip_evolve_dts(murbhip_ctx* c, float* dts, unsigned long capacity, unsigned long* count)
+{
+    if (!c || !count || (!dts && capacity)) return MURBHIP_E_INVALID;
+    if (!c->uploaded) return MURBHIP_E_STATE;
+    const unsigned long kept = std::min<unsigned long>(c->evolve_steps, MURB_EVOLVE_RING);
+    *count = kept;
+    if (!dts || kept == 0) return 0;
+    if (capacity < kept) return MURBHIP_E_INVALID;
+    Shard& sh = c->shards[0];
+    RC_TRY(murbhip_sync(c));
+    HIP_TRY(hipSetDevice(sh.device));
+    std::vector<float> ring(MURB_EVOLVE_RING);
+    HIP_TRY(hipMemcpy(ring.data(), sh.herm_ctl->ring, ring.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const unsigned long first = c->evolve_steps - kept;   // oldest step kept
+    for (unsigned long k = 0; k < kept; ++k) dts[k] = ring[(first + k) % MURB_EVOLVE_RING];
+    return 0;
+}
+
 int murbhip_warmup(murbhip_ctx* c, double milliseconds)
 {
     if (!c || !(milliseconds >= 0.0) || milliseconds > 10000.0) return MURBHIP_E_INVALID;
@@ -1971,7 +2104,8 @@ int ensure_acc_for_readout(murbhip_ctx* c)
 // The O(N) sums of the tracked metrics over this process's bodies (murb_metrics_kernel + the block rows added
 // in index order on the host).  want_phi: the potential sweep has just been written to phi_out.  pair_sum: also add up
 // the pair potentials murbhip_energy has just enqueued into the buffers' tails (then the kept sums are not enough).
-int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VALUES], double* pair_sum = nullptr)
+int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VALUES], double* pair_sum = nullptr,
+                   bool phi_has_self = true)
 {
     if (!pair_sum && c->metrics_serial == c->state_serial && (c->metrics_with_phi || !want_phi)) {   // same state, sums already here
         RC_TRY(murbhip_sync(c));
@@ -1997,7 +2131,7 @@ int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VAL
         a.count = (int)sh.count;
         a.acc_stride = (unsigned int)c->slice;
         a.half_dt = c->lf_half ? 0.5f * c->lf_last_dt : 0.f;
-        a.g_over_soft = (double)c->g / std::sqrt((double)c->soft2);
+        a.g_over_soft = phi_has_self ? (double)c->g / std::sqrt((double)c->soft2) : 0.0;
         hipLaunchKernelGGL(murb_metrics_kernel, dim3((unsigned)l.blocks), dim3(256), 0, sh.compute, a);
         RC_TRY(hip_rc(hipGetLastError()));
         // the read-out rides behind the kernels on the same stream, into pinned memory: one wait for everything
@@ -2072,9 +2206,10 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
         *potential = -pair_sum / (double)c->g;
         return 0;
     }
-    // phi_i = sum_j GM_j / sqrt(r_ij^2 + soft^2) over ALL j (self term included), written to the x plane of phi_out:
-    // pair-symmetric sweep where the force plan is pair-symmetric (one GPU: one launch; several ranks: the half-ring
-    // schedule with its reduce-scatter), the one-sided sweep otherwise
+    // phi_i = sum_j GM_j / sqrt(r_ij^2 + soft^2), written to the x plane of phi_out: pair-symmetric sweep where the force
+    // plan is pair-symmetric (one GPU: one launch; several ranks: the half-ring schedule with its reduce-scatter; over ALL
+    // j, self term included and removed by the metrics kernel), the one-sided sweep otherwise (j != i: the sweep leaves
+    // the self term out itself, murb_force_body)
     RC_TRY(ensure_acc_for_readout(c));   // before the sweep: it reuses the one-sided partial rows
     Plan p{};
     p.variant = kPotentialKernel;
@@ -2129,7 +2264,7 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
         RC_TRY(enqueue_integrate(c, sh, p.parts_local + p.parts_remote, 0.f, 0, nullptr, -1, sh.phi_out));
     }
     double sums[MURB_METRIC_VALUES];
-    RC_TRY(device_metrics(c, true, sums));
+    RC_TRY(device_metrics(c, true, sums, nullptr, main_plan.symmetric));
     *kinetic = sums[0];
     *potential = sums[1];
     return 0;
@@ -2176,6 +2311,10 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
         if (value == 2 && (c->world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
         c->integrator = (int)value;
+    }
+    else if (k == "evolve_batch") {
+        if (value < 0 || value > kEvolveBatch) return MURBHIP_E_INVALID;
+        c->evolve_batch = (int)value;
     }
     else if (k == "solo_shard") c->solo_shard = (int)value;
     else if (k == "cu_reserve") {

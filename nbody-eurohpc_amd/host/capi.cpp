@@ -73,7 +73,8 @@ void *murbhost_sim_create(unsigned long n, const char *scheme, float soft, float
     h->sim->setDt(dt);
     return h;
 }
-// --im hip+tracking (leapfrog = 0) / hip+leapfrog (1) / hip+hermite (2): the value is murbhip's option "integrator"
+// --im hip+tracking (leapfrog = 0) / hip+leapfrog (1) / hip+hermite (2): the value is murbhip's option "integrator";
+// hip+hermite+adaptive (3): option 2 driven by murbhip_evolve
 void *murbhost_tracking_create(unsigned long n, const char *scheme, float soft, float dt, int leapfrog, int ndev,
                                const int *devices, int exchange)
 {
@@ -115,6 +116,16 @@ int murbhost_history_csv(const char *path, int rows, const double *energy, const
     } catch (const std::runtime_error &) {
         return -1;
     }
+    return 0;
+}
+// hip+hermite+adaptive: {substeps so far, smallest dt, largest dt}.  0, or -1 for a simulation with fixed steps.
+int murbhost_sim_substeps(void *p, double *out3)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->isAdaptive()) return -1;
+    out3[0] = (double)t->getSubsteps();
+    out3[1] = t->getSmallestDt();
+    out3[2] = t->getLargestDt();
     return 0;
 }
 int murbhost_sim_history_csv(void *p, const char *path)

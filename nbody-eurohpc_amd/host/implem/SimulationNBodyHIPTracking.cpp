@@ -1,5 +1,6 @@
 #include "implem/SimulationNBodyHIPTracking.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 #include "murbhip.h"
@@ -9,11 +10,12 @@ SimulationNBodyHIPTracking<T, Q>::SimulationNBodyHIPTracking(const BodiesAllocat
                                                              std::shared_ptr<SimulationHistory<Q>> history, const T soft,
                                                              const int integrator, const std::vector<int> &devices,
                                                              int exchange)
-    : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}
+    : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}, adaptive{integrator == 3}
 {
     if (!this->history) this->history = std::make_shared<SimulationHistory<Q>>();
     if (integrator)
-        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", integrator), "murbhip_set_option(integrator)");
+        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", adaptive ? 2 : integrator),
+                     "murbhip_set_option(integrator)");
 }
 
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::computeMetrics()
@@ -32,7 +34,15 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::computeOneIteration()
 {
     computeMetrics();
-    SimulationNBodyHIP<T>::computeOneIteration();
+    if (adaptive) {   // exactly dt of model time, in the substeps the criterion chooses; returns synchronised
+        double out[5];
+        this->hipBodiesPtr->invalidateDataSoA();
+        murbhipCheck(murbhip_evolve(this->hipBodiesPtr->getContext(), (double)this->dt, eta, 0.01, 0.f, this->dt, 1000000ul, out),
+                     "murbhip_evolve");
+        dtSmallest = substeps ? std::min(dtSmallest, out[2]) : out[2];
+        dtLargest = std::max(dtLargest, out[3]);
+        substeps += (unsigned long)out[1];
+    } else SimulationNBodyHIP<T>::computeOneIteration();
     currentIteration++;
 }
 

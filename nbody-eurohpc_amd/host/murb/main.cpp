@@ -40,7 +40,8 @@ bool ShowGFlops = false;
 int NDevices = 0;        // --ngpu, hip+tile+multi only (0 = all visible)
 bool FreeRunning = false;   // --free: sync once at the end instead of once per iteration
 bool DeviceInit = false;    // --dinit: generate the initial conditions on the device (bit-identical to the host's)
-std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+hermite save their history
+std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+hermite[+adaptive] save their history
+double Eta = 0.02;          // --eta: accuracy parameter of hip+hermite+adaptive's step criterion
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -74,6 +75,8 @@ static std::vector<Option> optionTable()
          "\t\t\t - \"hip+leapfrog\"    hip+tracking with a kick-drift-kick leapfrog integrator\n"
          "\t\t\t - \"hip+hermite\"     hip+tracking with a 4th-order Hermite integrator (its sweep also computes the jerks:\n"
          "\t\t\t                      about twice the arithmetic of the 20 N^2 flops per iteration reported)\n"
+         "\t\t\t - \"hip+hermite+adaptive\"  hip+hermite, every iteration of --dt seconds in as many substeps as the\n"
+         "\t\t\t                      step criterion asks for (--eta)\n"
          "\t\t\t ----"},
         {"-soft", "softeningFactor", false, "softening factor."},
         {"s", "bodies scheme", false, "bodies scheme (initial conditions can be \"galaxy\" or \"random\")."},
@@ -82,6 +85,7 @@ static std::vector<Option> optionTable()
         {"-free", "", false, "free-running timing: one device sync at the end, not one per iteration."},
         {"-dinit", "", false, "generate the initial conditions on the device (same bodies, bit for bit)."},
         {"-csv", "file", false, "hip+tracking / hip+leapfrog / hip+hermite: save the metrics history as CSV."},
+        {"-eta", "accuracy", false, "hip+hermite+adaptive: accuracy parameter of the step criterion (default is 0.02)."},
     };
 }
 
@@ -113,6 +117,13 @@ static void argsReader(int argc, char **argv)
     if (given("s")) BodiesScheme = reader.get_argument("s");
     if (given("-ngpu")) NDevices = stoi(reader.get_argument("-ngpu"));
     if (given("-csv")) MetricsFile = reader.get_argument("-csv");
+    if (given("-eta")) {
+        Eta = stod(reader.get_argument("-eta"));
+        if (!(Eta > 0.0)) {
+            std::cout << "The accuracy parameter --eta must be positive... exiting." << std::endl;
+            exit(-1);
+        }
+    }
     if (given("-soft")) {
         Softening = stof(reader.get_argument("-soft"));
         if (Softening == 0.f) {   // the reference refuses it too (main.cpp:147-150): the self term would be 0/0
@@ -153,11 +164,15 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
         return new SimulationNBodyHIP<T>(hipAllocator, Softening, devices, /*exchange: RCCL when distinct GPUs*/
                                          use <= visible ? 1 : 0);
     }
-    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite") {   // shaped like main.cpp:245-261
+    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite" || ImplTag == "hip+hermite+adaptive") {
+        // shaped like main.cpp:245-261
+        const std::map<std::string, int> integrator = {{"hip+tracking", 0}, {"hip+leapfrog", 1}, {"hip+hermite", 2},
+                                                       {"hip+hermite+adaptive", 3}};
         HIPBodiesAllocator<T> hipAllocator(NBodies, BodiesScheme);
         History = std::make_shared<SimulationHistory<double>>((int)NIterations);
-        return new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening,
-                                                         ImplTag == "hip+leapfrog" ? 1 : (ImplTag == "hip+hermite" ? 2 : 0));
+        auto *tracking = new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening, integrator.at(ImplTag));
+        tracking->setEta(Eta);
+        return tracking;
     }
     std::cout << "Implementation '" << ImplTag << "' does not exist... Exiting." << std::endl;
     exit(-1);
@@ -234,6 +249,9 @@ int main(int argc, char **argv)
     std::cout << "Entire simulation took " << perfTotal.getElapsedTime() << " ms "
               << "(" << perfTotal.getFPS(iIte - 1) << " FPS" << gflops.str() << ")" << std::endl;
 
+    if (const auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu); tracking && tracking->isAdaptive())
+        std::cout << "Adaptive steps: " << tracking->getSubsteps() << " substeps, dt from " << std::setprecision(6)
+                  << tracking->getSmallestDt() << " to " << tracking->getLargestDt() << " sec (eta " << Eta << ")" << std::endl;
     if (History && History->getNumIterations() > 1) {
         const double e0 = History->getEnergyAt(0), e1 = History->getEnergyAt(History->getNumIterations() - 1);
         std::cout << "Energy at the first / last tracked iteration: " << std::setprecision(9) << e0 << " / " << e1

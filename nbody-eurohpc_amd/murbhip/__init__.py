@@ -64,6 +64,9 @@ def lib():
         L.murbhip_compute_acc.argtypes = [C.c_void_p]
         L.murbhip_compute_acc_jerk.argtypes = [C.c_void_p]
         L.murbhip_download_jerk.argtypes = [C.c_void_p] + [_fp] * 3
+        L.murbhip_evolve.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_ulong,
+                                     C.POINTER(C.c_double)]
+        L.murbhip_evolve_dts.argtypes = [C.c_void_p, _fp, C.c_ulong, C.POINTER(C.c_ulong)]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -81,7 +84,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_schedule_items murbhip_schedule_layout "
            "murbhip_device_count murbhip_create murbhip_create_sharded murbhip_unique_id murbhip_create_rank "
            "murbhip_destroy murbhip_upload murbhip_init_bodies murbhip_download_mass murbhip_download_state murbhip_download_acc murbhip_compute_acc "
-           "murbhip_compute_acc_jerk murbhip_download_jerk "
+           "murbhip_compute_acc_jerk murbhip_download_jerk murbhip_evolve murbhip_evolve_dts "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -228,6 +231,23 @@ class Simulation:
     def steps(self, dt, iterations):
         _check(lib().murbhip_steps(self._h, dt, iterations), "murbhip_steps")
 
+    def evolve(self, duration, eta=0.02, eta_start=0.01, dt_min=0.0, dt_max=None, max_steps=1_000_000):
+        """Advance `duration` seconds with Hermite steps whose common size the device chooses (include/murbhip.h:
+        murbhip_evolve; "integrator" must be 2).  dt_max=None means `duration`.  Returns after a sync."""
+        out = (C.c_double * 5)()
+        _check(lib().murbhip_evolve(self._h, duration, eta, eta_start, dt_min, duration if dt_max is None else dt_max,
+                                    max_steps, out), "murbhip_evolve")
+        return {"time": out[0], "steps": int(out[1]), "dt_min": out[2], "dt_max": out[3], "dt_next": out[4]}
+
+    def evolve_dts(self):
+        """float32 array of the step sizes the last evolve() used, oldest first (the last 4096 of them)."""
+        count = C.c_ulong()
+        _check(lib().murbhip_evolve_dts(self._h, None, 0, C.byref(count)), "murbhip_evolve_dts")
+        dts = np.zeros(count.value, np.float32)
+        if count.value:
+            _check(lib().murbhip_evolve_dts(self._h, _ptr(dts), count.value, C.byref(count)), "murbhip_evolve_dts")
+        return dts
+
     def integrate_host_acc(self, acc, dt):
         a = [_f32(x) for x in acc]
         _check(lib().murbhip_integrate_host_acc(self._h, *[_ptr(x) for x in a], dt), "murbhip_integrate_host_acc")
@@ -319,6 +339,7 @@ def host_lib():
         H.murbhost_history_get.argtypes = [C.c_void_p, _dp, _dp, _dp]
         H.murbhost_history_csv.argtypes = [C.c_char_p, C.c_int, _dp, _dp, _dp]
         H.murbhost_sim_history_csv.argtypes = [C.c_void_p, C.c_char_p]
+        H.murbhost_sim_substeps.argtypes = [C.c_void_p, _dp]
         _host = H
     return _host
 
@@ -359,7 +380,8 @@ class HostSim:
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
                  leapfrog=False, integrator=None):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
-        0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`)."""
+        0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
+        driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for)."""
         if integrator is None:
             integrator = int(bool(leapfrog))
         arr = (C.c_int * len(devices))(*devices)
@@ -387,6 +409,11 @@ class HostSim:
 
     def step(self, iterations=1):
         self.H.murbhost_sim_step(self.h, iterations)
+
+    def substeps(self):
+        """integrator=3: (substeps taken so far, smallest dt, largest dt); None for the fixed-step plugins."""
+        out = (C.c_double * 3)()
+        return tuple(out[:]) if self.H.murbhost_sim_substeps(self.h, out) == 0 else None
 
     def init_on_device(self, seed=0):
         """HIPBodies::initOnDevice: the same initial conditions, generated on the device."""
