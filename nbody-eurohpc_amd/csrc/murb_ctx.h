@@ -1,0 +1,184 @@
+// The context behind the C ABI (murbhip_ctx), a shard of it (Shard: one device's streams, buffers and tables), and the small
+// helpers every part of murbhip.hip uses: error codes, releases, the counted allocation of a shard's device buffers.
+#ifndef MURB_CTX_H_
+#define MURB_CTX_H_
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "murb_choose.h"
+#include "murb_crew.h"
+#include "murb_kernels_hermite.h"
+#include "murb_kernels_sym.h"
+#include "murb_rccl.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------ error codes
+inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(int)e; }
+inline int nccl_rc(int r) { return r == 0 ? 0 : -(3000 + r); }   // disjoint from -(hipError_t), which reaches past 1000
+
+// Teardown and error paths: a release that fails cannot be acted on (the context is going away either way).
+template <typename... P> inline void release(P*... p) { ((void)hipFree((void*)p), ...); }
+inline void release_event(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+inline void release_stream(hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; }
+inline void drain(hipStream_t s) { if (s) (void)hipStreamSynchronize(s); }
+
+#define HIP_TRY(expr)                        \
+    do {                                     \
+        const int rc_ = hip_rc((expr));      \
+        if (rc_ != 0) return rc_;            \
+    } while (0)
+#define RC_TRY(expr)                \
+    do {                            \
+        const int rc_ = (expr);     \
+        if (rc_ != 0) return rc_;   \
+    } while (0)
+
+// ------------------------------------------------------------------------------------ context
+// Partial rows of one group of launches (murb_kernels_sym.h): the buffer, and per block the row table its row sum reads
+// (SymPass, the layout and the planner: murb_plan.h).
+struct SymSet {
+    float* part = nullptr;
+    size_t comp_stride = 0;           // floats per component (single pass)
+    MurbSymBlockRows* rows = nullptr; // device copy of the table
+    int nblocks = 0;                  // entries (all passes)
+    std::vector<SymPass> passes;      // more than one entry: multi-pass evaluation
+};
+
+struct Shard {
+    int device = 0;
+    int rank = 0;
+    unsigned long first = 0, count = 0;   // global body range owned
+    hipStream_t compute = nullptr, comm = nullptr;
+    hipStream_t compute_low = nullptr;   // lowest priority: the own-slice triangle in "overlap" mode 2
+    hipEvent_t ev_integrated = nullptr, ev_gathered = nullptr, ev_tri = nullptr;
+    float4* rec[2] = {nullptr, nullptr};
+    float4* vel = nullptr;
+    float4* accp = nullptr;      // one-sided kernels: partial-sum rows, allocated on first use (ensure_accp)
+    float* acc_out = nullptr;
+    float* phi_out = nullptr;    // murbhip_energy's potential sweep (same shape as acc_out), allocated on first use
+    float* mass = nullptr;       // masses of the local slice as uploaded (metrics)
+    float* radius = nullptr;     // radii of the local slice: only after murbhip_init_bodies (the host never sent them)
+    double* metrics = nullptr;   // block sums of murb_metrics_kernel, then murbhip_energy's pair potentials (metrics_doubles)
+    double* metrics_host = nullptr;   // its pinned host copy: the read-out is one asynchronous copy behind the kernels
+    // pair-symmetric kernel: item table and partial-row layouts (built by build_sym_schedule for one plan)
+    MurbSymItem* sym_items = nullptr;
+    int sym_items_own = 0, sym_items_total = 0;   // [0, own) = own-slice triangle, the rest need the gathered positions
+    SymLayoutKey key;                             // what the tables were built for (sym_layout_key)
+    int sym_red = 0;                              // i-side reduction of the plan (kernel template parameter; not part of the tables)
+    int sym_t1 = 0;                               // items of the triangle's first launch (exchange pipeline, overlap 1)
+    SymSet sym_main;             // one GPU: every item; exchange pipeline: the rectangles (-> reduce-scatter send chunks)
+    SymSet sym_tri;              // exchange pipeline: the own-slice triangle (never enters the reduce-scatter)
+    float* sym_send = nullptr;   // [world][3][slice]
+    float* sym_recv = nullptr;   // [3][slice]
+    float* sym_p2p = nullptr;    // "exchange_p2p": chunks received from the floor(W/2) ranks behind this one [floor(W/2)][3][slice]
+    float* sym_tri_acc = nullptr;// row sums of sym_tri [3][slice]
+    double* sym_acc64 = nullptr; // multi-pass evaluation: fp64 row sums accumulated over the passes [3][slots]
+    hipEvent_t ev_rowsum = nullptr, ev_reduced = nullptr;
+    rccl_comm_t comm_rccl = nullptr;
+    std::vector<hipEvent_t> prof;   // pool of timing events ("profile"): two per recorded span
+    size_t prof_used = 0;
+    std::vector<int> prof_kind;     // what span k (events 2k, 2k+1) brackets: ProfKind
+    // Hermite integrator ("integrator" 2; one shard), allocated on first use (ensure_hermite)
+    float4* herm_rec = nullptr;     // predicted positions + GM, all slots
+    float4* herm_vel = nullptr;     // predicted velocities
+    float* herm_a0 = nullptr;       // ax | ay | az of the remembered evaluation
+    float* herm_j0 = nullptr;       // jx | jy | jz of it
+    float4* herm_part = nullptr;    // partial rows of the sweep: herm_rows rows of accelerations, then as many of jerks
+    int herm_rows = 0;
+    MurbEvolveCtl* herm_ctl = nullptr;        // murbhip_evolve's control block (device), allocated on first use
+    MurbEvolveCtl* herm_ctl_host = nullptr;   // pinned copy of its head (everything in front of the ring)
+    unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
+    size_t bytes = 0;
+};
+
+// Device buffers of a shard, allocated on first use and counted in Shard::bytes (info "device_bytes").  `zero_on`: a fresh
+// buffer is also cleared, on that stream.
+template <typename T>
+int shard_alloc(Shard& sh, T*& p, size_t bytes, hipStream_t zero_on = nullptr)
+{
+    if (p) return 0;
+    HIP_TRY(hipMalloc((void**)&p, bytes));
+    sh.bytes += bytes;
+    if (zero_on) HIP_TRY(hipMemsetAsync(p, 0, bytes, zero_on));
+    return 0;
+}
+template <typename T>
+void shard_free(Shard& sh, T*& p, size_t bytes)
+{
+    if (!p) return;
+    release(p);
+    p = nullptr;
+    sh.bytes -= bytes;
+}
+
+constexpr int kPeSumBlocks = 256;      // workgroups of murb_sym_pe_sum_kernel
+constexpr size_t kProfPairs = 4096;
+
+// What a pair of timing events brackets.  "profile" 1: the force launches only (two event records per launch);
+// 2: also the collectives on the exchange stream, the compute stream's waits for them (= the EXPOSED part of the
+// exchange) and the compute stream's whole step.
+enum ProfKind {
+    kProfForce = 0,       // a force launch outside the exchange pipeline (one GPU; the one-sided kernels)
+    kProfTri1,            // exchange pipeline: first part of the own-slice triangle (runs under the position gather)
+    kProfRect,            // ... rectangles against the other slices
+    kProfTri2,            // ... rest of the own-slice triangle (runs under the reduce-scatter)
+    kProfReduceScatter,   // exchange stream: from "my send chunks are ready" to "my reduced share has arrived"
+    kProfAllGather,       // exchange stream: from "my slice is integrated" to "all slices have arrived"
+    kProfWaitGather,      // compute stream: idle in front of the rectangles, waiting for the gathered positions
+    kProfWaitReduce,      // compute stream: idle in front of the state update, waiting for the reduced share
+    kProfStep,            // compute stream: first launch of a step to the end of its state update
+    kProfKinds
+};
+
+}  // namespace
+
+struct murbhip_ctx {
+    PlanInputs in;             // n, world, slice, slots, the device facts and every option the plan choice reads (murb_choose.h)
+    float soft2 = 0.f, g = 0.f;
+    int exchange = 0;          // 0 peer copies, 1 RCCL
+    bool rank_mode = false;    // one shard here, the others live in other processes
+    std::vector<Shard> shards;
+    ShardCrew* crew = nullptr; // one host thread per shard when this process drives several
+    int cur = 0;               // record buffer holding the current positions
+    bool uploaded = false;
+    bool gather_pending = false;   // an exchange into rec[cur] is in flight on the comm streams
+    bool reduce_pending = false;   // peers may still be reading this context's reduce-scatter send buffers
+    // options
+    int profile = 0, overlap = 1;
+    int tri_first_pct = 50;   // overlap 1: share of the own-slice triangle launched BEFORE the rectangles (under the
+                              // position gather); the rest runs under the reduce-scatter
+    int xcd_order = 0;        // pair-symmetric kernel: 1 = item table interleaved into one run per XCD (measured worse)
+    int evolve_batch = 0;     // murbhip_evolve: steps per batch; 0 = from the remaining time over the step last seen
+    int integrator = 0;       // 0 the reference's update (Bodies.cpp:260-278), 1 kick-drift-kick leapfrog, 2 4th-order Hermite
+    bool herm_current = false;// Hermite: herm_a0 / herm_j0 hold the evaluation the next step starts from
+    bool herm_in_acc_out = false;   // ... and acc_out still holds its accelerations (no force evaluation has run since)
+    bool herm_proposal = false;     // ... and the control block's `raw` is the step murbhip_evolve's criterion proposes from it
+    unsigned long evolve_steps = 0; // steps of the last murbhip_evolve (what murbhip_evolve_dts reads from the ring)
+    bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
+    // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
+    bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)
+    unsigned long state_serial = 1;  // counts the changes of the body state (upload, device initialisation, every update)
+    unsigned long metrics_serial = 0;// the state the cached metric sums below belong to (murbhip_energy and murbhip_moments of one
+    bool metrics_with_phi = false;   // tracked iteration share one pass of the metrics kernel and one read-back)
+    double metrics_sums[MURB_METRIC_VALUES] = {0};
+    bool want_pe = false;            // the force launches being enqueued also sum the pair potential (murbhip_energy)
+    bool pe_current = false;         // ... and the partial-row buffers hold it for the current positions
+    float lf_last_dt = 0.f;
+    int force_exchange = 0;   // run the exchange even with one rank (self-test of the RCCL binding)
+    int init_libm_fma = -1;   // murbhip_init_bodies: which build of glibc's sincosf to reproduce (-1 = what this host's libm picks)
+    int energy_sweep = 0;     // murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 (kept for the A/B)
+    int exchange_p2p = 0;     // RCCL exchange by grouped ncclSend/ncclRecv instead of ncclReduceScatter / ncclAllGather
+    int pad_aware = 1;        // pair-symmetric kernel: 1: padding slots are not walked (murb_schedule.h, sym_orient); 0: every block as if full (A/B)
+    int cu_reserve = 0;       // CUs masked out of the compute streams (left free for the collectives' kernels)
+    int solo_shard = -1;      // >= 0: only this shard computes (timing aid: one rank's isolated timeline
+                              // when W shards share one GPU; results are then meaningless)
+    // facts
+    int clock_mhz = 0;
+    double interactions_per_launch = 0;
+    int async_error = 0;
+};
+
+#endif

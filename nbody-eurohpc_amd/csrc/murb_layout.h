@@ -42,4 +42,34 @@ MURB_HD unsigned long murb_round_up_tile(unsigned long bodies)
     return ((bodies + MURB_SLICE_ALIGN - 1) / MURB_SLICE_ALIGN) * MURB_SLICE_ALIGN;
 }
 
+// ---- balanced persistent schedule -----------------------------------------------------------------
+// The (i group, j tile) units of a launch, linearised group-major (u = g * tiles + t), are cut into
+// `nblocks` contiguous, equally long runs: workgroup b owns [begin(b), begin(b+1)).  Every workgroup
+// does the same amount of work whatever N is (the 2-D grid above leaves the last scheduling round
+// partly empty: N = 30 000 gives 938 i groups for 1024 SIMDs).  A group whose tiles are split over
+// several workgroups gets one partial-sum row per workgroup: row = b - block_of(first unit of g).
+struct MurbSchedule {
+    int groups, tiles, nblocks, row_base;
+};
+
+MURB_HD long murb_sched_begin(const MurbSchedule& s, long b)
+{
+    return ((long)s.groups * (long)s.tiles * b) / (long)s.nblocks;
+}
+
+MURB_HD int murb_sched_block_of(const MurbSchedule& s, long u)
+{
+    const long total = (long)s.groups * (long)s.tiles;
+    long b = (u * (long)s.nblocks) / total;
+    while (b + 1 < s.nblocks && murb_sched_begin(s, b + 1) <= u) ++b;
+    while (b > 0 && murb_sched_begin(s, b) > u) --b;
+    return (int)b;
+}
+
+// rows a group's partial sums occupy (>= 1)
+MURB_HD int murb_sched_rows_of_group(const MurbSchedule& s, int g)
+{
+    return murb_sched_block_of(s, (long)(g + 1) * s.tiles - 1) - murb_sched_block_of(s, (long)g * s.tiles) + 1;
+}
+
 #endif

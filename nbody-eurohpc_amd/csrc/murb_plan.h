@@ -1,6 +1,6 @@
 // The host-side planner of the pair-symmetric launches: item table + partial-row layout of one rank, computed without touching
 // a device (no HIP in here).  Unit-tested on the CPU through murbhip_schedule_layout (tests/test_abi_and_host.py) and, under
-// AddressSanitizer / UBSan, by tests/helpers/plan_selftest.cpp.  Included by murbhip.hip only.
+// AddressSanitizer / UBSan, by tests/helpers/plan_selftest.cpp.  Included by murbhip.hip through murb_choose.h.
 #ifndef MURB_PLAN_H_
 #define MURB_PLAN_H_
 
@@ -25,7 +25,7 @@ struct SymPass {
 // Cut the pieces (j-major order) into passes at column boundaries so that no pass needs more than budget_floats of
 // partial rows per component; 0 = no limit (one pass).  Conservative estimate per column: every piece owns a j row, every
 // distinct (i block, column) pair an i row.
-std::vector<std::pair<size_t, size_t>> cut_passes(const std::vector<SymPiece>& pieces, size_t budget_floats)
+inline std::vector<std::pair<size_t, size_t>> cut_passes(const std::vector<SymPiece>& pieces, size_t budget_floats)
 {
     std::vector<std::pair<size_t, size_t>> out;
     size_t first = 0, used = 0, k = 0;
@@ -98,8 +98,26 @@ struct SymHostLayout {
     std::vector<SymPass> passes;              // of the main set
 };
 
-void plan_sym_layout(int W, int r, const SymFill& fill, int split, int waves, int taper, bool diag_tri, bool exchange_mode, int overlap,
-                     int tri_first_pct, bool xcd_order, size_t budget_floats, SymHostLayout& L, int tri_div = 1)
+// What the tables of one rank are built for, besides (W, rank, fill): a shard keeps the key of its tables and rebuilds them
+// when the key of the step differs (murb_choose.h, sym_layout_key, fills it in from the plan and the options).
+struct SymLayoutKey {
+    int split = 1, waves = 4, taper = 0;   // items of 1024/split bodies, waves per workgroup, % of each launch cut finer
+    bool diag_tri = false;                 // diagonal blocks as triangular pieces
+    bool exchange_mode = false;            // exchange pipeline: own-slice triangle (two launches) + rectangles
+    int overlap = 0, tri_first_pct = 0;    // ... and its launch boundaries inside the triangle (0 outside that mode)
+    bool xcd_order = false;                // item table interleaved into one run per XCD
+    size_t budget_floats = 0;              // one GPU: partial-row floats per component a pass may take (0 = no limit)
+    int tri_div = 1;                       // exchange pipeline: extra division of the triangle launches' items
+    bool pad_aware = true;                 // enters through `fill` (sym_fill's `aware`)
+    bool operator==(const SymLayoutKey& o) const
+    {
+        return split == o.split && waves == o.waves && taper == o.taper && diag_tri == o.diag_tri && exchange_mode == o.exchange_mode &&
+               overlap == o.overlap && tri_first_pct == o.tri_first_pct && xcd_order == o.xcd_order && budget_floats == o.budget_floats &&
+               tri_div == o.tri_div && pad_aware == o.pad_aware;
+    }
+};
+
+inline void plan_sym_layout(int W, int r, const SymFill& fill, const SymLayoutKey& key, SymHostLayout& L)
 {
     const int tb = fill.tb;
     std::vector<int> flat;
@@ -108,44 +126,44 @@ void plan_sym_layout(int W, int r, const SymFill& fill, int split, int waves, in
     std::vector<SymPiece> pieces;
     std::vector<size_t> piece_ends;
     const auto build_pieces = [&](bool interleaved) {
-        sym_schedule_items(W, r, tb, split, fill, flat, &own, interleaved);
+        sym_schedule_items(W, r, tb, key.split, fill, flat, &own, interleaved);
         // the launches of a step: one GPU = everything; exchange pipeline = triangle part 1, part 2, rectangles
         const size_t n_all = flat.size() / 2;
-        t1 = (exchange_mode && overlap == 1) ? (size_t)((long)own * tri_first_pct / 100) : 0;
+        t1 = (key.exchange_mode && key.overlap == 1) ? (size_t)((long)own * key.tri_first_pct / 100) : 0;
         std::vector<size_t> launch_ends;
         std::vector<int> launch_div;   // the own-slice triangle's launches in finer items ("tri_div")
-        if (exchange_mode) {
-            if (t1 > 0) { launch_ends.push_back(t1); launch_div.push_back(tri_div); }
-            if ((size_t)own > t1) { launch_ends.push_back((size_t)own); launch_div.push_back(tri_div); }
+        if (key.exchange_mode) {
+            if (t1 > 0) { launch_ends.push_back(t1); launch_div.push_back(key.tri_div); }
+            if ((size_t)own > t1) { launch_ends.push_back((size_t)own); launch_div.push_back(key.tri_div); }
             if (n_all > (size_t)own) { launch_ends.push_back(n_all); launch_div.push_back(1); }
         } else {
             launch_ends.push_back(n_all);
         }
-        sym_pieces(flat, split, taper, 16 * waves, diag_tri, fill, launch_ends, pieces, piece_ends, launch_div);
+        sym_pieces(flat, key.split, key.taper, 16 * key.waves, key.diag_tri, fill, launch_ends, pieces, piece_ends, launch_div);
     };
-    build_pieces(xcd_order);
+    build_pieces(key.xcd_order);
     // Several passes share ONE row buffer and are cut at COLUMN boundaries (cut_passes takes a column to be a contiguous
     // run of pieces with the same J): under the XCD-interleaved order a column is scattered over the table, a cut would
     // fall inside it and an i row would keep an earlier pass's sums in the cells this pass does not write.  A problem
     // that needs several passes is therefore always laid out in the plain j-major order.
-    if (!exchange_mode && xcd_order && cut_passes(pieces, budget_floats).size() > 1) build_pieces(false);
+    if (!key.exchange_mode && key.xcd_order && cut_passes(pieces, key.budget_floats).size() > 1) build_pieces(false);
     // pieces of the own-slice triangle = those of the launches before the rectangles' (a rectangle item may have an own
     // block on its j side: sym_orient puts the emptier block of a pair on the i side)
     size_t own_pieces = pieces.size();
-    if (exchange_mode && flat.size() / 2 > (size_t)own) own_pieces = piece_ends.size() >= 2 ? piece_ends[piece_ends.size() - 2] : 0;
+    if (key.exchange_mode && flat.size() / 2 > (size_t)own) own_pieces = piece_ends.size() >= 2 ? piece_ends[piece_ends.size() - 2] : 0;
     L.items.assign(pieces.size(), MurbSymItem{});
     L.table_main.clear(); L.table_tri.clear();
     L.floats_main = L.floats_tri = 0;
-    if (exchange_mode) {
-        L.floats_tri = layout_sym_set(pieces, 0, own_pieces, waves, L.items, L.table_tri, [&](int b) { return std::make_pair(0, b - r * tb); });
-        L.floats_main = layout_sym_set(pieces, own_pieces, pieces.size(), waves, L.items, L.table_main,
+    if (key.exchange_mode) {
+        L.floats_tri = layout_sym_set(pieces, 0, own_pieces, key.waves, L.items, L.table_tri, [&](int b) { return std::make_pair(0, b - r * tb); });
+        L.floats_main = layout_sym_set(pieces, own_pieces, pieces.size(), key.waves, L.items, L.table_main,
                                        [&](int b) { return std::make_pair(b / tb, b % tb); });
         L.passes.assign(1, SymPass{(int)own_pieces, (int)(pieces.size() - own_pieces), 0, (int)L.table_main.size(), L.floats_main});
     } else {
         L.passes.clear();
         std::vector<MurbSymBlockRows> table;
-        for (const auto& range : cut_passes(pieces, budget_floats)) {
-            const size_t floats = layout_sym_set(pieces, range.first, range.second, waves, L.items, table, [&](int b) { return std::make_pair(0, b); });
+        for (const auto& range : cut_passes(pieces, key.budget_floats)) {
+            const size_t floats = layout_sym_set(pieces, range.first, range.second, key.waves, L.items, table, [&](int b) { return std::make_pair(0, b); });
             L.passes.push_back(SymPass{(int)range.first, (int)(range.second - range.first), (int)L.table_main.size(), (int)table.size(), floats});
             L.table_main.insert(L.table_main.end(), table.begin(), table.end());
             L.floats_main = std::max(L.floats_main, floats);

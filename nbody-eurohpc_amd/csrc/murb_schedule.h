@@ -1,7 +1,7 @@
 // Host-only scheduling rules (no HIP call): the reference's body partition, and which (i sub-block, j block)
 // items a rank evaluates under the half-ring pair-symmetric schedule.  "Every unordered body pair is
 // evaluated by exactly one rank" lives here and is unit-tested on the CPU through murbhip_schedule_items().
-// Included by murbhip.hip only.
+// Included by murbhip.hip (through murb_plan.h) and by the CPU self-test of the planner.
 #ifndef MURB_SCHEDULE_H_
 #define MURB_SCHEDULE_H_
 
@@ -13,7 +13,7 @@
 namespace {
 
 // Reference rule counts[r] = n/R + (r < n%R), displs = prefix sums (SimulationNBodyMultiNode.cpp:76-91).
-void partition(unsigned long n, int world, int rank, unsigned long* first, unsigned long* count)
+inline void partition(unsigned long n, int world, int rank, unsigned long* first, unsigned long* count)
 {
     const unsigned long base = n / (unsigned long)world, rem = n % (unsigned long)world;
     const unsigned long r = (unsigned long)rank;
@@ -21,7 +21,7 @@ void partition(unsigned long n, int world, int rank, unsigned long* first, unsig
     *first = r * base + std::min(r, rem);
 }
 
-unsigned long slice_slots(unsigned long n, int world)
+inline unsigned long slice_slots(unsigned long n, int world)
 {
     unsigned long first, count;
     partition(n, world, 0, &first, &count);   // rank 0 always holds the largest slice
@@ -44,7 +44,7 @@ unsigned long slice_slots(unsigned long n, int world)
 // walks few j blocks but ALL i blocks): measured 35 % MORE L2 misses (FETCH_SIZE 216 vs 160 MiB per launch
 // at N=200k) and no time difference (tools/xcd_ab.py) — kept only for that comparison.
 constexpr int kXcds = 8;
-void xcd_interleave(std::vector<int>& flat, size_t first_item, size_t end_item)
+inline void xcd_interleave(std::vector<int>& flat, size_t first_item, size_t end_item)
 {
     const size_t n = end_item - first_item;
     if (n < 2 * kXcds) return;
@@ -106,7 +106,7 @@ inline void sym_push_block_pair(const SymFill& fill, int split, int i_block, int
     for (int q = 0; q < split && q * len < real; ++q) { flat.push_back(i_block * split + q); flat.push_back(j_block); }
 }
 
-void sym_schedule_items(int world, int rank, int tb, int split, const SymFill& fill, std::vector<int>& flat, int* own, bool xcd_order = false)
+inline void sym_schedule_items(int world, int rank, int tb, int split, const SymFill& fill, std::vector<int>& flat, int* own, bool xcd_order = false)
 {
     const int W = world, r = rank;
     flat.clear();

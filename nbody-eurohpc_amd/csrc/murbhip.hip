@@ -1,5 +1,7 @@
-// libmurbhip.so — the C ABI of include/murbhip.h: context, residency, launches, exchange.
-// The only translation unit of the product that needs hipcc.
+// libmurbhip.so — the C ABI of include/murbhip.h: residency, launches, exchange.
+// The only translation unit of the product that needs hipcc.  Its host code that needs no device lives in headers a plain
+// C++ compiler can check: the plan choice (murb_choose.h), the tables of the pair-symmetric launches (murb_plan.h,
+// murb_schedule.h), the shards' threads (murb_crew.h); the context and the counted allocations are in murb_ctx.h.
 //
 // Design notes (full text in DESIGN.md):
 //   * body state stays resident in HBM for the whole simulation (reference twin:
@@ -9,7 +11,7 @@
 //     rec[cur^1], so no kernel ever reads a buffer another kernel (or a peer GPU) is writing;
 //   * force kernels: the pair-symmetric kernel (murb_kernels_sym.h; every body pair once, both
 //     directions) wherever a GPU gets enough block pairs, the one-sided kernel (murb_kernels.h)
-//     otherwise; make_plan() decides, "variant"/"jsplit" override;
+//     otherwise; make_plan() (murb_choose.h) decides, "variant"/"jsplit" override;
 //   * multi-GPU: bodies are block-partitioned (murbhip_partition) into equal block-aligned slot
 //     ranges of one replicated record buffer.  Half-ring schedule (sym_schedule_items): every pair is
 //     evaluated by exactly one rank, ONE reduce-scatter returns each rank the accelerations of its own
@@ -24,212 +26,21 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <map>
-#include <mutex>
 #include <new>
 #include <string>
-#include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/murbhip.h"
-#include "murb_crew.h"
 #include "murb_init.h"
-#include "murb_kernels_hermite.h"
-#include "murb_kernels_sym.h"
-#include "murb_plan.h"
-#include "murb_rccl.h"
-#include "murb_schedule.h"
+#include "murb_ctx.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------ error codes
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(int)e; }
-inline int nccl_rc(int r) { return r == 0 ? 0 : -(3000 + r); }   // disjoint from -(hipError_t), which reaches past 1000
-
-// Teardown and error paths: a release that fails cannot be acted on (the context is going away either way).
-template <typename... P> inline void release(P*... p) { ((void)hipFree((void*)p), ...); }
-inline void release_event(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-inline void release_stream(hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; }
-inline void drain(hipStream_t s) { if (s) (void)hipStreamSynchronize(s); }
-
-#define HIP_TRY(expr)                        \
-    do {                                     \
-        const int rc_ = hip_rc((expr));      \
-        if (rc_ != 0) return rc_;            \
-    } while (0)
-#define RC_TRY(expr)                \
-    do {                            \
-        const int rc_ = (expr);     \
-        if (rc_ != 0) return rc_;   \
-    } while (0)
-
-// ------------------------------------------------------------------------------------ context
-// Partial rows of one group of launches (murb_kernels_sym.h): the buffer, and per block the row table its row sum reads
-// (SymPass, the layout and the planner: murb_plan.h).
-struct SymSet {
-    float* part = nullptr;
-    size_t comp_stride = 0;           // floats per component (single pass)
-    MurbSymBlockRows* rows = nullptr; // device copy of the table
-    int nblocks = 0;                  // entries (all passes)
-    std::vector<SymPass> passes;      // more than one entry: multi-pass evaluation
-};
-
-struct Shard {
-    int device = 0;
-    int rank = 0;
-    unsigned long first = 0, count = 0;   // global body range owned
-    hipStream_t compute = nullptr, comm = nullptr;
-    hipStream_t compute_low = nullptr;   // lowest priority: the own-slice triangle in "overlap" mode 2
-    hipEvent_t ev_integrated = nullptr, ev_gathered = nullptr, ev_tri = nullptr;
-    float4* rec[2] = {nullptr, nullptr};
-    float4* vel = nullptr;
-    float4* accp = nullptr;      // one-sided kernels: partial-sum rows, allocated on first use (ensure_accp)
-    float* acc_out = nullptr;
-    float* phi_out = nullptr;    // murbhip_energy's potential sweep (same shape as acc_out), allocated on first use
-    float* mass = nullptr;       // masses of the local slice as uploaded (metrics)
-    float* radius = nullptr;     // radii of the local slice: only after murbhip_init_bodies (the host never sent them)
-    double* metrics = nullptr;   // block sums of murb_metrics_kernel, then murbhip_energy's pair potentials (metrics_doubles)
-    double* metrics_host = nullptr;   // its pinned host copy: the read-out is one asynchronous copy behind the kernels
-    // pair-symmetric kernel: item table and partial-row layouts (built by build_sym_schedule for one plan)
-    MurbSymItem* sym_items = nullptr;
-    int sym_items_own = 0, sym_items_total = 0;   // [0, own) = own-slice triangle, the rest need the gathered positions
-    int sym_split = 0, sym_waves = 0, sym_taper = -1, sym_diag_tri = -1;   // what the table was built for
-    int sym_red = 0;                              // i-side reduction of the plan (kernel template parameter)
-    long sym_pass_mb = -1;                        // "sym_pass_mb" the passes were cut for
-    int sym_pad_aware = -1;                       // ... and "pad_aware"
-    int sym_tri_div = -1;                         // ... and the triangle launches' extra division
-    int sym_xcd_order = -1;                       // ... and the item order ("xcd_order")
-    int sym_tri_first = -1, sym_overlap = -1;     // ... and the launch boundaries inside the own-slice triangle ("tri_first_pct", "overlap")
-    int sym_t1 = 0;                               // items of the triangle's first launch (exchange pipeline, overlap 1)
-    bool sym_exchange_mode = false;               // ... and whether it was built for the exchange pipeline
-    SymSet sym_main;             // one GPU: every item; exchange pipeline: the rectangles (-> reduce-scatter send chunks)
-    SymSet sym_tri;              // exchange pipeline: the own-slice triangle (never enters the reduce-scatter)
-    float* sym_send = nullptr;   // [world][3][slice]
-    float* sym_recv = nullptr;   // [3][slice]
-    float* sym_p2p = nullptr;    // "exchange_p2p": chunks received from the floor(W/2) ranks behind this one [floor(W/2)][3][slice]
-    float* sym_tri_acc = nullptr;// row sums of sym_tri [3][slice]
-    double* sym_acc64 = nullptr; // multi-pass evaluation: fp64 row sums accumulated over the passes [3][slots]
-    size_t sym_bytes = 0;        // device bytes of all of the above
-    hipEvent_t ev_rowsum = nullptr, ev_reduced = nullptr;
-    rccl_comm_t comm_rccl = nullptr;
-    std::vector<hipEvent_t> prof;   // pool of timing events ("profile"): two per recorded span
-    size_t prof_used = 0;
-    std::vector<int> prof_kind;     // what span k (events 2k, 2k+1) brackets: ProfKind
-    // Hermite integrator ("integrator" 2; one shard), allocated on first use (ensure_hermite)
-    float4* herm_rec = nullptr;     // predicted positions + GM, all slots
-    float4* herm_vel = nullptr;     // predicted velocities
-    float* herm_a0 = nullptr;       // ax | ay | az of the remembered evaluation
-    float* herm_j0 = nullptr;       // jx | jy | jz of it
-    float4* herm_part = nullptr;    // partial rows of the sweep: herm_rows rows of accelerations, then as many of jerks
-    int herm_rows = 0;
-    MurbEvolveCtl* herm_ctl = nullptr;        // murbhip_evolve's control block (device), allocated on first use
-    MurbEvolveCtl* herm_ctl_host = nullptr;   // pinned copy of its head (everything in front of the ring)
-    unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
-    size_t bytes = 0;
-};
-
-constexpr int kMaxParts = 64;          // rows of the partial-sum buffer
-constexpr int kPeSumBlocks = 256;      // workgroups of murb_sym_pe_sum_kernel
-constexpr size_t kProfPairs = 4096;
-
-// What a pair of timing events brackets.  "profile" 1: the force launches only (two event records per launch);
-// 2: also the collectives on the exchange stream, the compute stream's waits for them (= the EXPOSED part of the
-// exchange) and the compute stream's whole step.
-enum ProfKind {
-    kProfForce = 0,       // a force launch outside the exchange pipeline (one GPU; the one-sided kernels)
-    kProfTri1,            // exchange pipeline: first part of the own-slice triangle (runs under the position gather)
-    kProfRect,            // ... rectangles against the other slices
-    kProfTri2,            // ... rest of the own-slice triangle (runs under the reduce-scatter)
-    kProfReduceScatter,   // exchange stream: from "my send chunks are ready" to "my reduced share has arrived"
-    kProfAllGather,       // exchange stream: from "my slice is integrated" to "all slices have arrived"
-    kProfWaitGather,      // compute stream: idle in front of the rectangles, waiting for the gathered positions
-    kProfWaitReduce,      // compute stream: idle in front of the state update, waiting for the reduced share
-    kProfStep,            // compute stream: first launch of a step to the end of its state update
-    kProfKinds
-};
-
-}  // namespace
-
-struct murbhip_ctx {
-    unsigned long n = 0;
-    int world = 1;
-    unsigned long slice = 0;   // slots per rank
-    unsigned long slots = 0;   // world * slice
-    float soft2 = 0.f, g = 0.f;
-    int exchange = 0;          // 0 peer copies, 1 RCCL
-    bool rank_mode = false;    // one shard here, the others live in other processes
-    std::vector<Shard> shards;
-    ShardCrew* crew = nullptr; // one host thread per shard when this process drives several
-    int cur = 0;               // record buffer holding the current positions
-    bool uploaded = false;
-    bool gather_pending = false;   // an exchange into rec[cur] is in flight on the comm streams
-    bool reduce_pending = false;   // peers may still be reading this context's reduce-scatter send buffers
-    // options
-    int variant = 0, jsplit = 0, profile = 0, overlap = 1;
-    int sym_waves = 0;        // pair-symmetric kernel: waves per workgroup, 0 = auto, 4 or 8
-    int tri_first_pct = 50;   // overlap 1: share of the own-slice triangle launched BEFORE the rectangles (under the
-                              // position gather); the rest runs under the reduce-scatter
-    int xcd_order = 0;        // pair-symmetric kernel: 1 = item table interleaved into one run per XCD (measured worse)
-    int evolve_batch = 0;     // murbhip_evolve: steps per batch; 0 = from the remaining time over the step last seen
-    int integrator = 0;       // 0 the reference's update (Bodies.cpp:260-278), 1 kick-drift-kick leapfrog, 2 4th-order Hermite
-    bool herm_current = false;// Hermite: herm_a0 / herm_j0 hold the evaluation the next step starts from
-    bool herm_in_acc_out = false;   // ... and acc_out still holds its accelerations (no force evaluation has run since)
-    bool herm_proposal = false;     // ... and the control block's `raw` is the step murbhip_evolve's criterion proposes from it
-    unsigned long evolve_steps = 0; // steps of the last murbhip_evolve (what murbhip_evolve_dts reads from the ring)
-    bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
-    // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
-    bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)
-    unsigned long state_serial = 1;  // counts the changes of the body state (upload, device initialisation, every update)
-    unsigned long metrics_serial = 0;// the state the cached metric sums below belong to (murbhip_energy and murbhip_moments of one
-    bool metrics_with_phi = false;   // tracked iteration share one pass of the metrics kernel and one read-back)
-    double metrics_sums[MURB_METRIC_VALUES] = {0};
-    bool want_pe = false;            // the force launches being enqueued also sum the pair potential (murbhip_energy)
-    bool pe_current = false;         // ... and the partial-row buffers hold it for the current positions
-    float lf_last_dt = 0.f;
-    int force_exchange = 0;   // run the exchange even with one rank (self-test of the RCCL binding)
-    int taper = -1;           // pair-symmetric kernel: % of each launch cut into finer items (-1 = the plan's default)
-    int diag_tri = -1;        // ... diagonal blocks as triangular pieces (-1 = the plan's default)
-    long sym_pass_mb = 0;     // ... one GPU: budget (MiB) for the partial rows of one pass; 0 = a quarter of the device memory
-    int sym_red = -1;         // ... i-side reduction in registers (0) or through LDS (1) (-1 = the plan's default)
-    int init_libm_fma = -1;   // murbhip_init_bodies: which build of glibc's sincosf to reproduce (-1 = what this host's libm picks)
-    int energy_sweep = 0;     // murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 (kept for the A/B)
-    int fuse_integrate = 1;   // "fuse_integrate": one-sided plan, the state update in the tail of the step's last force launch
-    int exchange_p2p = 0;     // RCCL exchange by grouped ncclSend/ncclRecv instead of ncclReduceScatter / ncclAllGather
-    int tri_div = 0;          // ... exchange pipeline: the own-slice triangle's items cut into this many parts more (0 = the plan's choice)
-    int pad_aware = 1;        // ... 1: padding slots are not walked (murb_schedule.h, sym_orient); 0: every block as if full (A/B)
-    int cu_reserve = 0;       // CUs masked out of the compute streams (left free for the collectives' kernels)
-    int solo_shard = -1;      // >= 0: only this shard computes (timing aid: one rank's isolated timeline
-                              // when W shards share one GPU; results are then meaningless)
-    // facts
-    int cu_count = 0, clock_mhz = 0;
-    size_t device_mem = 0;     // bytes of HBM on the first device
-    int last_parts = 0;
-    int plan_waves = 4;        // waves per workgroup of the current plan's pair-symmetric launches
-    double interactions_per_launch = 0;
-    int async_error = 0;
-};
-
-namespace {
-
-struct Plan {
-    int variant;   // resolved
-    int parts_local, parts_remote;   // 2-D grid variants: j chunks of the own-slice launch and of the rest
-    bool persistent;                 // balanced persistent schedule (murb_force_persistent)
-    bool symmetric;                  // pair-symmetric kernel (murb_force_sym_kernel)
-    int split;                       // its i-side sub-blocks per block (1, 2, 4, 8, 16)
-    int waves;                       // ... and its waves per workgroup (4 or 8)
-    int taper;                       // ... and the share (%) of each launch whose items are cut finer ("taper")
-    bool diag_tri;                   // ... diagonal blocks in triangular pieces ("diag_tri")
-    int red;                         // ... i-side reduction: 0 registers, 1 LDS teams ("sym_red")
-    MurbSchedule sched[2];           // [0] own slice (or everything), [1] the rest
-};
 
 constexpr int kPotentialKernel = 100;   // not a selectable variant: murbhip_energy's potential sweep
 
@@ -278,203 +89,23 @@ int launch_force_integrate(const MurbForceArgs& a, const MurbIntegrateArgs& ia, 
     if (i_slots <= 8192) return launch_force_integrate_t<4>(a, ia, i_slots, s);   // 4 at 7 000 (21.9 vs 22.4 us), all equal from 8 193
     return launch_force_integrate_t<8>(a, ia, i_slots, s);
 }
-constexpr int kNumVariants = 8;
-constexpr int kOneSidedVariant = 1;     // the persistent schedule (7) measured no faster: DESIGN.md §4.1
-constexpr int kOneSidedFewBodies = 2;   // 4 i bodies per wave instead of 8: twice the workgroups for a rank's small slice (tools/solo_rank.py,
-                                        // round 3, one rank alone: N = 30 000 W = 2/4/8 148 -> 138, 92 -> 86, 69 -> 63 us per step; N = 16 000
-                                        // W = 4: 54 -> 43; N = 45 000 W = 8: 108 -> 99; equal from ~20 000 bodies per rank)
-constexpr int kPersistentVariant = 7;   // murb_force_persistent<8, 4, 4>
-constexpr int kSymmetricVariant = 8;    // murb_force_sym_kernel<4, 4 or 8>
-constexpr unsigned long kSymmetricMinBodies = 2049;    // below this (one or two blocks) the one-sided kernel wins; round 2: 10 240 —
-                                                       // with items of 64-128 bodies the pair-symmetric kernel is 1.2-1.4x faster
-                                                       // from 3 blocks up (tools/small_plan_table.py: N = 3584 14.4 vs 20.5 us per step)
-constexpr int kRowsPerLaunch = kMaxParts / 2;
-
 int launch_persistent(const MurbForceArgs& a, const MurbSchedule& sc, hipStream_t s)
 {
     hipLaunchKernelGGL((murb_force_persistent<8, 4, 4>), dim3((unsigned)sc.nblocks), dim3(256), 0, s, a, sc);
     return hip_rc(hipGetLastError());
 }
 
-// Workgroups of the persistent kernel that fit on the chip at once.
-int resident_blocks(const murbhip_ctx* c)
+// The plan of the context as it stands (murb_choose.h).  A persistent plan needs the workgroups of its kernel that fit on a
+// CU: asked of the runtime the first time such a plan is wanted, not before (the query loads the kernel).
+Plan current_plan(murbhip_ctx* c)
 {
-    static int per_cu = 0;
-    if (per_cu == 0) {
+    if (c->in.variant == kPersistentVariant && c->in.resident_per_cu == 0) {
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, murb_force_persistent<8, 4, 4>, 256, 0) != hipSuccess || n < 1)
             n = 4;
-        per_cu = n;
+        c->in.resident_per_cu = n;
     }
-    return per_cu * std::max(c->cu_count, 1);
-}
-
-// Cut groups x tiles units into equal runs: `rounds` runs per resident slot (so that a slot lost to
-// another process or to the profiler costs 1/rounds, not 2x), at least ~8 tiles per run (the
-// end-of-run reduction is ~1 % of that), and few enough runs that a group spans < kRowsPerLaunch rows.
-MurbSchedule make_schedule(const murbhip_ctx* c, long groups, long tiles, int row_base)
-{
-    MurbSchedule sc{(int)groups, (int)tiles, 1, row_base};
-    const long units = groups * tiles;
-    if (units <= 0) { sc.nblocks = 0; return sc; }
-    const long slots = resident_blocks(c);
-    long rounds = c->jsplit > 0 ? c->jsplit : std::min<long>(8, std::max<long>(1, units / (slots * 8)));
-    long nb = std::min(units, slots * rounds);
-    nb = std::min(nb, std::max<long>(1, (kRowsPerLaunch - 2) * groups));
-    sc.nblocks = (int)std::max<long>(nb, 1);
-    return sc;
-}
-
-int variant_group(int variant)   // bodies per workgroup = waves * R
-{
-    switch (variant) {
-        case kPersistentVariant: return 32;
-        case kSymmetricVariant: return 32;
-        case 2: case 6: return 16;
-        case 5: return 64;
-        default: return 32;
-    }
-}
-
-// How many j chunks: enough workgroups for ~24 scheduling rounds of the chip, but chunks of at
-// least 8 tiles (4096 bodies) so the end-of-sweep reduction stays well under 1 % of the sweep.
-int auto_parts(const murbhip_ctx* c, int variant, unsigned long i_slots, unsigned long tiles)
-{
-    if (tiles == 0) return 0;
-    const unsigned long groups = (i_slots + variant_group(variant) - 1) / variant_group(variant);
-    const unsigned long want_blocks = (unsigned long)std::max(c->cu_count, 1) * 6ul * 24ul;
-    unsigned long parts = (want_blocks + groups - 1) / groups;
-    parts = std::min(parts, std::max(tiles / 8ul, 1ul));
-    parts = std::max(parts, 1ul);
-    return (int)std::min<unsigned long>(parts, kMaxParts / 2);
-}
-
-// Block pairs a rank evaluates under the (half-ring) pair-symmetric schedule with whole-block items.
-long sym_items_per_rank(const murbhip_ctx* c)
-{
-    const long tb = (long)(c->slice / MURB_SYM_BLOCK), w = c->world;
-    return tb * (tb + 1) / 2 + ((w - 1) / 2) * tb * tb + (w > 1 && w % 2 == 0 ? tb * ((tb + 1) / 2) : 0);
-}
-
-// One GPU: what the partial rows of one pass may take.  Problems whose rows exceed it are evaluated in several passes
-// over ranges of j columns (the rows of N = 1M take 12 GB, of 3.5M 144 GB: half of the HBM).
-size_t sym_pass_budget(const murbhip_ctx* c)
-{
-    if (c->sym_pass_mb > 0) return (size_t)c->sym_pass_mb << 20;
-    return c->device_mem ? c->device_mem / 4 : 0;
-}
-
-// Bytes of the partial rows of the pair-symmetric kernel on one rank for uniform items of 1024/split bodies
-// (12 B per row slot: three components).  One GPU: block b has split*b j rows and T-b i rows.  A rank of W: its
-// triangle (tb blocks) plus the rectangles against floor(W/2) slices: tb i rows per own block and split*tb j rows per
-// far block at most.
-size_t sym_row_bytes(const murbhip_ctx* c, int split)
-{
-    const size_t tb = c->slice / MURB_SYM_BLOCK, w = (size_t)c->world, far = w / 2;
-    size_t rows = tb * tb + (size_t)(split - 1) * tb * (tb - 1) / 2;
-    if (w > 1) rows += tb * far * tb + far * tb * (size_t)split * tb;
-    return rows * MURB_SYM_BLOCK * 3 * sizeof(float);
-}
-
-// One GPU, few bodies: the one-sided kernel with the state update in its tail (murb_force_integrate_kernel: ONE launch per
-// step, 2 i bodies per wave) against the pair-symmetric plan's two launches (force, row sum + update), by block count —
-// tools/rate_curve.py, us per step, round 3: N = 2 049: 8.9 vs 14.0; 3 000: 9.4 vs 13.9; 3 584: 11.2 vs 14.4; 4 097 (5 blocks):
-// 14.2 vs 14.9, 5 000: 15.0 vs 15.1 (a tie: the pair-symmetric plan stays); 6 000 (6 blocks, where the pair-symmetric items
-// fall badly on the workgroup slots): 16.2 vs 19.8; 7 000: 21.9 vs 20.2; 8 193: 37 vs 27.
-inline bool fused_one_sided_wins(const murbhip_ctx* c)
-{
-    const unsigned long T = c->slots / MURB_SYM_BLOCK;
-    return c->fuse_integrate && c->jsplit == 0 && (T <= 4 || T == 6);
-}
-
-Plan make_plan(const murbhip_ctx* c)
-{
-    Plan p{};
-    // variant 0 = auto: pair-symmetric when a GPU gets enough block pairs and its partial rows fit comfortably
-    // (they grow as N^2/1024 on one GPU: 0.5 GB at 200k, 12 GB at 1M; a rank of W holds ~1/W of that), else one-sided
-    // (one GPU: rows beyond the budget are handled in passes, so only a rank of several has to fit them whole)
-    const auto fits = [&](int split) { return c->world == 1 || c->device_mem == 0 || sym_row_bytes(c, split) < c->device_mem / 2; };
-    if (c->variant >= 1 && c->variant <= kNumVariants) p.variant = c->variant;
-    else if (c->world == 1) p.variant = (c->n >= kSymmetricMinBodies && !fused_one_sided_wins(c) && fits(1)) ? kSymmetricVariant : kOneSidedVariant;
-    else p.variant = (sym_items_per_rank(c) >= 400 && fits(1)) ? kSymmetricVariant : (c->slice <= 16384 ? kOneSidedFewBodies : kOneSidedVariant);
-    p.symmetric = p.variant == kSymmetricVariant;
-    if (p.symmetric) {
-        // finer items (i side cut in 2 or 4) until a GPU has ~8 scheduling rounds of them; ~16 in the
-        // multi-rank pipeline, whose three force launches per step each end in a tail (measured with
-        // tools/solo_profile.py: N=200k, W=2/4/8 -> split 2/4/4 is best)
-        const long items = sym_items_per_rank(c);
-        const long want = (c->world > 1 ? 16L : 8L) * 4 * std::max(c->cu_count, 1);
-        // ... and with few block pairs per rank finer still, so that each of the three launches of a step gets its round of
-        // workgroups (tools/solo_rank.py, round 3: N=100k W=8, 689 block pairs: split 8 beats 4 by 3 %; N=60k W=4, 465: by 4.6 %;
-        // N=30k W=2, 240: split 16 beats 4 by 5.5 %; from ~1000 block pairs up 4 is best: N=100k W=4, N=200k W=8)
-        p.split = (c->jsplit == 1 || c->jsplit == 2 || c->jsplit == 4 || c->jsplit == 8 || c->jsplit == 16)
-                      ? c->jsplit
-                      : (items >= want ? 1 : (2 * items >= want ? 2 : (c->world == 1 || items >= 1000 ? 4 : (items >= 400 ? 8 : 16))));
-        // Rounds 1-2, one GPU below 45 000 bodies (BASELINE's N = 30 000: 465 block pairs for 1024 workgroup slots): 8-wave
-        // workgroups (2 per SIMD, 2 workgroups per CU: a CU's last workgroup still has two waves per SIMD to interleave),
-        // quarter-block items with the last 30 % of the launch cut finer, diagonal blocks as triangular pieces.
-        // tools/ab.py, interleaved, N = 30 000, wall per step: 8 waves / split 8 (round 1) 174.5 us, 8 / 4 / taper 30 /
-        // triangular diagonal 170.5, 8 / 2 / taper 60 171.4; 4 waves never better.
-        // Round 3 (tools/small_plan_table.py: five plans interleaved for every block count T = 10 ... 44; padding-aware
-        // items, measurement without the profiling events): from T = 28 blocks up (N > 27 648) the plan of the larger
-        // problems — 4 waves, quarter blocks, 5 % taper, plain diagonal — is the fastest or within 1 % of it (N = 30 000:
-        // +3.6 % over the 8-wave plan, interleaved).  Below, the winner follows how the item count falls on the 1024
-        // (4 waves) or 512 (8 waves) workgroup slots of the chip, block count by block count, with up to 27 % between the
-        // plans at T = 10-16: a table (measured on the 256 CUs of an MI355X; any other CU count keeps the 8-wave plan).
-        struct SmallPlan { int waves, split, taper; bool diag_tri; };
-        static const SmallPlan kSmallPlans[5] = {{8, 4, 30, true}, {4, 4, 5, false}, {4, 8, 5, false}, {8, 8, 30, true}, {4, 16, 5, false}};
-        static const signed char kSmallPlanOfBlocks[25] = {4, 4, 4, 3, 3, 3, 4,                                      // T = 3 ... 9
-                                                           3, 3, 0, 2, 2, 1, 3, 0, 2, 1, 2, 0, 1, 2, 0, 1, 0, 2};   // T = 10 ... 27
-        const int T = (int)(c->slots / MURB_SYM_BLOCK);
-        const bool small = c->world == 1 && T <= 27;
-        const SmallPlan sp = kSmallPlans[(small && c->cu_count == 256 && T >= 3) ? kSmallPlanOfBlocks[T - 3] : (T < 10 ? 3 : 0)];
-        p.waves = (c->sym_waves == 4 || c->sym_waves == 8) ? c->sym_waves : (small ? sp.waves : 4);
-        if (c->jsplit == 0 && c->sym_waves == 0 && small) p.split = sp.split;
-        while (p.split > 1 && MURB_SYM_BLOCK / p.split < 16 * p.waves) p.split /= 2;   // an item is at least one group per wave
-        while (p.split > 1 && !fits(p.split)) p.split /= 2;   // the rows of the split actually used must fit, too
-        // the tail of a launch in finer items (murb_schedule.h): +1.2-1.4 % on the force launch at N = 200 000 with 5 %,
-        // nothing at 1M (the tail is 0.3 % of the launch there), and nothing on the wall clock of a rank of 8, whose three
-        // short launches gain what their row sums lose to the extra rows
-        p.taper = c->taper >= 0 ? c->taper : (c->world > 1 ? 0 : (small ? sp.taper : (c->n <= 600000 ? 5 : 0)));
-        p.diag_tri = c->diag_tri >= 0 ? c->diag_tri != 0 : (small && sp.diag_tri);
-        // i-side sums through LDS: 599 instead of 616 VALU instructions per group; +0.8-1.3 % at N = 200 000, +1.7 % for
-        // a rank of 8 (tools/ab.py)
-        p.red = c->sym_red >= 0 ? c->sym_red : 1;
-        p.persistent = false;
-        p.parts_local = p.parts_remote = 0;
-        return p;
-    }
-    const unsigned long tiles_local = c->slice / MURB_TILE_BODIES;
-    const unsigned long tiles_remote = (c->slots - c->slice) / MURB_TILE_BODIES;
-    p.persistent = p.variant == kPersistentVariant;
-    if (p.persistent) {
-        // every shard sweeps the same number of i groups: the largest slice count decides
-        unsigned long first, count;
-        partition(c->n, c->world, 0, &first, &count);
-        const long groups = (long)((count + 31) / 32);
-        p.sched[0] = make_schedule(c, groups, (long)tiles_local, 0);
-        p.sched[1] = make_schedule(c, groups, (long)tiles_remote, kRowsPerLaunch);
-        p.parts_local = p.parts_remote = 0;
-        return p;
-    }
-    if (c->world == 1) {
-        p.parts_local = c->jsplit > 0 ? std::min<int>(c->jsplit, (int)std::min<unsigned long>(tiles_local, kMaxParts))
-                                      : auto_parts(c, p.variant, c->slice, tiles_local);
-        // up to 6 blocks the default one-sided launch keeps all j in one chunk: its workgroups then need nothing from each
-        // other and take the state update along (murb_force_integrate_kernel)
-        if (c->jsplit == 0 && c->fuse_integrate && p.variant == kOneSidedVariant && c->slots / MURB_SYM_BLOCK <= 6) p.parts_local = 1;
-        p.parts_remote = 0;
-    } else {
-        // split the requested/auto chunk count between the two launches in proportion to their tiles
-        const unsigned long tiles_all = tiles_local + tiles_remote;
-        int total = c->jsplit > 0 ? c->jsplit : auto_parts(c, p.variant, c->slice, tiles_all);
-        total = std::max(total, 2);
-        int loc = (int)std::max<unsigned long>(1ul, (unsigned long)total * tiles_local / tiles_all);
-        int rem = std::max(1, total - loc);
-        p.parts_local = (int)std::min<unsigned long>((unsigned long)loc, std::min<unsigned long>(tiles_local, kMaxParts / 2));
-        p.parts_remote = (int)std::min<unsigned long>((unsigned long)rem, std::min<unsigned long>(tiles_remote, kMaxParts / 2));
-    }
-    return p;
+    return make_plan(c->in);
 }
 
 // ---- the shards' host threads: ShardCrew (murb_crew.h), one member per shard, bound to its device for life ---------------
@@ -519,22 +150,24 @@ int timed_wait(murbhip_ctx* c, Shard& sh, int kind, hipStream_t stream, hipEvent
 }
 
 int build_sym_schedule(murbhip_ctx* c, Shard& sh, const Plan& p);
-int ensure_accp(murbhip_ctx* c, Shard& sh);
+// The one-sided kernels' partial-sum rows: kMaxParts rows of float4 per local slot, zeroed once (rows a launch does
+// not write must read as 0).  Not needed by the pair-symmetric plan, so only allocated when a one-sided launch, the
+// one-sided potential sweep or murbhip_integrate_host_acc asks for it.
+int ensure_accp(murbhip_ctx* c, Shard& sh) { return shard_alloc(sh, sh.accp, (size_t)kMaxParts * c->in.slice * sizeof(float4), sh.compute); }
 // What a shard's read-out buffer (Shard::metrics) holds, in doubles: the block rows of murb_metrics_kernel, then the pair
 // potentials of murbhip_energy — the partial sums of the two sets' groups (murb_sym_pe_sum_kernel) and the own slice's
 // diagonal blocks (murb_sym_pe_diag_kernel).  One buffer so that one copy brings a tracked iteration's numbers to the host.
 struct MetricsLayout {
-    size_t blocks, rows, pe_main, pe_tri, pe_diag, own_blocks, total;
+    size_t blocks, pe_main, pe_tri, pe_diag, own_blocks, total;
 };
 MetricsLayout metrics_layout(const murbhip_ctx* c)
 {
     MetricsLayout l{};
-    l.blocks = (c->slice + 255) / 256;
-    l.rows = 0;
+    l.blocks = (c->in.slice + 255) / 256;
     l.pe_main = l.blocks * MURB_METRIC_VALUES;
     l.pe_tri = l.pe_main + kPeSumBlocks;
     l.pe_diag = l.pe_tri + kPeSumBlocks;
-    l.own_blocks = c->slice / MURB_SYM_BLOCK;
+    l.own_blocks = c->in.slice / MURB_SYM_BLOCK;
     l.total = l.pe_diag + l.own_blocks * MURB_PE_DIAG_SPLIT;
     return l;
 }
@@ -555,11 +188,11 @@ int enqueue_force(murbhip_ctx* c, Shard& sh, const Plan& p, int which, const Mur
     if (!p.symmetric) RC_TRY(ensure_accp(c, sh));
     a.rec = sh.rec[c->cur];
     a.accp = sh.accp;
-    a.i_first_slot = (int)((unsigned long)sh.rank * c->slice);
-    a.acc_stride = (unsigned int)c->slice;
+    a.i_first_slot = (int)((unsigned long)sh.rank * c->in.slice);
+    a.acc_stride = (unsigned int)c->in.slice;
     a.soft2 = c->soft2;
-    const int tiles_local = (int)(c->slice / MURB_TILE_BODIES);
-    const int tiles_all = (int)(c->slots / MURB_TILE_BODIES);
+    const int tiles_local = (int)(c->in.slice / MURB_TILE_BODIES);
+    const int tiles_all = (int)(c->in.slots / MURB_TILE_BODIES);
     if (which == 0) {
         a.tiles = MurbTileRange{sh.rank * tiles_local, tiles_local, tiles_local, 0};
         a.chunk_first = 0;
@@ -575,11 +208,11 @@ int enqueue_force(murbhip_ctx* c, Shard& sh, const Plan& p, int which, const Mur
         RC_TRY(build_sym_schedule(c, sh, p));
         if (sh.sym_main.passes.size() > 1) {
             RC_TRY(enqueue_sym_passes(c, sh, false));
-            note_interactions(c, sh, (double)c->n * (double)c->n / (double)sh.sym_main.passes.size());
+            note_interactions(c, sh, (double)c->in.n * (double)c->in.n / (double)sh.sym_main.passes.size());
             return 0;
         }
         RC_TRY(enqueue_sym_launch(c, sh, 0, sh.sym_items_total));   // its row sum is fused into the integrate launch
-        note_interactions(c, sh, (double)c->n * (double)c->n);
+        note_interactions(c, sh, (double)c->in.n * (double)c->in.n);
         return 0;
     }
     if (p.persistent) {
@@ -623,10 +256,10 @@ MurbIntegrateArgs integrate_args(const murbhip_ctx* c, const Shard& sh, int npar
     a.vel = sh.vel;
     a.accp = sh.accp;
     a.acc_out = acc_out ? acc_out : sh.acc_out;
-    a.i_first_slot = (int)((unsigned long)sh.rank * c->slice);
+    a.i_first_slot = (int)((unsigned long)sh.rank * c->in.slice);
     a.count = (int)sh.count;
     a.nparts = nparts;
-    a.acc_stride = (unsigned int)c->slice;
+    a.acc_stride = (unsigned int)c->in.slice;
     a.dt = dt;
     a.update_state = update_state;
     return a;
@@ -640,19 +273,19 @@ int enqueue_integrate(murbhip_ctx* c, Shard& sh, int nparts, float dt, int updat
         a.group_bodies = 32;
         a.sched[0] = plan->sched[0];
         a.nsched = 1;
-        if (c->world > 1 && plan->sched[1].nblocks > 0) { a.sched[1] = plan->sched[1]; a.nsched = 2; }
+        if (c->in.world > 1 && plan->sched[1].nblocks > 0) { a.sched[1] = plan->sched[1]; a.nsched = 2; }
     }
     if (acc_from_out) a.acc_planes = sh.acc_out;   // remembered forces: nothing to sum
     if (plan && plan->symmetric && sh.sym_main.passes.size() > 1) {   // several passes: the sums are in the fp64 accumulator
         a.acc64 = sh.sym_acc64;
-        a.acc64_stride = (unsigned int)c->slots;
+        a.acc64_stride = (unsigned int)c->in.slots;
     } else if (plan && plan->symmetric) {   // one shard, triangular schedule: row sum of the partial rows + update in one launch
-        hipLaunchKernelGGL(murb_sym_rowsum_integrate_kernel, dim3((unsigned)(c->slots / 64)), dim3(MURB_ROWSUM_THREADS), 0, sh.compute,
+        hipLaunchKernelGGL(murb_sym_rowsum_integrate_kernel, dim3((unsigned)(c->in.slots / 64)), dim3(MURB_ROWSUM_THREADS), 0, sh.compute,
                            sh.sym_main.part, sh.sym_main.comp_stride, sh.sym_main.rows, a);
         return hip_rc(hipGetLastError());
     }
     if (!acc_from_out && !a.acc64) { RC_TRY(ensure_accp(c, sh)); a.accp = sh.accp; }
-    const unsigned pairs = (unsigned)(c->slice / 2);
+    const unsigned pairs = (unsigned)(c->in.slice / 2);
     hipLaunchKernelGGL(murb_integrate_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
     return hip_rc(hipGetLastError());
 }
@@ -662,7 +295,7 @@ int enqueue_integrate(murbhip_ctx* c, Shard& sh, int nparts, float dt, int updat
 // job failed — keep meeting the others, enqueue nothing.
 int shard_exchange(murbhip_ctx* c, Shard& sh, int buf, int failed)
 {
-    const size_t slice_f4 = c->slice;                  // float4 records per slice (1 per body slot)
+    const size_t slice_f4 = c->in.slice;                  // float4 records per slice (1 per body slot)
     const size_t slice_bytes = slice_f4 * sizeof(float4);
     const bool idle = is_idle(c, sh);
     int rc = failed;
@@ -676,11 +309,11 @@ int shard_exchange(murbhip_ctx* c, Shard& sh, int buf, int failed)
         span = span_begin(c, sh, kProfAllGather, sh.comm, &rc);
         RC_TRY(rc);
         float4* base = sh.rec[buf];
-        if (c->exchange_p2p && c->world > 1) {   // every slice straight to every peer: W - 1 sends and receives, one hop each
+        if (c->exchange_p2p && c->in.world > 1) {   // every slice straight to every peer: W - 1 sends and receives, one hop each
             Rccl& r = rccl();
             RC_TRY(nccl_rc(r.GroupStart()));
-            for (int d = 1; d < c->world; ++d) {
-                const int to = (sh.rank + d) % c->world, from = (sh.rank - d + c->world) % c->world;
+            for (int d = 1; d < c->in.world; ++d) {
+                const int to = (sh.rank + d) % c->in.world, from = (sh.rank - d + c->in.world) % c->in.world;
                 RC_TRY(nccl_rc(r.Send(base + (size_t)sh.rank * slice_f4, slice_f4 * 4, kRcclFloat, to, sh.comm_rccl, sh.comm)));
                 RC_TRY(nccl_rc(r.Recv(base + (size_t)from * slice_f4, slice_f4 * 4, kRcclFloat, from, sh.comm_rccl, sh.comm)));
             }
@@ -712,22 +345,14 @@ int shard_exchange(murbhip_ctx* c, Shard& sh, int buf, int failed)
     return 0;
 }
 
-// The one-sided kernels' partial-sum rows: kMaxParts rows of float4 per local slot, zeroed once (rows a launch does
-// not write must read as 0).  Not needed by the pair-symmetric plan, so only allocated when a one-sided launch, the
-// one-sided potential sweep or murbhip_integrate_host_acc asks for it.
-int ensure_accp(murbhip_ctx* c, Shard& sh)
-{
-    if (sh.accp) return 0;
-    const size_t bytes = (size_t)kMaxParts * c->slice * sizeof(float4);
-    HIP_TRY(hipMalloc((void**)&sh.accp, bytes));
-    HIP_TRY(hipMemsetAsync(sh.accp, 0, bytes, sh.compute));
-    sh.bytes += bytes;
-    return 0;
-}
+// three components, and behind them one float per group of 4 i bodies for the pair potential of a tracked evaluation
+// (murb_kernels_sym.h, PHI = 2: entry ioff / 4 + group; zero wherever no item has groups)
+inline size_t sym_part_bytes(size_t floats) { return (3 * floats + floats / MURB_SYM_R + 1) * sizeof(float); }
 
-void free_sym_set(SymSet& st)
+void free_sym_set(Shard& sh, SymSet& st)
 {
-    release(st.part, st.rows);
+    shard_free(sh, st.part, sym_part_bytes(st.comp_stride));
+    shard_free(sh, st.rows, (size_t)st.nblocks * sizeof(MurbSymBlockRows));
     st = SymSet{};
 }
 
@@ -736,14 +361,10 @@ int upload_sym_set(Shard& sh, SymSet& st, const std::vector<MurbSymBlockRows>& t
     st.comp_stride = floats;
     st.nblocks = (int)table.size();
     if (floats == 0) return 0;
-    // three components, and behind them one float per group of 4 i bodies for the pair potential of a tracked evaluation
-    // (murb_kernels_sym.h, PHI = 2: entry ioff / 4 + group; zero wherever no item has groups)
-    const size_t bytes = (3 * floats + floats / MURB_SYM_R + 1) * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&st.part, bytes));
-    HIP_TRY(hipMemsetAsync(st.part, 0, bytes, sh.compute));   // every cell has a writer; zero anyway (on OUR stream: non-blocking w.r.t. stream 0)
-    HIP_TRY(hipMalloc((void**)&st.rows, table.size() * sizeof(MurbSymBlockRows)));
+    // every cell has a writer; zero anyway (on OUR stream: non-blocking w.r.t. stream 0)
+    RC_TRY(shard_alloc(sh, st.part, sym_part_bytes(floats), sh.compute));
+    RC_TRY(shard_alloc(sh, st.rows, table.size() * sizeof(MurbSymBlockRows)));
     HIP_TRY(hipMemcpy(st.rows, table.data(), table.size() * sizeof(MurbSymBlockRows), hipMemcpyHostToDevice));
-    sh.sym_bytes += bytes + table.size() * sizeof(MurbSymBlockRows);
     return 0;
 }
 
@@ -754,96 +375,73 @@ int upload_sym_set(Shard& sh, SymSet& st, const std::vector<MurbSymBlockRows>& t
 // unordered body pair is evaluated by exactly one rank.  A rank's partial sums for ALL slices it
 // touched are then row-summed into one chunk per slice and combined with ONE reduce-scatter (each
 // rank receives the complete accelerations of its own bodies); positions travel as before.
-// Exchange pipeline: the own-slice triangle is T_s (T_s + 1) / 2 block pairs in TWO launches (one under each collective); with
-// few blocks per slice neither fills the chip's 4 x CUs workgroup slots and both run at a fraction of the issue rate.
-// Their items (and only theirs) are cut finer until each launch has ~2 rounds of them ("tri_div" overrides).
-int plan_tri_div(const murbhip_ctx* c, const Plan& p)
+inline bool exchange_mode(const murbhip_ctx* c) { return c->in.world > 1 || c->force_exchange; }
+SymLayoutKey layout_key(const murbhip_ctx* c, const Plan& p)
 {
-    if (c->tri_div > 0) return c->tri_div;
-    if (c->world == 1) return 1;
-    const long tb = (long)(c->slice / MURB_SYM_BLOCK);
-    const long items = tb * (tb + 1) / 2 * p.split / 2;             // per triangle launch
-    const long slots = 4L * std::max(c->cu_count, 1) * 4 / p.waves;  // resident workgroups
-    int div = 1;
-    while (div < 4 && items * div < 2 * slots && MURB_SYM_BLOCK / (p.split * div * 2) >= 16 * p.waves) div *= 2;
-    return div;
+    return sym_layout_key(c->in, p, exchange_mode(c), c->overlap, c->tri_first_pct, c->xcd_order != 0, c->pad_aware != 0);
 }
 
-// false when the shard's tables were built for exactly this plan and these options.  A rebuild of EXISTING tables needs
-// every shard of the process drained first (the peer-read sums of the previous step may still be reading this shard's
-// send buffer): enqueue_iteration and murbhip_energy do that on the caller's thread before the shards' threads start.
-bool sym_schedule_stale(const murbhip_ctx* c, const Shard& sh, const Plan& p)
+// false when the shard's tables were built for exactly this key.  A rebuild of EXISTING tables needs every shard of the
+// process drained first (the peer-read sums of the previous step may still be reading this shard's send buffer):
+// drain_for_rebuild does that on the caller's thread before the shards' threads start.
+inline bool sym_schedule_stale(const Shard& sh, const SymLayoutKey& key) { return !sh.sym_items || !(sh.key == key); }
+int drain_for_rebuild(murbhip_ctx* c, const Plan& p)
 {
-    const bool exchange_mode = c->world > 1 || c->force_exchange;
-    return !(sh.sym_items && sh.sym_split == p.split && sh.sym_waves == p.waves && sh.sym_taper == p.taper && sh.sym_diag_tri == (int)p.diag_tri &&
-             sh.sym_exchange_mode == exchange_mode && sh.sym_xcd_order == c->xcd_order && sh.sym_pass_mb == c->sym_pass_mb &&
-             sh.sym_pad_aware == c->pad_aware && sh.sym_tri_div == plan_tri_div(c, p) &&
-             (!exchange_mode || (sh.sym_tri_first == c->tri_first_pct && sh.sym_overlap == c->overlap)));
+    if (!p.symmetric) return 0;
+    const SymLayoutKey key = layout_key(c, p);
+    for (const Shard& sh : c->shards)
+        if (sh.sym_items && sym_schedule_stale(sh, key)) return murbhip_sync(c);   // nothing may be in flight
+    return 0;
 }
 
 int build_sym_schedule(murbhip_ctx* c, Shard& sh, const Plan& p)
 {
-    const bool exchange_mode = c->world > 1 || c->force_exchange;
+    const SymLayoutKey key = layout_key(c, p);
     sh.sym_red = p.red;
-    if (!sym_schedule_stale(c, sh, p)) return 0;
-    release(sh.sym_items); sh.sym_items = nullptr;
-    free_sym_set(sh.sym_main);
-    free_sym_set(sh.sym_tri);
-    sh.bytes -= sh.sym_bytes;
-    sh.sym_bytes = 0;
+    if (!sym_schedule_stale(sh, key)) return 0;
+    shard_free(sh, sh.sym_items, (size_t)sh.sym_items_total * sizeof(MurbSymItem));
+    free_sym_set(sh, sh.sym_main);
+    free_sym_set(sh, sh.sym_tri);
 
     SymHostLayout L;
-    plan_sym_layout(c->world, sh.rank, sym_fill(c->n, c->world, c->pad_aware != 0), p.split, p.waves, p.taper, p.diag_tri, exchange_mode,
-                    c->overlap, c->tri_first_pct, c->xcd_order != 0, sym_pass_budget(c) / (3 * sizeof(float)), L, plan_tri_div(c, p));
-    if (!exchange_mode && L.passes.size() == 1 && (int)L.table_main.size() != (int)(c->slots / MURB_SYM_BLOCK))
+    plan_sym_layout(c->in.world, sh.rank, sym_fill(c->in.n, c->in.world, key.pad_aware), key, L);
+    if (!key.exchange_mode && L.passes.size() == 1 && (int)L.table_main.size() != (int)(c->in.slots / MURB_SYM_BLOCK))
         return MURBHIP_E_STATE;   // the fused row sum + integrate walks every block
     RC_TRY(upload_sym_set(sh, sh.sym_tri, L.table_tri, L.floats_tri));
     RC_TRY(upload_sym_set(sh, sh.sym_main, L.table_main, L.floats_main));
     sh.sym_main.passes = L.passes;
-    sh.sym_pass_mb = c->sym_pass_mb;
-    sh.sym_pad_aware = c->pad_aware;
-    sh.sym_tri_div = plan_tri_div(c, p);
-    if (L.passes.size() > 1 && !sh.sym_acc64) {
-        HIP_TRY(hipMalloc((void**)&sh.sym_acc64, 3 * c->slots * sizeof(double)));
-        sh.bytes += 3 * c->slots * sizeof(double);
-    }
-    const std::vector<MurbSymItem>& items = L.items;
-    const size_t own_pieces = (size_t)L.own;
-    const int W = c->world;
-    sh.sym_items_own = (int)own_pieces;
-    sh.sym_items_total = (int)items.size();
-    sh.sym_split = p.split;
-    sh.sym_waves = p.waves;
-    sh.sym_taper = p.taper;
-    sh.sym_diag_tri = (int)p.diag_tri;
-    sh.sym_xcd_order = c->xcd_order;
-    sh.sym_exchange_mode = exchange_mode;
-    sh.sym_tri_first = c->tri_first_pct;
-    sh.sym_overlap = c->overlap;
+    if (L.passes.size() > 1) RC_TRY(shard_alloc(sh, sh.sym_acc64, 3 * c->in.slots * sizeof(double)));
+    sh.sym_items_own = L.own;
+    sh.sym_items_total = (int)L.items.size();
     sh.sym_t1 = L.t1;
-    HIP_TRY(hipMalloc((void**)&sh.sym_items, items.size() * sizeof(MurbSymItem)));
-    HIP_TRY(hipMemcpy(sh.sym_items, items.data(), items.size() * sizeof(MurbSymItem), hipMemcpyHostToDevice));
-    sh.sym_bytes += items.size() * sizeof(MurbSymItem);
-    if (exchange_mode) {
-        const size_t chunk = (size_t)3 * c->slice * sizeof(float);
-        if (!sh.sym_send) {
-            HIP_TRY(hipMalloc((void**)&sh.sym_send, chunk * W));
-            HIP_TRY(hipMalloc((void**)&sh.sym_recv, chunk));
-            HIP_TRY(hipMalloc((void**)&sh.sym_tri_acc, chunk));
-            if (W > 1) {   // receive area of the point-to-point exchange (read as 0 where nothing has arrived yet)
-                HIP_TRY(hipMalloc((void**)&sh.sym_p2p, chunk * (size_t)(W / 2)));
-                HIP_TRY(hipMemsetAsync(sh.sym_p2p, 0, chunk * (size_t)(W / 2), sh.compute));
-                sh.bytes += chunk * (size_t)(W / 2);
-            }
-            HIP_TRY(hipEventCreateWithFlags(&sh.ev_rowsum, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&sh.ev_reduced, hipEventDisableTiming));
-            sh.bytes += chunk * (W + 2);
-        }
+    RC_TRY(shard_alloc(sh, sh.sym_items, L.items.size() * sizeof(MurbSymItem)));
+    HIP_TRY(hipMemcpy(sh.sym_items, L.items.data(), L.items.size() * sizeof(MurbSymItem), hipMemcpyHostToDevice));
+    sh.key = key;
+    if (key.exchange_mode) {
+        const int W = c->in.world;
+        const size_t chunk = (size_t)3 * c->in.slice * sizeof(float);
+        RC_TRY(shard_alloc(sh, sh.sym_send, chunk * W));
+        RC_TRY(shard_alloc(sh, sh.sym_recv, chunk));
+        RC_TRY(shard_alloc(sh, sh.sym_tri_acc, chunk));
+        // receive area of the point-to-point exchange (read as 0 where nothing has arrived yet)
+        if (W > 1) RC_TRY(shard_alloc(sh, sh.sym_p2p, chunk * (size_t)(W / 2), sh.compute));
+        if (!sh.ev_rowsum) HIP_TRY(hipEventCreateWithFlags(&sh.ev_rowsum, hipEventDisableTiming));
+        if (!sh.ev_reduced) HIP_TRY(hipEventCreateWithFlags(&sh.ev_reduced, hipEventDisableTiming));
         // chunks of slices this rank has no rows for are never written by the row sum: they must read as 0
         HIP_TRY(hipMemsetAsync(sh.sym_send, 0, chunk * W, sh.compute));
     }
-    sh.bytes += sh.sym_bytes;
     return 0;
+}
+
+// form: 0 forces, i-side sums in registers; 1 potential sweep; 2 forces + pair potential; 3 forces, i-side sums through LDS
+template <int WAVES>
+void launch_sym_t(int form, int count, hipStream_t stream, const MurbSymArgs& sa)
+{
+    const dim3 grid((unsigned)count), block(64 * WAVES);
+    if (form == 1) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 1>), grid, block, 0, stream, sa);
+    else if (form == 2) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 2, 1>), grid, block, 0, stream, sa);
+    else if (form == 3) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 0, 1>), grid, block, 0, stream, sa);
+    else hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1>), grid, block, 0, stream, sa);
 }
 
 int enqueue_sym_launch(murbhip_ctx* c, Shard& sh, int first, int count, bool own_triangle_rows, hipStream_t stream,
@@ -865,18 +463,9 @@ int enqueue_sym_launch(murbhip_ctx* c, Shard& sh, int first, int count, bool own
     int rc_span = 0;
     const int sp = timed ? span_begin(c, sh, kind, stream, &rc_span) : -1;
     RC_TRY(rc_span);
-    const dim3 grid((unsigned)count);
-    if (sh.sym_waves == 8) {
-        if (potential) hipLaunchKernelGGL((murb_force_sym_kernel<4, 8, 1, 1>), grid, dim3(512), 0, stream, sa);
-        else if (with_pe) hipLaunchKernelGGL((murb_force_sym_kernel<4, 8, 1, 2, 1>), grid, dim3(512), 0, stream, sa);
-        else if (sh.sym_red == 1) hipLaunchKernelGGL((murb_force_sym_kernel<4, 8, 1, 0, 1>), grid, dim3(512), 0, stream, sa);
-        else hipLaunchKernelGGL((murb_force_sym_kernel<4, 8, 1>), grid, dim3(512), 0, stream, sa);
-    } else {
-        if (potential) hipLaunchKernelGGL((murb_force_sym_kernel<4, 4, 1, 1>), grid, dim3(256), 0, stream, sa);
-        else if (with_pe) hipLaunchKernelGGL((murb_force_sym_kernel<4, 4, 1, 2, 1>), grid, dim3(256), 0, stream, sa);
-        else if (sh.sym_red == 1) hipLaunchKernelGGL((murb_force_sym_kernel<4, 4, 1, 0, 1>), grid, dim3(256), 0, stream, sa);
-        else hipLaunchKernelGGL((murb_force_sym_kernel<4, 4, 1>), grid, dim3(256), 0, stream, sa);
-    }
+    const int form = potential ? 1 : (with_pe ? 2 : (sh.sym_red == 1 ? 3 : 0));
+    if (sh.key.waves == 8) launch_sym_t<8>(form, count, stream, sa);
+    else launch_sym_t<4>(form, count, stream, sa);
     RC_TRY(hip_rc(hipGetLastError()));
     RC_TRY(span_end(sh, sp, stream));
     return 0;
@@ -896,15 +485,15 @@ int enqueue_sym_rowsum(const SymSet& st, float* out, unsigned int out_slice_slot
 // enqueued (ev_rowsum recorded; with peer copies: after the meet() that follows).
 int shard_reduce_scatter(murbhip_ctx* c, Shard& sh)
 {
-    const unsigned int chunk_floats = (unsigned int)(3 * c->slice);
+    const unsigned int chunk_floats = (unsigned int)(3 * c->in.slice);
     const bool idle = is_idle(c, sh);
     int rc = 0, span = -1;
-    if (c->exchange == 1 && c->exchange_p2p && c->world > 1) {
+    if (c->exchange == 1 && c->exchange_p2p && c->in.world > 1) {
         // Point-to-point form.  Under the half-ring schedule a rank only has contributions for the floor(W/2) slices ahead of
         // it (and its own): the reduce-scatter moves and adds zeros for the rest.  Here every rank sends those chunks straight
         // to their owners (one xGMI hop each, all links at once) and adds up what the floor(W/2) ranks behind it sent.
         Rccl& r = rccl();
-        const int W = c->world, D = W / 2;
+        const int W = c->in.world, D = W / 2;
         HIP_TRY(hipStreamWaitEvent(sh.comm, sh.ev_rowsum, 0));
         span = span_begin(c, sh, kProfReduceScatter, sh.comm, &rc);
         RC_TRY(rc);
@@ -928,7 +517,7 @@ int shard_reduce_scatter(murbhip_ctx* c, Shard& sh)
         // Under the half-ring schedule only the floor(W/2) ranks BEHIND this one (and the rank itself) hold contributions to its
         // slice: the chunks the others keep for it are zero and are not read (no xGMI traffic for zeros).  Fixed order: own,
         // then by distance along the ring.
-        const int W = c->world, D = W / 2;
+        const int W = c->in.world, D = W / 2;
         MurbPeerPtrs peers{};
         peers.n = 0;
         for (int d = 0; d <= D; ++d) {
@@ -954,7 +543,7 @@ int wait_send_buffer_free(murbhip_ctx* c, Shard& sh)
 {
     if (!c->reduce_pending) return 0;
     if (c->exchange == 0) {   // the readers of this shard's send buffer: itself and the floor(W/2) ranks AHEAD of it (shard_reduce_scatter)
-        const int W = c->world, D = W / 2;
+        const int W = c->in.world, D = W / 2;
         for (Shard& peer : c->shards)
             if ((peer.rank - sh.rank + W) % W <= D) HIP_TRY(hipStreamWaitEvent(sh.compute, peer.ev_reduced, 0));
     } else HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_reduced, 0));
@@ -992,18 +581,18 @@ int shard_iteration_sym_multi(murbhip_ctx* c, Shard& sh, const Plan& p, float dt
             // the positions are still being gathered, then fills the gaps and the tail of the rectangles
             if (c->gather_pending || c->reduce_pending) HIP_TRY(hipStreamWaitEvent(sh.compute_low, sh.ev_integrated, 0));
             RC_TRY(enqueue_sym_launch(c, sh, 0, own, true, sh.compute_low));
-            RC_TRY(enqueue_sym_rowsum(sh.sym_tri, sh.sym_tri_acc, (unsigned int)c->slice, sh.compute_low));
+            RC_TRY(enqueue_sym_rowsum(sh.sym_tri, sh.sym_tri_acc, (unsigned int)c->in.slice, sh.compute_low));
             HIP_TRY(hipEventRecord(sh.ev_tri, sh.compute_low));
         }
         RC_TRY(enqueue_sym_launch(c, sh, 0, t1, true, nullptr, false, 0, kProfTri1));
         if (c->gather_pending) RC_TRY(timed_wait(c, sh, kProfWaitGather, sh.compute, sh.ev_gathered));
         RC_TRY(enqueue_sym_launch(c, sh, own, sh.sym_items_total - own, false, nullptr, false, 0, kProfRect));
         RC_TRY(wait_send_buffer_free(c, sh));
-        RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.sym_send, (unsigned int)c->slice, sh.compute));
+        RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.sym_send, (unsigned int)c->in.slice, sh.compute));
         HIP_TRY(hipEventRecord(sh.ev_rowsum, sh.compute));
         // what ONE launch covers on average: the rank's share of the step over its non-empty force launches
         const int launches = (t1 > 0) + (own - t1 > 0 || c->overlap == 2) + (sh.sym_items_total - own > 0);
-        note_interactions(c, sh, (double)sh.count * (double)c->n / (double)std::max(launches, 1));
+        note_interactions(c, sh, (double)sh.count * (double)c->in.n / (double)std::max(launches, 1));
         return 0;
     }();
     if (copies) c->crew->meet();   // every shard's ev_rowsum is recorded
@@ -1016,25 +605,13 @@ int shard_iteration_sym_multi(murbhip_ctx* c, Shard& sh, const Plan& p, float dt
             RC_TRY(enqueue_sym_launch(c, sh, t1, own - t1, true, nullptr, false, 0, kProfTri2));
         }
         RC_TRY(timed_wait(c, sh, kProfWaitReduce, sh.compute, sh.ev_reduced));
-        MurbIntegrateArgs a{};
-        a.rec_in = sh.rec[c->cur];
-        a.rec_out = sh.rec[c->cur ^ 1];
-        a.vel = sh.vel;
-        a.accp = sh.accp;
-        a.acc_out = sh.acc_out;
+        MurbIntegrateArgs a = integrate_args(c, sh, 0, dt, update_state);   // no one-sided partial rows: the sums come in planes
         a.acc_planes = sh.sym_recv;
-        a.scheme = c->integrator;
-        a.kick_dt = leapfrog_kick(c, dt);
-        a.i_first_slot = (int)((unsigned long)sh.rank * c->slice);
-        a.count = (int)sh.count;
-        a.acc_stride = (unsigned int)c->slice;
-        a.dt = dt;
-        a.update_state = update_state;
         if (c->overlap == 2) {   // the triangle's row sums were taken on the other stream
             a.acc_planes2 = sh.sym_tri_acc;
-            hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
+            hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->in.slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
         } else {                 // row sum of the triangle's rows + the reduced share + state update in one launch
-            hipLaunchKernelGGL(murb_sym_rowsum_integrate_kernel, dim3((unsigned)(c->slice / 64)), dim3(MURB_ROWSUM_THREADS), 0, sh.compute,
+            hipLaunchKernelGGL(murb_sym_rowsum_integrate_kernel, dim3((unsigned)(c->in.slice / 64)), dim3(MURB_ROWSUM_THREADS), 0, sh.compute,
                                sh.sym_tri.part, sh.sym_tri.comp_stride, sh.sym_tri.rows, a);
         }
         RC_TRY(hip_rc(hipGetLastError()));
@@ -1049,7 +626,7 @@ int shard_iteration_sym_multi(murbhip_ctx* c, Shard& sh, const Plan& p, float dt
 // One GPU, several passes: every pass's items into the shared row buffer, its row sums added to the fp64 accumulator.
 int enqueue_sym_passes(murbhip_ctx* c, Shard& sh, bool potential)
 {
-    HIP_TRY(hipMemsetAsync(sh.sym_acc64, 0, 3 * c->slots * sizeof(double), sh.compute));
+    HIP_TRY(hipMemsetAsync(sh.sym_acc64, 0, 3 * c->in.slots * sizeof(double), sh.compute));
     // force + pair potential (murbhip_energy): every pass has a layout of its own in the shared buffer, so the plane of the
     // groups' potentials — one float per group of the pass's i rows, zero elsewhere — is cleared before the pass and summed
     // right after it, into the same doubles of the read-out buffer pass after pass
@@ -1067,7 +644,7 @@ int enqueue_sym_passes(murbhip_ctx* c, Shard& sh, bool potential)
             first = false;
         }
         hipLaunchKernelGGL(murb_sym_rowsum_acc_kernel, dim3((unsigned)ps.table_count * (MURB_SYM_BLOCK / 64)), dim3(MURB_ROWSUM_THREADS), 0,
-                           sh.compute, sh.sym_main.part, ps.floats, sh.sym_main.rows + ps.table_first, sh.sym_acc64, (unsigned int)c->slots);
+                           sh.compute, sh.sym_main.part, ps.floats, sh.sym_main.rows + ps.table_first, sh.sym_acc64, (unsigned int)c->in.slots);
         RC_TRY(hip_rc(hipGetLastError()));
     }
     return 0;
@@ -1085,9 +662,9 @@ int shard_potential_sym_multi(murbhip_ctx* c, Shard& sh, const Plan& p)
         if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
         RC_TRY(enqueue_sym_launch(c, sh, 0, sh.sym_items_own, true, nullptr, true));
         RC_TRY(enqueue_sym_launch(c, sh, sh.sym_items_own, sh.sym_items_total - sh.sym_items_own, false, nullptr, true));
-        RC_TRY(enqueue_sym_rowsum(sh.sym_tri, sh.sym_tri_acc, (unsigned int)c->slice, sh.compute));
+        RC_TRY(enqueue_sym_rowsum(sh.sym_tri, sh.sym_tri_acc, (unsigned int)c->in.slice, sh.compute));
         RC_TRY(wait_send_buffer_free(c, sh));
-        RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.sym_send, (unsigned int)c->slice, sh.compute));
+        RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.sym_send, (unsigned int)c->in.slice, sh.compute));
         HIP_TRY(hipEventRecord(sh.ev_rowsum, sh.compute));
         return 0;
     }();
@@ -1102,31 +679,31 @@ int shard_potential_sym_multi(murbhip_ctx* c, Shard& sh, const Plan& p)
     a.acc_out = sh.phi_out;
     a.acc_planes = sh.sym_recv;
     a.acc_planes2 = sh.sym_tri_acc;
-    a.i_first_slot = (int)((unsigned long)sh.rank * c->slice);
+    a.i_first_slot = (int)((unsigned long)sh.rank * c->in.slice);
     a.count = (int)sh.count;
-    a.acc_stride = (unsigned int)c->slice;
+    a.acc_stride = (unsigned int)c->in.slice;
     a.update_state = 0;
-    hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
+    hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->in.slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
     return hip_rc(hipGetLastError());
 }
 
 // One iteration with the one-sided kernels (or with one shard and no exchange): one shard's share, on its thread.
 int shard_iteration_plain(murbhip_ctx* c, Shard& sh, const Plan& p, float dt, int update_state, bool reuse)
 {
-    const bool exchange = update_state && (c->world > 1 || c->force_exchange);
+    const bool exchange = update_state && (c->in.world > 1 || c->force_exchange);
     int rc = 0;
     if (!is_idle(c, sh)) rc = [&]() -> int {   // timing aid: see "solo_shard"
         // one-sided kernel, one GPU, one j chunk: the state update rides in the tail of the force launch (murb_force_integrate_kernel)
         bool fused = false;
         MurbIntegrateArgs then{};
-        const bool may_fuse = c->fuse_integrate && !reuse && !p.symmetric && !p.persistent && p.variant == kOneSidedVariant &&
-                              c->world == 1 && p.parts_local + p.parts_remote == 1;
+        const bool may_fuse = c->in.fuse_integrate && !reuse && !p.symmetric && !p.persistent && p.variant == kOneSidedVariant &&
+                              c->in.world == 1 && p.parts_local + p.parts_remote == 1;
         if (may_fuse) {
             RC_TRY(ensure_accp(c, sh));
             then = integrate_args(c, sh, p.parts_local + p.parts_remote, dt, update_state);
         }
         const MurbIntegrateArgs* const tail = may_fuse ? &then : nullptr;
-        if (c->world == 1 || reuse) {   // reuse: the forces at these positions are in acc_out, only the update is left
+        if (c->in.world == 1 || reuse) {   // reuse: the forces at these positions are in acc_out, only the update is left
             if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
             if (!reuse) RC_TRY(enqueue_force(c, sh, p, 0, tail, &fused));
         } else if (c->overlap) {
@@ -1159,9 +736,7 @@ void invalidate_cached_forces(murbhip_ctx* c)
 
 int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
 {
-    const Plan p = make_plan(c);
-    c->last_parts = p.parts_local + p.parts_remote;
-    c->plan_waves = p.symmetric ? p.waves : 4;
+    const Plan p = current_plan(c);
     c->herm_in_acc_out = false;   // acc_out is the force plan's from here on
     // forces at the current positions are already in acc_out (compute_acc, or a leapfrog read-out, just ran): an
     // evaluation needs nothing at all, a state update (one shard, no exchange) only the integrate launch
@@ -1170,14 +745,10 @@ int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
     c->acc_current = false;
     c->pe_current = false;
     if (have_acc && !update_state && (!c->want_pe || have_pe)) { c->acc_current = true; c->pe_current = have_pe; return 0; }
-    const bool exchanging = c->world > 1 || c->force_exchange;
+    const bool exchanging = exchange_mode(c);
     // ... with several shards: the integrate launch from the remembered forces and the position exchange
     const bool reuse = have_acc && update_state && c->solo_shard < 0;
-    if (p.symmetric) {
-        bool stale = false;
-        for (const Shard& sh : c->shards) stale = stale || (sh.sym_items && sym_schedule_stale(c, sh, p));
-        if (stale) RC_TRY(murbhip_sync(c));   // tables are rebuilt below: nothing may be in flight
-    }
+    RC_TRY(drain_for_rebuild(c, p));   // tables are rebuilt below
     if (p.symmetric && exchanging && !reuse)
         RC_TRY(crew_run(c, [&](Shard& sh) { return shard_iteration_sym_multi(c, sh, p, dt, update_state); }));
     else
@@ -1200,41 +771,19 @@ int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
 // 4 waves per workgroup, 2 position + 2 velocity tiles per stage (32 KiB of LDS, like the one-sided force kernel).
 constexpr int kHermiteR = 4, kHermiteWaves = 4, kHermiteStage = 2;
 
-// j chunks of the sweep: the one-sided kernels' rule ("jsplit" overrides), for i groups of 16 bodies
-int hermite_parts(const murbhip_ctx* c)
-{
-    const unsigned long tiles = c->slots / MURB_TILE_BODIES;
-    if (c->jsplit > 0) return (int)std::min<unsigned long>((unsigned long)c->jsplit, std::min<unsigned long>(tiles, kMaxParts / 2));
-    return auto_parts(c, kOneSidedFewBodies, c->slots, tiles);
-}
-
 int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
 {
     // each buffer under its own guard: a failed allocation leaves its pointer null and the next call tries again
-    const size_t rec_bytes = c->slots * sizeof(float4), plane_bytes = 3 * c->slots * sizeof(float);
-    for (float4** p : {&sh.herm_rec, &sh.herm_vel}) {
-        if (*p) continue;
-        HIP_TRY(hipMalloc((void**)p, rec_bytes));
-        sh.bytes += rec_bytes;
-    }
-    for (float** p : {&sh.herm_a0, &sh.herm_j0}) {
-        if (*p) continue;
-        HIP_TRY(hipMalloc((void**)p, plane_bytes));
-        sh.bytes += plane_bytes;
-        const int rc = hip_rc(hipMemsetAsync(*p, 0, plane_bytes, sh.compute));
-        if (rc) return rc;
-    }
+    const size_t rec_bytes = c->in.slots * sizeof(float4), plane_bytes = 3 * c->in.slots * sizeof(float);
+    for (float4** p : {&sh.herm_rec, &sh.herm_vel}) RC_TRY(shard_alloc(sh, *p, rec_bytes));
+    for (float** p : {&sh.herm_a0, &sh.herm_j0}) RC_TRY(shard_alloc(sh, *p, plane_bytes, sh.compute));
     if (rows > sh.herm_rows) {   // more chunks than before ("jsplit"): the rows in flight are read by an enqueued corrector
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        release(sh.herm_part);
-        sh.herm_part = nullptr;
-        sh.bytes -= (size_t)2 * sh.herm_rows * c->slots * sizeof(float4);
+        shard_free(sh, sh.herm_part, (size_t)2 * sh.herm_rows * c->in.slots * sizeof(float4));
         sh.herm_rows = 0;
-        const size_t bytes = (size_t)2 * rows * c->slots * sizeof(float4);
-        HIP_TRY(hipMalloc((void**)&sh.herm_part, bytes));
-        HIP_TRY(hipMemsetAsync(sh.herm_part, 0, bytes, sh.compute));   // slots past the last i group have no writer: they read as 0
+        // slots past the last i group have no writer: they read as 0
+        RC_TRY(shard_alloc(sh, sh.herm_part, (size_t)2 * rows * c->in.slots * sizeof(float4), sh.compute));
         sh.herm_rows = rows;
-        sh.bytes += bytes;
     }
     return 0;
 }
@@ -1247,51 +796,56 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
     a.a0 = sh.herm_a0;
     a.j0 = sh.herm_j0;
     a.part_a = sh.herm_part;
-    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
+    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->in.slots;
     a.acc_out = sh.acc_out;
     a.nparts = parts;
     a.count = (int)sh.count;
-    a.stride = (unsigned int)c->slots;
+    a.stride = (unsigned int)c->in.slots;
     a.dt = dt;
     a.update_state = update_state;
     return a;
 }
 
-// accelerations and jerks of the state (rec, vel) into the partial rows
-int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts)
+// accelerations and jerks of the state (rec, vel) into the partial rows.  `ctl`: the control-block form of an adaptive step
+// (enqueue_hermite_adaptive), which records no timing span.
+int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts, MurbEvolveCtl* ctl = nullptr)
 {
     MurbJerkArgs a{};
     a.rec = rec;
     a.vel = vel;
     a.part_a = sh.herm_part;
-    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
-    a.tiles = (int)(c->slots / MURB_TILE_BODIES);
+    a.part_j = sh.herm_part + (size_t)sh.herm_rows * c->in.slots;
+    a.tiles = (int)(c->in.slots / MURB_TILE_BODIES);
     a.nchunks = parts;
-    a.stride = (unsigned int)c->slots;
+    a.stride = (unsigned int)c->in.slots;
     a.soft2 = c->soft2;
     constexpr int group = kHermiteWaves * kHermiteR;
     const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);   // whole i groups: the extra slots hold mass 0
-    int rc = 0;
-    const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
-    RC_TRY(rc);
-    hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a);
-    RC_TRY(hip_rc(hipGetLastError()));
-    RC_TRY(span_end(sh, sp, sh.compute));
-    note_interactions(c, sh, (double)sh.count * (double)c->slots);
-    return 0;
+    if (!ctl) {
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a);
+        RC_TRY(hip_rc(hipGetLastError()));
+        RC_TRY(span_end(sh, sp, sh.compute));
+        note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
+        return 0;
+    }
+    hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute,
+                       a, ctl);
+    return hip_rc(hipGetLastError());
 }
 
 // update_state 0: make sure (a0, j0) of the current state are remembered; 1: one step.
 int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
 {
-    if (c->world != 1 || c->shards.size() != 1 || c->force_exchange) return MURBHIP_E_STATE;
+    if (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange) return MURBHIP_E_STATE;
     Shard& sh = c->shards[0];
     HIP_TRY(hipSetDevice(sh.device));
-    const int parts = hermite_parts(c);
-    c->last_parts = parts;
+    const int parts = hermite_parts(c->in);
     RC_TRY(ensure_hermite(c, sh, parts));
     if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
-    const unsigned pairs = (unsigned)(c->slots / 2);
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
     if (!c->herm_current) {
         RC_TRY(enqueue_hermite_sweep(c, sh, sh.rec[c->cur], sh.vel, parts));
         const MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 0);
@@ -1304,7 +858,7 @@ int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
     }
     if (!update_state) {
         if (!c->herm_in_acc_out) {   // a force evaluation has used acc_out since: murbhip_download_acc is to return THIS evaluation's
-            HIP_TRY(hipMemcpyAsync(sh.acc_out, sh.herm_a0, 3 * c->slots * sizeof(float), hipMemcpyDeviceToDevice, sh.compute));
+            HIP_TRY(hipMemcpyAsync(sh.acc_out, sh.herm_a0, 3 * c->in.slots * sizeof(float), hipMemcpyDeviceToDevice, sh.compute));
             c->acc_current = false;
             c->pe_current = false;
             c->herm_in_acc_out = true;
@@ -1336,26 +890,13 @@ constexpr size_t kEvolveHead = offsetof(MurbEvolveCtl, ring);   // what the host
 // the device still takes the step or has finished, the records end up in the other position buffer.
 int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
 {
-    const unsigned pairs = (unsigned)(c->slots / 2);
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
     MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 1);
     a.rec_out = sh.herm_rec;
     a.vel_out = sh.herm_vel;
     hipLaunchKernelGGL(murb_hermite_predict_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
     RC_TRY(hip_rc(hipGetLastError()));
-    MurbJerkArgs j{};
-    j.rec = sh.herm_rec;
-    j.vel = sh.herm_vel;
-    j.part_a = sh.herm_part;
-    j.part_j = sh.herm_part + (size_t)sh.herm_rows * c->slots;
-    j.tiles = (int)(c->slots / MURB_TILE_BODIES);
-    j.nchunks = parts;
-    j.stride = (unsigned int)c->slots;
-    j.soft2 = c->soft2;
-    constexpr int group = kHermiteWaves * kHermiteR;
-    const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);
-    hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0,
-                       sh.compute, j, sh.herm_ctl);
-    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(enqueue_hermite_sweep(c, sh, sh.herm_rec, sh.herm_vel, parts, sh.herm_ctl));
     a.rec_out = sh.rec[c->cur ^ 1];
     a.vel_out = nullptr;
     hipLaunchKernelGGL(murb_hermite_correct_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
@@ -1374,14 +915,15 @@ int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
 // has default priority and the default (blocking with respect to stream 0) flag — the library never uses stream 0, but a
 // host application that does (torch's default stream) then synchronises with the force kernels implicitly
 // (include/murbhip.h, "cu_reserve").  The low-priority stream of "overlap" 2 stays unmasked so that it keeps its priority.
-int create_compute_streams(const murbhip_ctx* c, Shard& sh, int reserve)
+int create_compute_streams(const murbhip_ctx* c, Shard& sh, int reserve, int* highest_priority = nullptr)
 {
     int least = 0, greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (highest_priority) *highest_priority = greatest;
     HIP_TRY(hipStreamCreateWithPriority(&sh.compute_low, hipStreamNonBlocking, least));
-    if (reserve > 0 && c->cu_count > reserve) {
-        std::vector<uint32_t> mask((size_t)(c->cu_count + 31) / 32, 0u);
-        for (int b = 0; b < c->cu_count - reserve; ++b) mask[(size_t)b / 32] |= 1u << (b % 32);
+    if (reserve > 0 && c->in.cu_count > reserve) {
+        std::vector<uint32_t> mask((size_t)(c->in.cu_count + 31) / 32, 0u);
+        for (int b = 0; b < c->in.cu_count - reserve; ++b) mask[(size_t)b / 32] |= 1u << (b % 32);
         HIP_TRY(hipExtStreamCreateWithCUMask(&sh.compute, (uint32_t)mask.size(), mask.data()));
         return 0;
     }
@@ -1401,10 +943,10 @@ int create_common(murbhip_ctx** out, unsigned long n, float soft, float g, int w
 
     murbhip_ctx* c = new (std::nothrow) murbhip_ctx;
     if (!c) return MURBHIP_E_NOMEM;
-    c->n = n;
-    c->world = world;
-    c->slice = slice_slots(n, world);
-    c->slots = c->slice * (unsigned long)world;
+    c->in.n = n;
+    c->in.world = world;
+    c->in.slice = slice_slots(n, world);
+    c->in.slots = c->in.slice * (unsigned long)world;
     c->soft2 = soft * soft;
     c->g = g;
     c->exchange = exchange;
@@ -1413,7 +955,7 @@ int create_common(murbhip_ctx** out, unsigned long n, float soft, float g, int w
 
     hipDeviceProp_t prop;
     int rc = hip_rc(hipGetDeviceProperties(&prop, devices[0]));
-    if (rc == 0) { c->cu_count = prop.multiProcessorCount; c->clock_mhz = prop.clockRate / 1000; c->device_mem = prop.totalGlobalMem; }
+    if (rc == 0) { c->in.cu_count = prop.multiProcessorCount; c->clock_mhz = prop.clockRate / 1000; c->in.device_mem = prop.totalGlobalMem; }
 
     for (int i = 0; rc == 0 && i < nlocal; ++i) {
         Shard& sh = c->shards[i];
@@ -1421,26 +963,22 @@ int create_common(murbhip_ctx** out, unsigned long n, float soft, float g, int w
         sh.rank = ranks[i];
         partition(n, world, sh.rank, &sh.first, &sh.count);
         if ((rc = hip_rc(hipSetDevice(sh.device)))) break;
-        if ((rc = create_compute_streams(c, sh, 0))) break;
+        int greatest = 0;
+        if ((rc = create_compute_streams(c, sh, 0, &greatest))) break;
         // the exchange stream gets the highest priority: its (few, small) collective kernels must be
         // dispatched as soon as they are ready although the force kernel keeps every CU full
-        {
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            if ((rc = hip_rc(hipStreamCreateWithPriority(&sh.comm, hipStreamNonBlocking, greatest)))) break;
-        }
+        if ((rc = hip_rc(hipStreamCreateWithPriority(&sh.comm, hipStreamNonBlocking, greatest)))) break;
         if ((rc = hip_rc(hipEventCreateWithFlags(&sh.ev_tri, hipEventDisableTiming)))) break;
         if ((rc = hip_rc(hipEventCreateWithFlags(&sh.ev_integrated, hipEventDisableTiming)))) break;
         if ((rc = hip_rc(hipEventCreateWithFlags(&sh.ev_gathered, hipEventDisableTiming)))) break;
-        const size_t rec_bytes = c->slots * sizeof(float4);
-        const size_t vel_bytes = c->slice * sizeof(float4);
-        const size_t acco_bytes = 3 * c->slice * sizeof(float);
-        if ((rc = hip_rc(hipMalloc((void**)&sh.rec[0], rec_bytes)))) break;
-        if ((rc = hip_rc(hipMalloc((void**)&sh.rec[1], rec_bytes)))) break;
-        if ((rc = hip_rc(hipMalloc((void**)&sh.vel, vel_bytes)))) break;
-        if ((rc = hip_rc(hipMalloc((void**)&sh.acc_out, acco_bytes)))) break;
+        const size_t rec_bytes = c->in.slots * sizeof(float4);
+        const size_t vel_bytes = c->in.slice * sizeof(float4);
+        const size_t acco_bytes = 3 * c->in.slice * sizeof(float);
+        if ((rc = shard_alloc(sh, sh.rec[0], rec_bytes))) break;
+        if ((rc = shard_alloc(sh, sh.rec[1], rec_bytes))) break;
+        if ((rc = shard_alloc(sh, sh.vel, vel_bytes))) break;
+        if ((rc = shard_alloc(sh, sh.acc_out, acco_bytes))) break;
         if ((rc = hip_rc(hipMemset(sh.acc_out, 0, acco_bytes)))) break;
-        sh.bytes = 2 * rec_bytes + vel_bytes + acco_bytes;
     }
     // peer access for the copy exchange between distinct devices
     if (rc == 0 && world > 1 && !rank_mode && exchange == 0) {
@@ -1467,24 +1005,39 @@ int create_common(murbhip_ctx** out, unsigned long n, float soft, float g, int w
     return 0;
 }
 
+// The four values of body slot `slot` in packed records (murb_layout.h), as offsets from the returned pointer.
+constexpr size_t kSlotX = 0, kSlotY = 2, kSlotZ = 4 * MURB_TILE_PAIRS, kSlotW = kSlotZ + 2;
+template <class F4>
+auto* slot_values(F4* recs, unsigned long slot)
+{
+    using F = std::conditional_t<std::is_const_v<F4>, const float, float>;
+    return reinterpret_cast<F*>(recs + murb_rec_a(slot >> 1)) + (slot & 1);
+}
+
 // host SoA -> pair records for all slots
-void pack_records(const murbhip_ctx* c, const float* x, const float* y, const float* z, const float* w, float scale_w,
-                  bool w_present, unsigned long first_body, unsigned long nbodies, unsigned long first_slot,
-                  std::vector<float4>& out)
+void pack_records(const float* x, const float* y, const float* z, const float* w, float scale_w, bool w_present, unsigned long first_body,
+                  unsigned long nbodies, unsigned long first_slot, std::vector<float4>& out)
 {
     // writes bodies [first_body, first_body + nbodies) at slots first_slot..; caller zero-fills `out`
     for (unsigned long k = 0; k < nbodies; ++k) {
-        const unsigned long slot = first_slot + k, body = first_body + k;
-        const unsigned long ra = murb_rec_a(slot >> 1);
-        float* A = reinterpret_cast<float*>(&out[ra]);
-        float* B = reinterpret_cast<float*>(&out[ra + MURB_TILE_PAIRS]);
-        const int h = (int)(slot & 1);
-        A[h] = x[body];
-        A[2 + h] = y[body];
-        B[h] = z[body];
-        B[2 + h] = w_present ? scale_w * w[body] : 0.f;
+        const unsigned long body = first_body + k;
+        float* const v = slot_values(out.data(), first_slot + k);
+        v[kSlotX] = x[body];
+        v[kSlotY] = y[body];
+        v[kSlotZ] = z[body];
+        v[kSlotW] = w_present ? scale_w * w[body] : 0.f;
     }
-    (void)c;
+}
+
+// A fresh set of bodies is on the device (murbhip_upload, murbhip_init_bodies).
+void bodies_loaded(murbhip_ctx* c)
+{
+    for (Shard& sh : c->shards) sh.prof_used = 0;
+    c->cur = 0;
+    c->gather_pending = false;
+    c->uploaded = true;
+    c->lf_half = false;
+    invalidate_cached_forces(c);
 }
 
 }  // namespace
@@ -1565,15 +1118,18 @@ int murbhip_schedule_layout(unsigned long n, int world, int rank, int split, int
         return MURBHIP_E_INVALID;
     if (MURB_SYM_BLOCK / split < 16 * waves) return MURBHIP_E_INVALID;
     SymHostLayout L;
-    plan_sym_layout(world, rank, sym_fill(n, world), split, waves, taper_pct & 0xff, (taper_pct & 0x100) != 0,
-                    exchange_mode != 0 || world > 1, 1, tri_first_pct, false, 0, L, 1 << ((taper_pct >> 9) & 3));
+    SymLayoutKey key;
+    key.split = split; key.waves = waves; key.taper = taper_pct & 0xff; key.diag_tri = (taper_pct & 0x100) != 0;
+    key.exchange_mode = exchange_mode != 0 || world > 1;
+    key.overlap = 1; key.tri_first_pct = tri_first_pct; key.tri_div = 1 << ((taper_pct >> 9) & 3);
+    plan_sym_layout(world, rank, sym_fill(n, world), key, L);
     *item_count = L.items.size();
     *row_count = L.table_main.size() + L.table_tri.size();
     if (floats_main) *floats_main = L.floats_main;
     if (floats_tri) *floats_tri = L.floats_tri;
     if (items) {
         if (item_capacity < L.items.size()) return MURBHIP_E_INVALID;
-        const bool ex = exchange_mode != 0 || world > 1;
+        const bool ex = key.exchange_mode;
         for (size_t k = 0; k < L.items.size(); ++k) {
             const MurbSymItem& it = L.items[k];
             long* o = items + 8 * k;
@@ -1674,7 +1230,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part, sh.herm_ctl);
         if (sh.herm_ctl_host) (void)hipHostFree(sh.herm_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
-        free_sym_set(sh.sym_main); free_sym_set(sh.sym_tri);
+        free_sym_set(sh, sh.sym_main); free_sym_set(sh, sh.sym_tri);
     }
     delete c;
     return 0;
@@ -1686,33 +1242,25 @@ int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float
     if (!c || !qx || !qy || !qz || !vx || !vy || !vz || !m) return MURBHIP_E_INVALID;
     RC_TRY(murbhip_sync(c));
     // positions + GM for every slot (replicated), velocities for each local slice
-    std::vector<float4> rec(c->slots, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int r = 0; r < c->world; ++r) {
+    std::vector<float4> rec(c->in.slots, make_float4(0.f, 0.f, 0.f, 0.f));
+    for (int r = 0; r < c->in.world; ++r) {
         unsigned long first, count;
-        partition(c->n, c->world, r, &first, &count);
-        pack_records(c, qx, qy, qz, m, c->g, true, first, count, (unsigned long)r * c->slice, rec);
+        partition(c->in.n, c->in.world, r, &first, &count);
+        pack_records(qx, qy, qz, m, c->g, true, first, count, (unsigned long)r * c->in.slice, rec);
     }
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
-        std::vector<float4> vel(c->slice, make_float4(0.f, 0.f, 0.f, 0.f));
-        pack_records(c, vx, vy, vz, nullptr, 0.f, false, sh.first, sh.count, 0, vel);
+        std::vector<float4> vel(c->in.slice, make_float4(0.f, 0.f, 0.f, 0.f));
+        pack_records(vx, vy, vz, nullptr, 0.f, false, sh.first, sh.count, 0, vel);
         HIP_TRY(hipMemcpy(sh.rec[0], rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(sh.rec[1], rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(sh.vel, vel.data(), vel.size() * sizeof(float4), hipMemcpyHostToDevice));
-        if (!sh.mass) {
-            HIP_TRY(hipMalloc((void**)&sh.mass, c->slice * sizeof(float)));
-            sh.bytes += c->slice * sizeof(float);
-        }
-        std::vector<float> mass(c->slice, 0.f);
+        RC_TRY(shard_alloc(sh, sh.mass, c->in.slice * sizeof(float)));
+        std::vector<float> mass(c->in.slice, 0.f);
         std::copy(m + sh.first, m + sh.first + sh.count, mass.begin());
         HIP_TRY(hipMemcpy(sh.mass, mass.data(), mass.size() * sizeof(float), hipMemcpyHostToDevice));
-        sh.prof_used = 0;
     }
-    c->cur = 0;
-    c->gather_pending = false;
-    c->uploaded = true;
-    c->lf_half = false;
-    invalidate_cached_forces(c);
+    bodies_loaded(c);
     return 0;
 }
 
@@ -1751,14 +1299,13 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
     const bool galaxy = sc == "galaxy";
     if (!galaxy && sc != "random") return MURBHIP_E_INVALID;
     RC_TRY(murbhip_sync(c));
-    const unsigned long draws = galaxy ? 4ul * (c->n - 1) : 7ul * c->n;
+    const unsigned long draws = galaxy ? 4ul * (c->in.n - 1) : 7ul * c->in.n;
     const MurbRandBase base = rand_base_words((unsigned int)seed);
     // glibc picks its FMA build of sincosf on CPUs with FMA and AVX2 (sysdeps/x86_64/fpu/multiarch/ifunc-fma.h)
     const bool fma = c->init_libm_fma >= 0 ? c->init_libm_fma != 0 : (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"));
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
-        if (!sh.mass) { HIP_TRY(hipMalloc((void**)&sh.mass, c->slice * sizeof(float))); sh.bytes += c->slice * sizeof(float); }
-        if (!sh.radius) { HIP_TRY(hipMalloc((void**)&sh.radius, c->slice * sizeof(float))); sh.bytes += c->slice * sizeof(float); }
+        for (float** p : {&sh.mass, &sh.radius}) RC_TRY(shard_alloc(sh, *p, c->in.slice * sizeof(float)));
         unsigned int* d_draws = nullptr;
         HIP_TRY(hipMalloc((void**)&d_draws, std::max(draws, 1ul) * sizeof(unsigned int)));
         int rc = 0;
@@ -1766,16 +1313,16 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
         if (chunks) hipLaunchKernelGGL(murb_rand_fill_kernel, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, sh.compute, base, draws, d_draws);
         rc = hip_rc(hipGetLastError());
         // padding slots: position 0, mass 0, like the records murbhip_upload packs
-        if (!rc) rc = hip_rc(hipMemsetAsync(sh.rec[0], 0, c->slots * sizeof(float4), sh.compute));
-        if (!rc) rc = hip_rc(hipMemsetAsync(sh.rec[1], 0, c->slots * sizeof(float4), sh.compute));
-        if (!rc) rc = hip_rc(hipMemsetAsync(sh.vel, 0, c->slice * sizeof(float4), sh.compute));
-        if (!rc) rc = hip_rc(hipMemsetAsync(sh.mass, 0, c->slice * sizeof(float), sh.compute));
-        if (!rc) rc = hip_rc(hipMemsetAsync(sh.radius, 0, c->slice * sizeof(float), sh.compute));
+        if (!rc) rc = hip_rc(hipMemsetAsync(sh.rec[0], 0, c->in.slots * sizeof(float4), sh.compute));
+        if (!rc) rc = hip_rc(hipMemsetAsync(sh.rec[1], 0, c->in.slots * sizeof(float4), sh.compute));
+        if (!rc) rc = hip_rc(hipMemsetAsync(sh.vel, 0, c->in.slice * sizeof(float4), sh.compute));
+        if (!rc) rc = hip_rc(hipMemsetAsync(sh.mass, 0, c->in.slice * sizeof(float), sh.compute));
+        if (!rc) rc = hip_rc(hipMemsetAsync(sh.radius, 0, c->in.slice * sizeof(float), sh.compute));
         if (!rc) {
             MurbInitArgs a{};
             a.draws = d_draws; a.rec0 = sh.rec[0]; a.rec1 = sh.rec[1]; a.vel = sh.vel; a.mass = sh.mass; a.radius = sh.radius;
-            a.n = c->n; a.world = (unsigned int)c->world; a.rank = (unsigned int)sh.rank; a.slice = (unsigned int)c->slice; a.g = c->g;
-            const dim3 grid((unsigned)((c->n + 255) / 256));
+            a.n = c->in.n; a.world = (unsigned int)c->in.world; a.rank = (unsigned int)sh.rank; a.slice = (unsigned int)c->in.slice; a.g = c->g;
+            const dim3 grid((unsigned)((c->in.n + 255) / 256));
             if (!galaxy) hipLaunchKernelGGL(murb_init_random_kernel, grid, dim3(256), 0, sh.compute, a);
             else if (fma) hipLaunchKernelGGL((murb_init_galaxy_kernel<true>), grid, dim3(256), 0, sh.compute, a);
             else hipLaunchKernelGGL((murb_init_galaxy_kernel<false>), grid, dim3(256), 0, sh.compute, a);
@@ -1784,13 +1331,8 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
         const int rs = hip_rc(hipStreamSynchronize(sh.compute));
         release(d_draws);
         if (rc || rs) return rc ? rc : rs;
-        sh.prof_used = 0;
     }
-    c->cur = 0;
-    c->gather_pending = false;
-    c->uploaded = true;
-    c->lf_half = false;
-    invalidate_cached_forces(c);
+    bodies_loaded(c);
     return 0;
 }
 
@@ -1799,7 +1341,7 @@ int murbhip_download_mass(murbhip_ctx* c, float* m, float* r)
     if (!c || !m) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
     RC_TRY(murbhip_sync(c));
-    std::vector<float> buf(c->slice);
+    std::vector<float> buf(c->in.slice);
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
         HIP_TRY(hipMemcpy(buf.data(), sh.mass, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1847,25 +1389,21 @@ int murbhip_download_state(murbhip_ctx* c, float* qx, float* qy, float* qz, floa
     const bool closing_kick = c->lf_half && (vx || vy || vz);
     if (closing_kick) RC_TRY(enqueue_iteration(c, 0.f, 0));
     RC_TRY(murbhip_sync(c));
-    std::vector<float4> rec(c->slots), vel(c->slice);
-    std::vector<float> acc(closing_kick ? 3 * c->slice : 0);
+    std::vector<float4> rec(c->in.slots), vel(c->in.slice);
+    std::vector<float> acc(closing_kick ? 3 * c->in.slice : 0);
     // positions: any shard holds all of them once its exchange has landed (sync above)
     {
         Shard& sh = c->shards[0];
         HIP_TRY(hipSetDevice(sh.device));
         HIP_TRY(hipMemcpy(rec.data(), sh.rec[c->cur], rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (int r = 0; r < c->world; ++r) {
+        for (int r = 0; r < c->in.world; ++r) {
             unsigned long first, count;
-            partition(c->n, c->world, r, &first, &count);
+            partition(c->in.n, c->in.world, r, &first, &count);
             for (unsigned long k = 0; k < count; ++k) {
-                const unsigned long slot = (unsigned long)r * c->slice + k;
-                const unsigned long ra = murb_rec_a(slot >> 1);
-                const float* A = reinterpret_cast<const float*>(&rec[ra]);
-                const float* B = reinterpret_cast<const float*>(&rec[ra + MURB_TILE_PAIRS]);
-                const int h = (int)(slot & 1);
-                if (qx) qx[first + k] = A[h];
-                if (qy) qy[first + k] = A[2 + h];
-                if (qz) qz[first + k] = B[h];
+                const float* const v = slot_values(rec.data(), (unsigned long)r * c->in.slice + k);
+                if (qx) qx[first + k] = v[kSlotX];
+                if (qy) qy[first + k] = v[kSlotY];
+                if (qz) qz[first + k] = v[kSlotZ];
             }
         }
     }
@@ -1876,15 +1414,12 @@ int murbhip_download_state(murbhip_ctx* c, float* qx, float* qy, float* qz, floa
             if (closing_kick) HIP_TRY(hipMemcpy(acc.data(), sh.acc_out, acc.size() * sizeof(float), hipMemcpyDeviceToHost));
             const float half = 0.5f * c->lf_last_dt;
             for (unsigned long k = 0; k < sh.count; ++k) {
-                const unsigned long ra = murb_rec_a(k >> 1);
-                const float* A = reinterpret_cast<const float*>(&vel[ra]);
-                const float* B = reinterpret_cast<const float*>(&vel[ra + MURB_TILE_PAIRS]);
-                const int h = (int)(k & 1);
-                float ox = A[h], oy = A[2 + h], oz = B[h];
+                const float* const v = slot_values(vel.data(), k);
+                float ox = v[kSlotX], oy = v[kSlotY], oz = v[kSlotZ];
                 if (closing_kick) {
                     ox = half_kick(ox, acc[k], half);
-                    oy = half_kick(oy, acc[c->slice + k], half);
-                    oz = half_kick(oz, acc[2 * c->slice + k], half);
+                    oy = half_kick(oy, acc[c->in.slice + k], half);
+                    oz = half_kick(oz, acc[2 * c->in.slice + k], half);
                 }
                 if (vx) vx[sh.first + k] = ox;
                 if (vy) vy[sh.first + k] = oy;
@@ -1900,13 +1435,13 @@ int murbhip_download_acc(murbhip_ctx* c, float* ax, float* ay, float* az)
     if (!c || !ax || !ay || !az) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
     RC_TRY(murbhip_sync(c));
-    std::vector<float> a(3 * c->slice);
+    std::vector<float> a(3 * c->in.slice);
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
         HIP_TRY(hipMemcpy(a.data(), sh.acc_out, a.size() * sizeof(float), hipMemcpyDeviceToHost));
         std::memcpy(ax + sh.first, a.data(), sh.count * sizeof(float));
-        std::memcpy(ay + sh.first, a.data() + c->slice, sh.count * sizeof(float));
-        std::memcpy(az + sh.first, a.data() + 2 * c->slice, sh.count * sizeof(float));
+        std::memcpy(ay + sh.first, a.data() + c->in.slice, sh.count * sizeof(float));
+        std::memcpy(az + sh.first, a.data() + 2 * c->in.slice, sh.count * sizeof(float));
     }
     return 0;
 }
@@ -1931,12 +1466,12 @@ int murbhip_download_jerk(murbhip_ctx* c, float* jx, float* jy, float* jz)
     if (!c->uploaded || !c->herm_current) return MURBHIP_E_STATE;
     RC_TRY(murbhip_sync(c));
     Shard& sh = c->shards[0];
-    std::vector<float> j(3 * c->slots);
+    std::vector<float> j(3 * c->in.slots);
     HIP_TRY(hipSetDevice(sh.device));
     HIP_TRY(hipMemcpy(j.data(), sh.herm_j0, j.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::memcpy(jx, j.data(), c->n * sizeof(float));
-    std::memcpy(jy, j.data() + c->slots, c->n * sizeof(float));
-    std::memcpy(jz, j.data() + 2 * c->slots, c->n * sizeof(float));
+    std::memcpy(jx, j.data(), c->in.n * sizeof(float));
+    std::memcpy(jy, j.data() + c->in.slots, c->in.n * sizeof(float));
+    std::memcpy(jz, j.data() + 2 * c->in.slots, c->in.n * sizeof(float));
     return 0;
 }
 
@@ -1950,13 +1485,10 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
     if (!c->uploaded || c->integrator != 2) return MURBHIP_E_STATE;
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
     Shard& sh = c->shards[0];
-    if (!sh.herm_ctl) {
-        HIP_TRY(hipMalloc((void**)&sh.herm_ctl, sizeof(MurbEvolveCtl)));
-        sh.bytes += sizeof(MurbEvolveCtl);
-    }
+    RC_TRY(shard_alloc(sh, sh.herm_ctl, sizeof(MurbEvolveCtl)));
     if (!sh.herm_ctl_host) HIP_TRY(hipHostMalloc((void**)&sh.herm_ctl_host, kEvolveHead, hipHostMallocDefault));
-    const int parts = hermite_parts(c);
-    const unsigned pairs = (unsigned)(c->slots / 2);
+    const int parts = hermite_parts(c->in);
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
     const int fresh = c->herm_proposal ? 0 : 1;
     hipLaunchKernelGGL(murb_evolve_begin_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl, duration, eta, dt_min, dt_max,
                        (unsigned long long)max_steps, fresh);
@@ -2034,7 +1566,7 @@ int murbhip_warmup(murbhip_ctx* c, double milliseconds)
     if (!c->uploaded) return MURBHIP_E_STATE;
     // a COUNT fixed by n and the number of ranks, not a clock: in rank mode every evaluation carries collectives, and
     // all ranks must enqueue the same number of them
-    const double per_eval_s = (double)c->n * (double)c->n / (5e12 * (double)c->world) + 10e-6;
+    const double per_eval_s = (double)c->in.n * (double)c->in.n / (5e12 * (double)c->in.world) + 10e-6;
     const int evaluations = (int)std::min(5000.0, std::ceil(milliseconds * 1e-3 / per_eval_s));
     for (int k = 0; k < evaluations; ++k) {
         c->acc_current = false;   // evaluate again, whatever is remembered
@@ -2047,12 +1579,7 @@ int murbhip_warmup(murbhip_ctx* c, double milliseconds)
 
 int murbhip_step(murbhip_ctx* c, float dt)
 {
-    if (!c) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
-    if (c->integrator == 2) return enqueue_hermite(c, dt, 1);
-    RC_TRY(enqueue_iteration(c, dt, 1));
-    if (c->integrator == 1) { c->lf_half = true; c->lf_last_dt = dt; }
-    return 0;
+    return murbhip_steps(c, dt, 1);
 }
 
 int murbhip_steps(murbhip_ctx* c, float dt, int iterations)
@@ -2071,7 +1598,7 @@ int murbhip_integrate_host_acc(murbhip_ctx* c, const float* ax, const float* ay,
 {
     if (!c || !ax || !ay || !az) return MURBHIP_E_INVALID;
     if (!c->uploaded || c->lf_half) return MURBHIP_E_STATE;   // a leapfrog run in flight has half-step velocities
-    std::vector<float4> part(c->slice);
+    std::vector<float4> part(c->in.slice);
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
         if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
@@ -2083,7 +1610,7 @@ int murbhip_integrate_host_acc(murbhip_ctx* c, const float* ax, const float* ay,
         HIP_TRY(hipStreamSynchronize(sh.compute));   // `part` is reused for the next shard
         RC_TRY(enqueue_integrate(c, sh, 1, dt, 1, nullptr, 0));
     }
-    if (c->world > 1) {
+    if (c->in.world > 1) {
         RC_TRY(crew_run(c, [&](Shard& sh) { return shard_exchange(c, sh, c->cur ^ 1, 0); }));
         c->gather_pending = true;
     }
@@ -2115,10 +1642,7 @@ int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VAL
     const MetricsLayout l = metrics_layout(c);
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
-        if (!sh.metrics) {
-            HIP_TRY(hipMalloc((void**)&sh.metrics, l.total * sizeof(double)));
-            sh.bytes += l.total * sizeof(double);
-        }
+        RC_TRY(shard_alloc(sh, sh.metrics, l.total * sizeof(double)));
         if (c->gather_pending) HIP_TRY(hipStreamWaitEvent(sh.compute, sh.ev_gathered, 0));
         MurbMetricsArgs a{};
         a.rec = sh.rec[c->cur];
@@ -2127,9 +1651,9 @@ int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VAL
         a.phi = want_phi ? sh.phi_out : nullptr;
         a.acc = sh.acc_out;
         a.out = sh.metrics;
-        a.i_first_slot = (int)((unsigned long)sh.rank * c->slice);
+        a.i_first_slot = (int)((unsigned long)sh.rank * c->in.slice);
         a.count = (int)sh.count;
-        a.acc_stride = (unsigned int)c->slice;
+        a.acc_stride = (unsigned int)c->in.slice;
         a.half_dt = c->lf_half ? 0.5f * c->lf_last_dt : 0.f;
         a.g_over_soft = phi_has_self ? (double)c->g / std::sqrt((double)c->soft2) : 0.0;
         hipLaunchKernelGGL(murb_metrics_kernel, dim3((unsigned)l.blocks), dim3(256), 0, sh.compute, a);
@@ -2161,7 +1685,7 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
 {
     if (!c || !kinetic || !potential) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
-    const Plan main_plan = make_plan(c);
+    const Plan main_plan = current_plan(c);
     if (main_plan.symmetric && !c->energy_sweep) {
         // Pair-symmetric plan: the potential energy comes out of a FORCE evaluation (murb_kernels_sym.h, PHI = 2: two more
         // packed instructions per 18 sum G m_i G m_j / r of every pair a wave meets, one float per group of 4 i bodies behind
@@ -2174,8 +1698,7 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
         for (Shard& sh : c->shards) {
             if (sh.metrics) continue;
             HIP_TRY(hipSetDevice(sh.device));
-            HIP_TRY(hipMalloc((void**)&sh.metrics, l.total * sizeof(double)));
-            sh.bytes += l.total * sizeof(double);
+            RC_TRY(shard_alloc(sh, sh.metrics, l.total * sizeof(double)));
         }
         if (!(c->acc_current && c->pe_current)) {
             c->acc_current = false;   // forces alone are not enough: evaluate again, this time with the pair potential
@@ -2214,26 +1737,19 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
     Plan p{};
     p.variant = kPotentialKernel;
     {
-        const unsigned long tiles_local = c->slice / MURB_TILE_BODIES, tiles_remote = (c->slots - c->slice) / MURB_TILE_BODIES;
-        p.parts_local = std::max(1, auto_parts(c, 1, c->slice, tiles_local));
-        p.parts_remote = c->world > 1 ? std::max(1, std::min<int>(auto_parts(c, 1, c->slice, tiles_remote), kMaxParts / 2)) : 0;
+        const unsigned long tiles_local = c->in.slice / MURB_TILE_BODIES, tiles_remote = (c->in.slots - c->in.slice) / MURB_TILE_BODIES;
+        p.parts_local = std::max(1, auto_parts(c->in, 1, c->in.slice, tiles_local));
+        p.parts_remote = c->in.world > 1 ? std::max(1, std::min<int>(auto_parts(c->in, 1, c->in.slice, tiles_remote), kMaxParts / 2)) : 0;
     }
     // one shard on the pair-symmetric plan: the sweep is pair-symmetric too (phi_i += G m_j / r, phi_j += G m_i / r:
     // 8 packed + 2 rsq per 4 pair terms instead of 7 + 2 per 2), through the force kernel's partial rows
-    const bool symmetric_sweep = main_plan.symmetric && c->world == 1 && !c->force_exchange;
+    const bool symmetric_sweep = main_plan.symmetric && c->in.world == 1 && !c->force_exchange;
     const bool symmetric_multi = main_plan.symmetric && !symmetric_sweep;   // several ranks: the half-ring form
     for (Shard& sh : c->shards) {
         HIP_TRY(hipSetDevice(sh.device));
-        if (!sh.phi_out) {
-            HIP_TRY(hipMalloc((void**)&sh.phi_out, 3 * c->slice * sizeof(float)));
-            sh.bytes += 3 * c->slice * sizeof(float);
-        }
+        RC_TRY(shard_alloc(sh, sh.phi_out, 3 * c->in.slice * sizeof(float)));
     }
-    if (main_plan.symmetric) {   // a rebuild of existing tables needs everything drained (see sym_schedule_stale)
-        bool stale = false;
-        for (const Shard& sh : c->shards) stale = stale || (sh.sym_items && sym_schedule_stale(c, sh, main_plan));
-        if (stale) RC_TRY(murbhip_sync(c));
-    }
+    RC_TRY(drain_for_rebuild(c, main_plan));
     if (symmetric_multi) {
         RC_TRY(crew_run(c, [&](Shard& sh) { return shard_potential_sym_multi(c, sh, main_plan); }));
         c->reduce_pending = true;
@@ -2249,18 +1765,18 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
                 MurbIntegrateArgs a{};   // no state update: phi_out = the accumulated sums
                 a.rec_in = sh.rec[c->cur]; a.rec_out = sh.rec[c->cur ^ 1]; a.vel = sh.vel;
                 a.acc_out = sh.phi_out;
-                a.acc64 = sh.sym_acc64; a.acc64_stride = (unsigned int)c->slots;
-                a.count = (int)sh.count; a.acc_stride = (unsigned int)c->slice;
-                hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
+                a.acc64 = sh.sym_acc64; a.acc64_stride = (unsigned int)c->in.slots;
+                a.count = (int)sh.count; a.acc_stride = (unsigned int)c->in.slice;
+                hipLaunchKernelGGL(murb_integrate_kernel, dim3((unsigned)((c->in.slice / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
                 RC_TRY(hip_rc(hipGetLastError()));
                 continue;
             }
             RC_TRY(enqueue_sym_launch(c, sh, 0, sh.sym_items_total, false, nullptr, true));
-            RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.phi_out, (unsigned int)c->slots, sh.compute));
+            RC_TRY(enqueue_sym_rowsum(sh.sym_main, sh.phi_out, (unsigned int)c->in.slots, sh.compute));
             continue;
         }
         RC_TRY(enqueue_force(c, sh, p, 0));
-        if (c->world > 1) RC_TRY(enqueue_force(c, sh, p, 1));
+        if (c->in.world > 1) RC_TRY(enqueue_force(c, sh, p, 1));
         RC_TRY(enqueue_integrate(c, sh, p.parts_local + p.parts_remote, 0.f, 0, nullptr, -1, sh.phi_out));
     }
     double sums[MURB_METRIC_VALUES];
@@ -2286,30 +1802,30 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     if (!c || !key) return MURBHIP_E_INVALID;
     const std::string k(key);
     if (k == "solo_shard" || k == "force_exchange") c->acc_current = false;   // what acc_out covers changes
-    if (k == "variant") { if (value < 0 || value > kNumVariants) return MURBHIP_E_INVALID; c->variant = (int)value; }
-    else if (k == "jsplit") { if (value < 0 || value > kMaxParts / 2) return MURBHIP_E_INVALID; c->jsplit = (int)value; }
+    if (k == "variant") { if (value < 0 || value > kNumVariants) return MURBHIP_E_INVALID; c->in.variant = (int)value; }
+    else if (k == "jsplit") { if (value < 0 || value > kMaxParts / 2) return MURBHIP_E_INVALID; c->in.jsplit = (int)value; }
     else if (k == "xcd_order") c->xcd_order = value ? 1 : 0;
     else if (k == "pad_aware") c->pad_aware = value ? 1 : 0;
     else if (k == "energy_sweep") c->energy_sweep = value ? 1 : 0;
-    else if (k == "fuse_integrate") c->fuse_integrate = value ? 1 : 0;
+    else if (k == "fuse_integrate") c->in.fuse_integrate = value ? 1 : 0;
     else if (k == "exchange_p2p") {
         if (value && (c->exchange != 1 || !rccl().Send || !rccl().Recv)) return MURBHIP_E_STATE;   // needs the RCCL exchange and ncclSend/ncclRecv
         RC_TRY(murbhip_sync(c));
         c->exchange_p2p = value ? 1 : 0;
     }
-    else if (k == "tri_div") { if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->tri_div = (int)value; }
+    else if (k == "tri_div") { if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->in.tri_div = (int)value; }
     else if (k == "init_libm_fma") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->init_libm_fma = (int)value; }
     else if (k == "tri_first_pct") { if (value < 0 || value > 100) return MURBHIP_E_INVALID; c->tri_first_pct = (int)value; }
-    else if (k == "taper") { if (value < -1 || value > 100) return MURBHIP_E_INVALID; c->taper = (int)value; }
-    else if (k == "sym_pass_mb") { if (value < 0) return MURBHIP_E_INVALID; c->sym_pass_mb = value; }
-    else if (k == "diag_tri") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->diag_tri = (int)value; }
-    else if (k == "sym_red") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->sym_red = (int)value; }
-    else if (k == "sym_waves") { if (value != 0 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->sym_waves = (int)value; }
+    else if (k == "taper") { if (value < -1 || value > 100) return MURBHIP_E_INVALID; c->in.taper = (int)value; }
+    else if (k == "sym_pass_mb") { if (value < 0) return MURBHIP_E_INVALID; c->in.sym_pass_mb = value; }
+    else if (k == "diag_tri") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->in.diag_tri = (int)value; }
+    else if (k == "sym_red") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->in.sym_red = (int)value; }
+    else if (k == "sym_waves") { if (value != 0 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->in.sym_waves = (int)value; }
     else if (k == "overlap") { if (value < 0 || value > 2) return MURBHIP_E_INVALID; c->overlap = (int)value; }
     else if (k == "integrator") {
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
-        if (value == 2 && (c->world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
+        if (value == 2 && (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
         c->integrator = (int)value;
     }
     else if (k == "evolve_batch") {
@@ -2318,7 +1834,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     }
     else if (k == "solo_shard") c->solo_shard = (int)value;
     else if (k == "cu_reserve") {
-        if (value < 0 || value > c->cu_count / 2) return MURBHIP_E_INVALID;
+        if (value < 0 || value > c->in.cu_count / 2) return MURBHIP_E_INVALID;
         if ((int)value != c->cu_reserve) {
             RC_TRY(murbhip_sync(c));
             for (Shard& sh : c->shards) {
@@ -2357,21 +1873,21 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
 {
     if (!c || !key || !value) return MURBHIP_E_INVALID;
     const std::string k(key);
-    const Plan p = make_plan(c);
-    if (k == "cu_count") *value = c->cu_count;
+    const Plan p = current_plan(c);
+    if (k == "cu_count") *value = c->in.cu_count;
     else if (k == "clock_mhz") *value = c->clock_mhz;
-    else if (k == "n") *value = (double)c->n;
-    else if (k == "slots") *value = (double)c->slots;
-    else if (k == "world") *value = c->world;
+    else if (k == "n") *value = (double)c->in.n;
+    else if (k == "slots") *value = (double)c->in.slots;
+    else if (k == "world") *value = c->in.world;
     else if (k == "cu_reserve") *value = c->cu_reserve;
     else if (k == "sym_passes") *value = c->shards[0].sym_main.passes.empty() ? 0.0 : (double)c->shards[0].sym_main.passes.size();
     else if (k == "rank") *value = c->shards[0].rank;
     else if (k == "jsplit") *value = p.symmetric ? (double)p.split
-                                     : p.persistent ? (double)p.sched[0].nblocks / std::max(resident_blocks(c), 1)
+                                     : p.persistent ? (double)p.sched[0].nblocks / std::max(resident_blocks(c->in), 1)
                                                     : (double)(p.parts_local + p.parts_remote);
     else if (k == "sym_waves") *value = p.symmetric ? p.waves : 0;
     else if (k == "taper") *value = p.symmetric ? p.taper : 0;
-    else if (k == "workgroups") *value = p.persistent ? p.sched[0].nblocks + (c->world > 1 ? p.sched[1].nblocks : 0) : 0;
+    else if (k == "workgroups") *value = p.persistent ? p.sched[0].nblocks + (c->in.world > 1 ? p.sched[1].nblocks : 0) : 0;
     else if (k == "variant") *value = p.variant;
     else if (k == "interactions_per_launch") *value = c->interactions_per_launch;
     else if (k == "device_bytes") { double b = 0; for (Shard& sh : c->shards) b += (double)sh.bytes; *value = b; }

@@ -397,7 +397,8 @@ def test_planner_selftest_under_sanitizers():
     """The host-side planner (csrc/murb_plan.h, murb_schedule.h: item tables and partial-row layouts, no HIP in them)
     compiled with g++ under AddressSanitizer + UBSan and swept over a few thousand plans (sizes 1 … 60 001, 1-8 ranks, splits,
     waves, tapers, triangular diagonals, the exchange pipeline, several passes, finer triangle launches): every index the
-    planner computes is in bounds, no partial-row cell has two writers, tables and passes account for every item."""
+    planner computes is in bounds, no partial-row cell has two writers, tables and passes account for every item.
+    The same binary checks the plan choice (csrc/murb_choose.h) and chains its pair-symmetric choices into those layout checks."""
     exe = os.path.join(ROOT, "tests", "helpers", "_build", "plan_selftest")
     if not os.path.exists(exe):
         subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "helpers"), "_build/plan_selftest"], check=True, timeout=600)

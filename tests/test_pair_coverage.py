@@ -23,7 +23,7 @@ TOL_PE_FUSED = 1e-7      # ... the potential out of the pair-symmetric force eva
 TOL_PE_SWEEP = 5e-7      # ... the separate potential sweep
 BLOCK = 1024             # MURB_SYM_BLOCK: slots per block of the pair-symmetric kernel
 
-# plan defaults (murbhip.hip, murbhip_ctx): every forced configuration starts from these
+# plan defaults (csrc/murb_choose.h, PlanInputs; csrc/murb_ctx.h, murbhip_ctx): every forced configuration starts from these
 DEFAULTS = dict(variant=0, jsplit=0, sym_waves=0, taper=-1, diag_tri=-1, sym_red=-1, pad_aware=1, xcd_order=0, sym_pass_mb=0,
                 overlap=1, tri_div=0, tri_first_pct=50, energy_sweep=0)
 

@@ -1,6 +1,6 @@
 """Lab: which plan of the pair-symmetric kernel is fastest for every block count T = ceil(N / 1024) below the 45 000-body switch, one
 GPU.  Interleaved rounds of the candidates in one process (like tools/ab.py); prints one line per T and, at the end, the table
-csrc/murbhip.hip keeps (kSmallPlanOfBlocks).    python tools/small_plan_table.py [--tmin 10] [--tmax 44]"""
+csrc/murb_choose.h keeps (kSmallPlanOfBlocks).    python tools/small_plan_table.py [--tmin 10] [--tmax 44]"""
 import argparse
 import os
 import sys
