@@ -366,7 +366,8 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
 int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 
 /* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "taper",
- * "workgroups", "interactions_per_launch", "device_bytes", and the timing spans of the steps since "profile" was set (HIP
+ * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
+ * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):
  *   "force_launches", "force_ms_avg", "force_ms_total"      every force launch
  *   "span_<kind>_ms_avg", "span_<kind>_count"               kind = tri1 | rect | tri2 (the three force launches of the exchange

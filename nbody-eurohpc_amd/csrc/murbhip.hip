@@ -1885,6 +1885,7 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "jsplit") *value = p.symmetric ? (double)p.split
                                      : p.persistent ? (double)p.sched[0].nblocks / std::max(resident_blocks(c->in), 1)
                                                     : (double)(p.parts_local + p.parts_remote);
+    else if (k == "hermite_parts") *value = hermite_parts(c->in);   // j chunks of the acceleration + jerk sweep
     else if (k == "sym_waves") *value = p.symmetric ? p.waves : 0;
     else if (k == "taper") *value = p.symmetric ? p.taper : 0;
     else if (k == "workgroups") *value = p.persistent ? p.sched[0].nblocks + (c->in.world > 1 ? p.sched[1].nblocks : 0) : 0;

@@ -102,6 +102,47 @@ def acc_jerk_f32(s, soft, nsplit=128):
     return a, j
 
 
+def acc_jerk_sources(s, src, soft, dtype=np.float64, block=1024):
+    """(a, j, abs_a, abs_j, min_j) of every body due to the bodies `src` alone (a sparse-mass probe, oracle.probe_state:
+    every other mass is 0): a, j (3, n) in `dtype`, every operation of the header's formulas in `dtype`; abs_a, abs_j the
+    per-body sums of the magnitudes of the terms and min_j the smallest jerk term over the sources other than the body
+    itself (+inf without one), those three in fp64 from the terms as computed.  O(n K), blocked over i."""
+    src = np.asarray(src, np.int64)
+    q, v = _stack(s, _Q, dtype), _stack(s, _V, dtype)
+    n = q.shape[1]
+    gm = _gm(s, dtype)[src]
+    qs, vs = q[:, src], v[:, src]
+    soft2 = dtype(soft) * dtype(soft)
+    a, j = np.zeros((3, n), dtype), np.zeros((3, n), dtype)
+    abs_a, abs_j, min_j = np.zeros(n), np.zeros(n), np.full(n, np.inf)
+    if len(src) == 0:
+        return a, j, abs_a, abs_j, min_j
+
+    def norm64(t):
+        t = [np.asarray(x, np.float64) for x in t]
+        return np.sqrt(t[0] ** 2 + t[1] ** 2 + t[2] ** 2)
+
+    for i0 in range(0, n, block):
+        i1 = min(n, i0 + block)
+        d = qs[:, None, :] - q[:, i0:i1, None]                 # (3, b, K)
+        w = vs[:, None, :] - v[:, i0:i1, None]
+        r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + soft2
+        inv = dtype(1.0) / np.sqrt(r2)
+        inv2 = inv * inv
+        sc = (gm[None, :] * inv) * inv2
+        c = dtype(-3.0) * ((d[0] * w[0] + d[1] * w[1] + d[2] * w[2]) * inv2)
+        ta = [sc * d[k] for k in range(3)]
+        tj = [sc * (w[k] + c * d[k]) for k in range(3)]
+        for k in range(3):
+            a[k, i0:i1] = ta[k].sum(1, dtype=dtype)
+            j[k, i0:i1] = tj[k].sum(1, dtype=dtype)
+        na, nj = norm64(ta), norm64(tj)
+        abs_a[i0:i1], abs_j[i0:i1] = na.sum(1), nj.sum(1)
+        other = src[None, :] != np.arange(i0, i1)[:, None]
+        min_j[i0:i1] = np.where(other, nj, np.inf).min(1)
+    return a, j, abs_a, abs_j, min_j
+
+
 def scaled_err(test, truth, abs_sum):
     """Per body |test - truth| / (sum of the magnitudes of the body's terms): oracle.probe_err's convention."""
     t = np.stack([np.asarray(c, np.float64) for c in test])

@@ -212,6 +212,26 @@ static int check_invariants(unsigned long n, int W, int variant)
     return 0;
 }
 
+// (e) j chunks of the Hermite sweep (hermite_parts, read back as info("hermite_parts")): "jsplit" clamped to the layout tiles and
+// to kMaxParts / 2, so that no chunk of murb_force_jerk_sweep's rule [tiles c / parts, tiles (c + 1) / parts) is empty
+static int check_hermite_parts()
+{
+    for (unsigned long n : {1ul, 2ul, 17ul, 513ul, 1025ul, 2049ul, 3035ul, 12001ul, 30000ul, 200000ul})
+        for (int jsplit = 0; jsplit <= kMaxParts / 2; ++jsplit) {
+            PlanInputs in = inputs(n, 1, 256);
+            in.jsplit = jsplit;
+            const long tiles = (long)(in.slots / MURB_TILE_BODIES);
+            const int parts = hermite_parts(in);
+            const Plan p = make_plan(in);   // for EXPECT's message
+            const long most = std::min<long>(tiles, kMaxParts / 2);
+            EXPECT(parts >= 1 && parts <= most && (jsplit == 0 || parts == std::min<long>(jsplit, most)), "hermite_parts %d of %ld tiles", parts, tiles);
+            if (jsplit == 0 && n == 30000) EXPECT(parts > 1, "the default sweep at N = 30 000 is chunked");
+            for (int c = 0; c < parts; ++c)
+                EXPECT(tiles * c / parts < tiles * (c + 1) / parts, "chunk %d of %d is empty", c, parts);
+        }
+    return 0;
+}
+
 int main()
 {
     const unsigned long sizes[] = {1, 250, 1025, 2049, 9001, 30000, 60001};
@@ -241,6 +261,7 @@ int main()
     for (int cu_count : {256, 304, 128})
         if (check_block_sweep(cu_count)) return 1;
     if (check_forced_options()) return 1;
+    if (check_hermite_parts()) return 1;
     for (unsigned long n : {1ul, 250ul, 1025ul, 2049ul, 9001ul, 30000ul, 60001ul, 100000ul, 200000ul, 1000000ul})
         for (int W : {1, 2, 3, 4, 8})
             for (int variant : {0, 1, 2, 7, 8})

@@ -133,7 +133,17 @@ def test_corrector_bit_exact(gpu, O, scheme):
     """The integrator alone (the standard of test_integrator_bit_exact): with the device's own fp32 a0, j0, a1, j1 the
     numpy fp64 restatement of the corrector reproduces q and v bit for bit; the predictor, which only feeds the sweep,
     is pinned through a1 = the device's evaluation at the restated prediction (second context)."""
-    n = 4000
+    corrector_bit_exact(gpu, O, scheme, 4000)
+
+
+@pytest.mark.parametrize("scheme", ["random", "galaxy"])
+@pytest.mark.parametrize("n", [2049, 513])
+def test_corrector_bit_exact_odd_counts(gpu, O, scheme, n):
+    """The same with an odd count: the odd half of the last pair of slots is padding, with whole tiles of padding behind it."""
+    corrector_bit_exact(gpu, O, scheme, n)
+
+
+def corrector_bit_exact(gpu, O, scheme, n):
     s = O.init_bodies(n, scheme)
     with gpu.Simulation(n, soft=SOFT) as sim:
         sim.set_option("integrator", 2)
