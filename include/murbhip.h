@@ -103,7 +103,14 @@ int murbhip_device_count(int* count);
 /* One GPU, whole problem.  Replaces what the reference does at construction of a device
  * implementation: CUDABodies allocation (src/common/core/CUDABodies.cu:12-31), acceleration and
  * GM buffers (SimulationNBodyCUDATileFullDevice.cu:181-199).  `g` is the gravitational constant
- * (SimulationNBodyInterface.hpp:18), `soft` the softening length (squared inside). */
+ * (SimulationNBodyInterface.hpp:18), `soft` the softening length (squared inside).
+ * Units: any consistent system — SI, Henon units (G = M = 1), AU / solar masses / years.  `g` must be a finite number
+ * greater than 0 (MURBHIP_E_INVALID otherwise, from every murbhip_create*: the upload folds G*m into the records and
+ * murbhip_energy divides by it).  All arithmetic of the force path is fp32, so with r^2 = |q_j - q_i|^2 + soft^2 of any pair
+ * (the self pair, r = soft, included), r^2, 1 / r^2, G m / r, the pair factor G m / r^3 and its products with the position and
+ * velocity differences must be normal fp32 numbers; inside [2^-118, 2^120] for all of them every plan is within 2e-6 of an
+ * fp64 evaluation ("Numeric domain").  Results scale exactly, bit for bit, under powers of two of the units.
+ * `soft` == 0 is accepted, but the self pair is then 0 * inf = NaN on every plan, as in the reference. */
 int murbhip_create(murbhip_ctx** out, unsigned long n, float soft, float g, int device);
 
 /* One process driving `ndev` GPUs (bodies block-partitioned over them, positions exchanged every
@@ -294,6 +301,11 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    swaps + DPP), 1 = through LDS (fewer VALU instructions).  -1 (default) = the plan's own choice
  *   "sym_waves"      variant 8: waves per workgroup, 4 or 8; 0 = auto (one GPU up to 27 blocks: 8 or 4 by a measured table per
  *                    block count together with the item length, profiles/r03_small_plan_table.txt; 4 otherwise)
+ *   "sym_wide"       variant 8: the pair factor as (G m / r) (1 / r^2), one packed multiply more per 4 pair terms (+6 %), instead
+ *                    of G m (1 / r^3), whose cube leaves the normal fp32 range for r beyond 2^42 length units.  -1 (default) =
+ *                    chosen by every murbhip_upload: 1 where the diagonal of the bodies' bounding box and the softening, added
+ *                    in quadrature, exceed 2^34 length units (2^8 of headroom for the system to expand) or the softening is
+ *                    below 2^-40, else 0; murbhip_init_bodies keeps 0.  0 / 1 force a form
  *   "pad_aware"      variant 8: 1 (default) = the zero-mass padding slots that fill a slice up to whole blocks of 1024 are
  *                    not walked: the emptier block of a pair goes on the walked (i) side and its items end at its last
  *                    real body; 0 = every block as if full (kept for the A/B: -3 % at N = 30 000, -4 % for a rank of 8
@@ -365,7 +377,7 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  */
 int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 
-/* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "taper",
+/* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "sym_wide" (the form of the pair factor in use: 0 or 1; 0 on a one-sided plan), "taper",
  * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
  * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):

@@ -61,6 +61,17 @@ struct Plan {
     MurbSchedule sched[2];           // [0] own slice (or everything), [1] the rest
 };
 
+// "sym_wide": which form of its pair factor the pair-symmetric kernel takes (csrc/murb_kernels_sym.h, murb_interact_sym).  The
+// fast form cubes 1 / sqrt(r^2 + soft^2) before G m comes in: the cube is a normal fp32 number for 2^-42 <= r <= 2^42.
+// `reach` bounds the largest r of the uploaded bodies (the diagonal of their bounding box and the softening, added in
+// quadrature); the fast form is kept where the system may still grow 2^8-fold, and where the softening — the smallest r, a
+// body against itself — leaves the cube two binades and more below the largest fp32 number.  Anything that is not a number
+// takes the wide form.
+constexpr double kSymFastMaxReach = 0x1p34;
+constexpr double kSymFastMinSoft = 0x1p-40;
+inline bool sym_wide_needed(double reach, double soft) { return !(reach <= kSymFastMaxReach && soft >= kSymFastMinSoft); }
+inline bool sym_wide_chosen(int option, bool needed) { return option < 0 ? needed : option != 0; }   // -1 automatic, 0 / 1 forced
+
 // Workgroups of the persistent kernel that fit on the chip at once.
 inline int resident_blocks(const PlanInputs& in) { return std::max(in.resident_per_cu, 1) * std::max(in.cu_count, 1); }
 

@@ -169,6 +169,8 @@ struct murbhip_ctx {
     float lf_last_dt = 0.f;
     int force_exchange = 0;   // run the exchange even with one rank (self-test of the RCCL binding)
     int init_libm_fma = -1;   // murbhip_init_bodies: which build of glibc's sincosf to reproduce (-1 = what this host's libm picks)
+    int sym_wide = -1;        // pair-symmetric kernel: the range-safe pair factor (G m inv) inv^2; -1 = where the last upload needs it
+    bool sym_wide_needed = false;   // ... what murbhip_upload found (csrc/murb_choose.h, sym_wide_needed); device-made bodies: false
     int energy_sweep = 0;     // murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 (kept for the A/B)
     int exchange_p2p = 0;     // RCCL exchange by grouped ncclSend/ncclRecv instead of ncclReduceScatter / ncclAllGather
     int pad_aware = 1;        // pair-symmetric kernel: 1: padding slots are not walked (murb_schedule.h, sym_orient); 0: every block as if full (A/B)

@@ -99,7 +99,12 @@ __device__ __forceinline__ unsigned murb_ones_if_ge(int p, int threshold)   // a
     return out;
 }
 
-// one i body against a j pair, both directions
+// one i body against a j pair, both directions.  WIDE = 0: the pair factor as G m (inv^2 inv), 16 packed instructions per 4 pair
+// terms — inv^3 alone leaves the normal fp32 range for r > 2^42 = 4.4e12 length units (0 beyond 9e14) and for
+// r^2 + soft^2 below about 2^-85; murbhip_upload picks this form only where the bodies' bounding box and the softening keep 2^8 clear
+// of that (csrc/murb_choose.h, sym_wide_needed).  WIDE = 1: (G m inv) inv^2 as in murb_interact_pk, one packed multiply more
+// (+6 % per evaluation at N = 30 000 ... 200 000), good for every input the one-sided kernels take.
+template <int WIDE = 0>
 __device__ __forceinline__ void murb_interact_sym(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
                                                   const float xi, const float yi, const float zi, const float gi,
                                                   const float soft2, murb_f2& aix, murb_f2& aiy, murb_f2& aiz,
@@ -114,9 +119,16 @@ __device__ __forceinline__ void murb_interact_sym(const murb_f2 xj, const murb_f
     murb_f2 inv;
     inv.x = __builtin_amdgcn_rsqf(r2.x);
     inv.y = __builtin_amdgcn_rsqf(r2.y);
-    const murb_f2 inv3 = (inv * inv) * inv;
-    const murb_f2 fi = gj * inv3;          // pull of j on i
-    const murb_f2 fj = inv3 * (-gi);       // pull of i on j (opposite direction)
+    murb_f2 fi, fj;   // pull of j on i, pull of i on j (opposite direction)
+    if constexpr (WIDE) {
+        const murb_f2 inv2 = inv * inv;
+        fi = (gj * inv) * inv2;
+        fj = ((murb_f2)(-gi) * inv) * inv2;
+    } else {
+        const murb_f2 inv3 = (inv * inv) * inv;
+        fi = gj * inv3;
+        fj = inv3 * (-gi);
+    }
     aix = __builtin_elementwise_fma(fi, dx, aix);
     aiy = __builtin_elementwise_fma(fi, dy, aiy);
     aiz = __builtin_elementwise_fma(fi, dz, aiz);
@@ -132,6 +144,7 @@ __device__ __forceinline__ void murb_interact_sym(const murb_f2 xj, const murb_f
 // from both sides and every body itself, and that self term — (G m)^2 / soft, for the galaxy's central body 10^4 times
 // everything around it — would swallow the low bits of its neighbours in an fp32 chain; murb_sym_pe_diag_kernel sums the
 // diagonal blocks' pairs separately, in fp64 and without the self terms.
+template <int WIDE = 0>
 __device__ __forceinline__ void murb_interact_sym_pe(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
                                                      const float xi, const float yi, const float zi, const float gi, const float gi_pe,
                                                      const float soft2, murb_f2& aix, murb_f2& aiy, murb_f2& aiz,
@@ -146,10 +159,18 @@ __device__ __forceinline__ void murb_interact_sym_pe(const murb_f2 xj, const mur
     murb_f2 inv;
     inv.x = __builtin_amdgcn_rsqf(r2.x);
     inv.y = __builtin_amdgcn_rsqf(r2.y);
-    const murb_f2 inv3 = (inv * inv) * inv;
-    const murb_f2 fi = gj * inv3;          // pull of j on i
-    const murb_f2 fj = inv3 * (-gi);       // pull of i on j (opposite direction)
-    const murb_f2 gg = gj * inv;           // G m_j / r
+    murb_f2 fi, fj, gg;   // gg = G m_j / r
+    if constexpr (WIDE) {
+        const murb_f2 inv2 = inv * inv;
+        gg = gj * inv;
+        fi = gg * inv2;
+        fj = ((murb_f2)(-gi) * inv) * inv2;
+    } else {
+        const murb_f2 inv3 = (inv * inv) * inv;
+        fi = gj * inv3;
+        fj = inv3 * (-gi);
+        gg = gj * inv;
+    }
     pe = __builtin_elementwise_fma(gg, (murb_f2)(gi_pe), pe);
     aix = __builtin_elementwise_fma(fi, dx, aix);
     aiy = __builtin_elementwise_fma(fi, dy, aiy);
@@ -184,7 +205,7 @@ __device__ __forceinline__ void murb_interact_sym_phi(const murb_f2 xj, const mu
 // steps [p_first, p_sym): steps before p_first are skipped (those pairs belong to the items of the earlier i ranges,
 // which apply both sides), steps in [p_first, p_sym) keep the i side only (their j bodies include the i bodies
 // themselves), steps from p_sym on apply both sides.
-template <int WAVES, int ILOAD, int PHI, int RED, int DYN>
+template <int WAVES, int ILOAD, int PHI, int RED, int DYN, int WIDE>
 __device__ __forceinline__ void murb_sym_walk(const MurbSymArgs& a, const float4* tileA, const float4* tileB, float* stage,
                                               const int lane, const int wave, const int groups_per_wave,
                                               const unsigned int i_block_slot, const unsigned long out_off, const int out_stride,
@@ -276,10 +297,10 @@ __device__ __forceinline__ void murb_sym_walk(const MurbSymArgs& a, const float4
                     if constexpr (PHI == 1)
                         murb_interact_sym_phi(xj, yj, zj, gj, xi[r], yi[r], zi[r], gie, soft2, aix[r], ajx[p]);
                     else if constexpr (PHI == 2)
-                        murb_interact_sym_pe(xj, yj, zj, gj, xi[r], yi[r], zi[r], gie, gi[r], soft2, aix[r], aiy[r], aiz[r], ajx[p],
+                        murb_interact_sym_pe<WIDE>(xj, yj, zj, gj, xi[r], yi[r], zi[r], gie, gi[r], soft2, aix[r], aiy[r], aiz[r], ajx[p],
                                              ajy[p], ajz[p], pe);
                     else
-                        murb_interact_sym(xj, yj, zj, gj, xi[r], yi[r], zi[r], gie, soft2, aix[r], aiy[r], aiz[r], ajx[p], ajy[p],
+                        murb_interact_sym<WIDE>(xj, yj, zj, gj, xi[r], yi[r], zi[r], gie, soft2, aix[r], aiy[r], aiz[r], ajx[p], ajy[p],
                                           ajz[p]);
                 }
             }
@@ -327,7 +348,8 @@ __device__ __forceinline__ void murb_sym_walk(const MurbSymArgs& a, const float4
 // 22 VALU instructions per group.
 // (Taking the team sums one group later, in the middle of the next group's sweep, to cover the LDS round trip, measured
 // 2 % SLOWER than RED = 1 at N = 200 000 and was dropped.)
-template <int MINW, int WAVES = 4, int ILOAD = 0, int PHI = 0, int RED = 0>
+// WIDE: the form of the pair factor (murb_interact_sym), option "sym_wide".
+template <int MINW, int WAVES = 4, int ILOAD = 0, int PHI = 0, int RED = 0, int WIDE = 0>
 __global__ __launch_bounds__(64 * WAVES, MINW) void murb_force_sym_kernel(const MurbSymArgs a)
 {
     constexpr int THREADS = 64 * WAVES;
@@ -385,10 +407,10 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void murb_force_sym_kernel(const 
     // RED = 1: this wave's staging area (12 rows of 64 floats at a stride of 80)
     float* const stage = reinterpret_cast<float*>(&scratch[0][0][0]) + wave * ((PHI == 2 ? 13 : 12) * 80);
     if (triangular)
-        murb_sym_walk<WAVES, ILOAD, PHI, RED, 1>(a, tileA, tileB, stage, lane, wave, groups_per_wave, (unsigned int)i_item_slot, out_off,
+        murb_sym_walk<WAVES, ILOAD, PHI, RED, 1, WIDE>(a, tileA, tileB, stage, lane, wave, groups_per_wave, (unsigned int)i_item_slot, out_off,
                                                  out_stride, 0.f, p_first, p_sym, ajx, ajy, ajz);
     else
-        murb_sym_walk<WAVES, ILOAD, PHI, RED, 0>(a, tileA, tileB, stage, lane, wave, groups_per_wave, (unsigned int)i_item_slot, out_off,
+        murb_sym_walk<WAVES, ILOAD, PHI, RED, 0, WIDE>(a, tileA, tileB, stage, lane, wave, groups_per_wave, (unsigned int)i_item_slot, out_off,
                                                  out_stride, (i_item_slot / MURB_SYM_BLOCK == J) ? 0.f : 1.f, 0, 0, ajx, ajy, ajz);
 
     // j side: fold the waves pairwise in a fixed order (WAVES = 4: 3+2 -> 1+0 -> 0), wave 0 writes the item's j row

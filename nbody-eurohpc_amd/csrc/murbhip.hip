@@ -434,14 +434,15 @@ int build_sym_schedule(murbhip_ctx* c, Shard& sh, const Plan& p)
 }
 
 // form: 0 forces, i-side sums in registers; 1 potential sweep; 2 forces + pair potential; 3 forces, i-side sums through LDS
-template <int WAVES>
+// WIDE: the pair factor as (G m inv) inv^2 ("sym_wide"; the potential sweep has no cube and one form)
+template <int WAVES, int WIDE>
 void launch_sym_t(int form, int count, hipStream_t stream, const MurbSymArgs& sa)
 {
     const dim3 grid((unsigned)count), block(64 * WAVES);
     if (form == 1) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 1>), grid, block, 0, stream, sa);
-    else if (form == 2) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 2, 1>), grid, block, 0, stream, sa);
-    else if (form == 3) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 0, 1>), grid, block, 0, stream, sa);
-    else hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1>), grid, block, 0, stream, sa);
+    else if (form == 2) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 2, 1, WIDE>), grid, block, 0, stream, sa);
+    else if (form == 3) hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 0, 1, WIDE>), grid, block, 0, stream, sa);
+    else hipLaunchKernelGGL((murb_force_sym_kernel<4, WAVES, 1, 0, 0, WIDE>), grid, block, 0, stream, sa);
 }
 
 int enqueue_sym_launch(murbhip_ctx* c, Shard& sh, int first, int count, bool own_triangle_rows, hipStream_t stream,
@@ -464,8 +465,9 @@ int enqueue_sym_launch(murbhip_ctx* c, Shard& sh, int first, int count, bool own
     const int sp = timed ? span_begin(c, sh, kind, stream, &rc_span) : -1;
     RC_TRY(rc_span);
     const int form = potential ? 1 : (with_pe ? 2 : (sh.sym_red == 1 ? 3 : 0));
-    if (sh.key.waves == 8) launch_sym_t<8>(form, count, stream, sa);
-    else launch_sym_t<4>(form, count, stream, sa);
+    const bool wide = sym_wide_chosen(c->sym_wide, c->sym_wide_needed);
+    if (sh.key.waves == 8) { if (wide) launch_sym_t<8, 1>(form, count, stream, sa); else launch_sym_t<8, 0>(form, count, stream, sa); }
+    else { if (wide) launch_sym_t<4, 1>(form, count, stream, sa); else launch_sym_t<4, 0>(form, count, stream, sa); }
     RC_TRY(hip_rc(hipGetLastError()));
     RC_TRY(span_end(sh, sp, stream));
     return 0;
@@ -935,6 +937,7 @@ int create_common(murbhip_ctx** out, unsigned long n, float soft, float g, int w
                   const int* ranks, int exchange, bool rank_mode)
 {
     if (!out || n == 0 || world < 1 || world > MURB_SYM_MAX_RANKS || nlocal < 1 || !(soft == soft)) return MURBHIP_E_INVALID;
+    if (!(g > 0.f) || !std::isfinite(g)) return MURBHIP_E_INVALID;   // murbhip_energy divides by it; G*m is folded into the records
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MURBHIP_E_NO_DEVICE;
     for (int i = 0; i < nlocal; ++i)
@@ -1241,6 +1244,21 @@ int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float
 {
     if (!c || !qx || !qy || !qz || !vx || !vy || !vz || !m) return MURBHIP_E_INVALID;
     RC_TRY(murbhip_sync(c));
+    {   // how far apart two bodies can be: decides the form of the pair-symmetric kernel's pair factor ("sym_wide")
+        double reach2 = (double)c->soft2;
+        for (const float* q : {qx, qy, qz}) {
+            float lo = q[0], hi = q[0];
+            bool finite = true;
+            for (unsigned long i = 0; i < c->in.n; ++i) {
+                lo = std::min(lo, q[i]);
+                hi = std::max(hi, q[i]);
+                finite = finite && std::isfinite(q[i]);
+            }
+            const double extent = finite ? (double)hi - (double)lo : (double)INFINITY;
+            reach2 += extent * extent;
+        }
+        c->sym_wide_needed = sym_wide_needed(std::sqrt(reach2), std::sqrt((double)c->soft2));
+    }
     // positions + GM for every slot (replicated), velocities for each local slice
     std::vector<float4> rec(c->in.slots, make_float4(0.f, 0.f, 0.f, 0.f));
     for (int r = 0; r < c->in.world; ++r) {
@@ -1332,6 +1350,7 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
         release(d_draws);
         if (rc || rs) return rc ? rc : rs;
     }
+    c->sym_wide_needed = false;   // the reference's schemes span 1e9 m: the fast form of the pair-symmetric kernel ("sym_wide")
     bodies_loaded(c);
     return 0;
 }
@@ -1807,6 +1826,11 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "xcd_order") c->xcd_order = value ? 1 : 0;
     else if (k == "pad_aware") c->pad_aware = value ? 1 : 0;
     else if (k == "energy_sweep") c->energy_sweep = value ? 1 : 0;
+    else if (k == "sym_wide") {
+        if (value < -1 || value > 1) return MURBHIP_E_INVALID;
+        if ((int)value != c->sym_wide) { c->acc_current = false; c->pe_current = false; }   // the other form rounds differently
+        c->sym_wide = (int)value;
+    }
     else if (k == "fuse_integrate") c->in.fuse_integrate = value ? 1 : 0;
     else if (k == "exchange_p2p") {
         if (value && (c->exchange != 1 || !rccl().Send || !rccl().Recv)) return MURBHIP_E_STATE;   // needs the RCCL exchange and ncclSend/ncclRecv
@@ -1887,6 +1911,7 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
                                                     : (double)(p.parts_local + p.parts_remote);
     else if (k == "hermite_parts") *value = hermite_parts(c->in);   // j chunks of the acceleration + jerk sweep
     else if (k == "sym_waves") *value = p.symmetric ? p.waves : 0;
+    else if (k == "sym_wide") *value = p.symmetric && sym_wide_chosen(c->sym_wide, c->sym_wide_needed) ? 1 : 0;
     else if (k == "taper") *value = p.symmetric ? p.taper : 0;
     else if (k == "workgroups") *value = p.persistent ? p.sched[0].nblocks + (c->in.world > 1 ? p.sched[1].nblocks : 0) : 0;
     else if (k == "variant") *value = p.variant;

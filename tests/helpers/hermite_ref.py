@@ -176,10 +176,11 @@ def correct(q, v, a0, j0, a1, j1, dt, state32=True):
     return q1, v1
 
 
-def hermite_f64(s, steps, soft, dt, state32=False):
+def hermite_f64(s, steps, soft, dt, state32=False, gm=None):
     """`steps` Hermite steps from the state dict s (not modified).  Returns a state dict (fp32 arrays with state32,
-    fp64 otherwise) with the masses of s."""
-    q, v, gm = _stack(s, _Q), _stack(s, _V), _gm(s)
+    fp64 otherwise) with the masses of s.  gm: the bodies' G m in another unit system (default: G of the reference times
+    the masses of s)."""
+    q, v, gm = _stack(s, _Q), _stack(s, _V), _gm(s) if gm is None else np.asarray(gm, np.float64)
     rnd = _r32 if state32 else (lambda x: x)
     a0, j0, _ = _evaluate(q, v, gm, soft)
     a0, j0 = rnd(a0), rnd(j0)

@@ -7,6 +7,8 @@
 // choice is chained through sym_layout_key into the same layout checks.
 //   plan_selftest        prints "ok <plans checked>" and exits 0
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <set>
@@ -232,6 +234,30 @@ static int check_hermite_parts()
     return 0;
 }
 
+// (f) "sym_wide": which form of the pair factor an upload selects (sym_wide_needed) and how the option overrides it
+static int check_sym_wide()
+{
+    struct Case { double reach, soft; bool wide; const char* what; };
+    const Case cases[] = {
+        {6.9e8, 2e8, false, "the galaxy scheme"}, {1.95e9, 2e8, false, "the random scheme"}, {2e11, 1e3, true, "1e11 m binaries"},
+        {12.0, 1e-3, false, "Henon units"}, {2.4e5, 10.0, false, "AU, a cluster of 2e4 AU"}, {1.2e14, 1e9, true, "SI at 1e13 m"},
+        {1.2e16, 1e11, true, "SI at 1e15 m"}, {3.7e17, 1e13, true, "SI at 1 pc"}, {1.1e-8, 0x1p-40, false, "G = 1 at 2^-30"},
+        {0x1p34, 1.0, false, "the last reach of the fast form"}, {0x1.000002p34, 1.0, true, "one step beyond it"},
+        {1.0, 0x1p-40, false, "the smallest softening of the fast form"}, {1.0, 0x1.fffffep-41, true, "one step below it"},
+        {1.0, 0.0, true, "no softening"}, {HUGE_VAL, 1.0, true, "an infinite extent"}, {std::nan(""), 1.0, true, "a NaN extent"},
+        {1.0, std::nan(""), true, "a NaN softening"},
+    };
+    for (const Case& c : cases)
+        if (sym_wide_needed(c.reach, c.soft) != c.wide) FAIL("sym_wide_needed(%g, %g) is not %d: %s", c.reach, c.soft, (int)c.wide, c.what);
+    // the fast form's cube of 1 / r stays a normal fp32 number with 2^8 to spare at the far end and 2^7 below the largest at the near one
+    if (std::pow(kSymFastMaxReach * 256.0, -3.0) < (double)FLT_MIN) FAIL("the far threshold leaves less than 2^8 of headroom");
+    if (std::pow(kSymFastMinSoft, -3.0) * 128.0 > (double)FLT_MAX) FAIL("the near threshold lets the cube of 1 / soft overflow");
+    for (int needed = 0; needed <= 1; ++needed)
+        if (sym_wide_chosen(-1, needed) != (needed != 0) || sym_wide_chosen(0, needed) || !sym_wide_chosen(1, needed))
+            FAIL("sym_wide_chosen: -1 follows the upload, 0 and 1 are forced");
+    return 0;
+}
+
 int main()
 {
     const unsigned long sizes[] = {1, 250, 1025, 2049, 9001, 30000, 60001};
@@ -262,6 +288,7 @@ int main()
         if (check_block_sweep(cu_count)) return 1;
     if (check_forced_options()) return 1;
     if (check_hermite_parts()) return 1;
+    if (check_sym_wide()) return 1;
     for (unsigned long n : {1ul, 250ul, 1025ul, 2049ul, 9001ul, 30000ul, 60001ul, 100000ul, 200000ul, 1000000ul})
         for (int W : {1, 2, 3, 4, 8})
             for (int variant : {0, 1, 2, 7, 8})
