@@ -222,6 +222,55 @@ int murbhip_evolve(murbhip_ctx* ctx, double duration, double eta, double eta_sta
  * work. */
 int murbhip_evolve_dts(murbhip_ctx* ctx, float* dts, unsigned long capacity, unsigned long* count);
 
+/* Advance the bodies by `blocks` blocks of dt_max seconds with Hermite steps ("integrator" 2) of INDIVIDUAL size: every body
+ * takes steps of its own, dt_i = dt_max 2^-k_i with a level k_i in [0, kmax] (hierarchical "block" steps, Makino 1991), so that
+ * one tight pair no longer sets the step of every body.
+ *   Time.  A block is cut into T = 2^kmax ticks.  Body i holds its level k_i and its own time t_i in ticks, an unsigned 32-bit
+ *   number in [0, T); its step is T >> k_i ticks.  All bookkeeping is in integers, no floating-point time is accumulated:
+ *   seconds are only ever formed as (double)ticks * ((double)dt_max * 2^-kmax), which is exact for kmax <= 20, and
+ *   dt_i = dt_max 2^-k_i is exact in fp32.
+ *   One block step:
+ *    1. t_next = min_i (t_i + (T >> k_i)); the active set is every real body (massless ones included) that attains it.
+ *    2. EVERY body is predicted to t_next with its own dt = (t_next - t_i) ticks in seconds, the exact fp64 value, by the
+ *       predictor of a Hermite step (the fp64 coefficients dt, dt*dt*0.5, dt*dt*dt/6 formed from that dt; one rounding to
+ *       fp32 per stored value).  An inactive body's q, v, a0, j0, t_i, k_i are not touched by the step, bit for bit.
+ *    3. (a1, j1) of the active bodies only, at the predicted state of all n bodies (murbhip_compute_acc_jerk's arithmetic).
+ *    4. Each active body is corrected from its own (q, v, a0, j0) at t_i with its dt_i, by the corrector of a Hermite step,
+ *       in place; then (a0, j0) <- (a1, j1) and t_i <- t_next (0 when t_next == T).
+ *    5. Its new level: req = murbhip_evolve's dt_i from (a0, j0, a1, j1, dt_i, eta), rounded to fp32 (+inf where that is not a
+ *       finite positive number); k_req = the smallest k in [0, kmax] with dt_max 2^-k <= req (+inf gives 0); if no k qualifies,
+ *       k_req = kmax and the step counts as CLAMPED (the cap is too coarse for that body: look at out8[5]).  If k_req > k_i:
+ *       k_i <- k_req (several halvings at once are allowed).  Else if k_req < k_i and t_next is a multiple of 2 (T >> k_i):
+ *       k_i <- k_i - 1 (one doubling, and only where the coarser grid has a point).  Else k_i stays.
+ *    6. At t_next == T every body is active (all steps divide T): the block ends with all bodies synchronised.
+ *   The call ends after `blocks` such boundaries, or after max_steps block steps, possibly inside a block.
+ *   Starting levels.  Those a previous call left are kept when that call ended synchronised, dt_max and kmax are the same and
+ *   nothing changed the bodies in between; otherwise k_i = k_req(eta_start |a0_i| / |j0_i|) (murbhip_evolve's starting rule per
+ *   body, fp32) from the remembered evaluation or a fresh one.  A call that finds the context inside a block continues that
+ *   block with the same dt_max and kmax (MURBHIP_E_STATE for others); `blocks` counts the boundaries still to reach.
+ *   out8 = { model time advanced in seconds, block steps, body-steps (sum of the active sets' sizes: what the N^2 sweep is
+ *            paid for), smallest dt_i used, largest, clamped steps, largest active set, 1 if synchronised at return }.
+ * The active set, its size and the end of the run live on the device; the host enqueues batches of at most 64 block steps and
+ * looks at the control block once per batch ("evolve_batch" fixes the batch length here too).  The order of the active list
+ * is unspecified and no result depends on it: results are bit-reproducible from run to run.
+ * MURBHIP_E_STATE unless "integrator" is 2 and the context has one shard; MURBHIP_E_INVALID for a dt_max that is not finite or
+ * <= 0, blocks == 0, eta <= 0, eta_start <= 0, kmax outside 0 ... 20, dt_max 2^-kmax not a normal fp32 number, max_steps == 0.
+ * While a block is open (a max_steps stop), murbhip_step(s), murbhip_evolve, murbhip_compute_acc, murbhip_compute_acc_jerk,
+ * murbhip_energy, murbhip_moments and murbhip_warmup return MURBHIP_E_STATE; murbhip_upload, murbhip_init_bodies and
+ * murbhip_integrate_host_acc close it and drop the levels; murbhip_download_state / _acc / _jerk return every body at its own
+ * time (a test hook).  After a synchronised return the remembered (a0, j0) serve murbhip_step, murbhip_evolve and
+ * murbhip_download_acc / _jerk exactly as a Hermite step's do. */
+int murbhip_evolve_block(murbhip_ctx* ctx, float dt_max, unsigned long blocks, double eta, double eta_start, int kmax,
+                         unsigned long max_steps, double* out8);
+
+/* Test hooks of murbhip_evolve_block, like murbhip_download_jerk.  murbhip_block_state: the bodies' own times (ticks) and levels,
+ * n entries each, either pointer may be NULL; waits for enqueued work; MURBHIP_E_STATE before the first murbhip_evolve_block or
+ * murbhip_block_set_levels.  murbhip_block_set_levels: the next murbhip_evolve_block with that kmax starts from these levels
+ * (all bodies at tick 0) instead of the starting rule; any change of the bodies drops them.  MURBHIP_E_INVALID for a level
+ * outside [0, kmax], MURBHIP_E_STATE while a block is open or unless "integrator" is 2 with one shard. */
+int murbhip_block_state(murbhip_ctx* ctx, unsigned int* ticks, int* levels);
+int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
+
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
  * §4.5) — as long as the reference's whole 200-iteration run at N = 30 000.  Construction is outside the reference's timing
@@ -340,11 +389,16 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    velocities of ALL bodies, which sharded and rank-mode contexts keep for their own slice alone
  *                    (they exchange positions, never velocities), so on a context of several shards or ranks, or
  *                    with "force_exchange" set, the value 2 is refused with MURBHIP_E_STATE (and "force_exchange"
- *                    is refused while the value is 2).  murbhip_evolve drives the same steps with sizes the device chooses
+ *                    is refused while the value is 2).  murbhip_evolve drives the same steps with sizes the device chooses,
+ *                    murbhip_evolve_block gives every body a step of its own
  *   "evolve_batch"   murbhip_evolve: steps enqueued between two looks at the device's control block.  0 (default) = as
  *                    many as the remaining time takes at the step last seen, 64 at the most; 1..64 = exactly that many
  *                    (timing aid: a batch longer than the run needs ends in launches that find the done flag set and do
  *                    nothing, which tools/hermite_adaptive_rate.py times).  The results do not depend on it
+ *   "block_units"    murbhip_evolve_block: U, the number of (group of 16 active bodies, j chunk) work units the active sweep
+ *                    is cut into at least: chunks = ceil(U / groups) clamped to [1, layout tiles].  0 (default) = one per
+ *                    workgroup the chip holds at once (5 per CU; info "block_units" / "block_grid"); up to 65 536.  The
+ *                    results depend on it only through the chunk cut of the fp32 row sums
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real
@@ -378,6 +432,8 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
 int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 
 /* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "sym_wide" (the form of the pair factor in use: 0 or 1; 0 on a one-sided plan), "taper",
+ * "block_units", "block_grid" (work units and workgroups of murbhip_evolve_block's active sweep), "block_steps", "block_body_steps",
+ * "block_clamped", "block_max_active" (the last murbhip_evolve_block call's counts),
  * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
  * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):

@@ -90,6 +90,16 @@ struct Shard {
     int herm_rows = 0;
     MurbEvolveCtl* herm_ctl = nullptr;        // murbhip_evolve's control block (device), allocated on first use
     MurbEvolveCtl* herm_ctl_host = nullptr;   // pinned copy of its head (everything in front of the ring)
+    // individual block time steps (murbhip_evolve_block), allocated on first use (ensure_block)
+    MurbBlockCtl* blk_ctl = nullptr;          // control block (device)
+    MurbBlockCtl* blk_ctl_host = nullptr;     // pinned copy
+    unsigned int* blk_ticks = nullptr;        // per body: its own time inside the block, in ticks
+    int* blk_levels = nullptr;                // per body: its level
+    int* blk_list = nullptr;                  // the active bodies of the step in flight
+    float4* blk_rec = nullptr;                // their predicted positions and velocities by list index, pair layout
+    float4* blk_vel = nullptr;
+    float4* blk_part = nullptr;               // partial rows of the active sweep: blk_rows entries of accelerations, then of jerks
+    size_t blk_rows = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -157,6 +167,15 @@ struct murbhip_ctx {
     bool herm_in_acc_out = false;   // ... and acc_out still holds its accelerations (no force evaluation has run since)
     bool herm_proposal = false;     // ... and the control block's `raw` is the step murbhip_evolve's criterion proposes from it
     unsigned long evolve_steps = 0; // steps of the last murbhip_evolve (what murbhip_evolve_dts reads from the ring)
+    // individual block time steps (murbhip_evolve_block)
+    int block_units = 0;            // "block_units": (group, chunk) units the active sweep is cut into at least; 0 = default
+    bool blk_open = false;          // a call ended inside a block (max_steps): bodies sit at their own times
+    int blk_have_levels = 0;        // 1: the device's levels were left by a call that ended synchronised, for (blk_dt_max, blk_kmax);
+                                    // 2: murbhip_block_set_levels put them there, for blk_kmax
+    float blk_dt_max = 0.f;
+    int blk_kmax = 0;
+    double blk_steps_per_block = 0; // block steps a block took in the last call (sizes the first batch of the next)
+    double blk_info[4] = {0, 0, 0, 0};   // last call: block steps, body-steps, clamped steps, largest active set
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

@@ -733,6 +733,8 @@ void invalidate_cached_forces(murbhip_ctx* c)
     c->pe_current = false;
     c->herm_current = false;
     c->herm_proposal = false;
+    c->blk_open = false;        // murbhip_evolve_block: an open block is closed, the bodies' levels are dropped
+    c->blk_have_levels = 0;
     ++c->state_serial;
 }
 
@@ -907,6 +909,74 @@ int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
     RC_TRY(hip_rc(hipGetLastError()));
     c->cur ^= 1;
     return 0;
+}
+
+// ---- individual block time steps (murbhip_evolve_block; control block and kernels: murb_kernels_hermite.h, third part) -------
+constexpr int kBlockBatch = 64;        // block steps enqueued between two looks at the control block
+constexpr int kBlockMaxUnits = 65536;  // "block_units"
+
+// Workgroups of the active sweep: what the chip holds at once (32 KiB of LDS each: 5 per CU).  The default "block_units"
+// is the same number, one unit per resident workgroup.
+inline int block_grid(const murbhip_ctx* c) { return 5 * std::max(c->in.cu_count, 1); }
+inline int block_units(const murbhip_ctx* c) { return c->block_units > 0 ? c->block_units : block_grid(c); }
+
+int ensure_block(murbhip_ctx* c, Shard& sh)
+{
+    const size_t slots = c->in.slots;
+    RC_TRY(shard_alloc(sh, sh.blk_ctl, sizeof(MurbBlockCtl), sh.compute));
+    if (!sh.blk_ctl_host) HIP_TRY(hipHostMalloc((void**)&sh.blk_ctl_host, sizeof(MurbBlockCtl), hipHostMallocDefault));
+    RC_TRY(shard_alloc(sh, sh.blk_ticks, slots * sizeof(unsigned int), sh.compute));
+    RC_TRY(shard_alloc(sh, sh.blk_levels, slots * sizeof(int), sh.compute));
+    RC_TRY(shard_alloc(sh, sh.blk_list, slots * sizeof(int), sh.compute));
+    for (float4** p : {&sh.blk_rec, &sh.blk_vel}) RC_TRY(shard_alloc(sh, *p, slots * sizeof(float4), sh.compute));
+    // groups * chunks <= max(groups, units + groups - 1) with chunks = ceil(units / groups) clamped, and 16 * groups <= slots
+    const size_t rows = slots + (size_t)MURB_BLOCK_GROUP * (size_t)block_units(c);
+    if (rows > sh.blk_rows) {   // "block_units" grew: no step is in flight between two calls, but the stream may still run
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        shard_free(sh, sh.blk_part, 2 * sh.blk_rows * sizeof(float4));
+        sh.blk_rows = 0;
+        RC_TRY(shard_alloc(sh, sh.blk_part, 2 * rows * sizeof(float4), sh.compute));
+        sh.blk_rows = rows;
+    }
+    return 0;
+}
+
+MurbBlockArgs block_args(const murbhip_ctx* c, const Shard& sh)
+{
+    MurbBlockArgs a{};
+    a.rec = sh.rec[c->cur];
+    a.vel = sh.vel;
+    a.rec_pred = sh.herm_rec;
+    a.vel_pred = sh.herm_vel;
+    a.rec_act = sh.blk_rec;
+    a.vel_act = sh.blk_vel;
+    a.a0 = sh.herm_a0;
+    a.j0 = sh.herm_j0;
+    a.acc_out = sh.acc_out;
+    a.part_a = sh.blk_part;
+    a.part_j = sh.blk_part + sh.blk_rows;
+    a.ticks = sh.blk_ticks;
+    a.levels = sh.blk_levels;
+    a.list = sh.blk_list;
+    a.count = (int)sh.count;
+    a.stride = (unsigned int)c->in.slots;
+    a.soft2 = c->soft2;
+    return a;
+}
+
+// One block step: six launches of fixed size, whatever the device makes of them (nothing, once `done` is set).
+int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
+{
+    const unsigned per_body = (unsigned)((sh.count + 255) / 256), per_pair = (unsigned)((c->in.slots / 2 + 255) / 256);
+    hipLaunchKernelGGL(murb_block_min_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
+    hipLaunchKernelGGL(murb_block_predict_kernel, dim3(per_pair), dim3(256), 0, sh.compute, a, sh.blk_ctl);
+    hipLaunchKernelGGL(murb_block_plan_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
+    const MurbBlockSweepArgs sa{a.rec_pred, a.vel_pred, a.soft2};
+    hipLaunchKernelGGL((murb_force_jerk_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)block_grid(c)),
+                       dim3(kHermiteWaves * 64), 0, sh.compute, sa, sh.blk_ctl);
+    hipLaunchKernelGGL(murb_block_correct_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
+    hipLaunchKernelGGL(murb_block_book_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
+    return hip_rc(hipGetLastError());
 }
 
 // The compute streams of a shard.  reserve > 0: created with a CU mask that leaves out the `reserve` highest-numbered
@@ -1232,6 +1302,8 @@ int murbhip_destroy(murbhip_ctx* c)
         if (sh.metrics_host) (void)hipHostFree(sh.metrics_host);
         release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part, sh.herm_ctl);
         if (sh.herm_ctl_host) (void)hipHostFree(sh.herm_ctl_host);
+        release(sh.blk_ctl, sh.blk_ticks, sh.blk_levels, sh.blk_list, sh.blk_rec, sh.blk_vel, sh.blk_part);
+        if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
         free_sym_set(sh, sh.sym_main); free_sym_set(sh, sh.sym_tri);
     }
@@ -1468,14 +1540,14 @@ int murbhip_download_acc(murbhip_ctx* c, float* ax, float* ay, float* az)
 int murbhip_compute_acc(murbhip_ctx* c)
 {
     if (!c) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;
     return enqueue_iteration(c, 0.f, 0);
 }
 
 int murbhip_compute_acc_jerk(murbhip_ctx* c)
 {
     if (!c) return MURBHIP_E_INVALID;
-    if (!c->uploaded || c->lf_half) return MURBHIP_E_STATE;   // a leapfrog run in flight has half-step velocities
+    if (!c->uploaded || c->lf_half || c->blk_open) return MURBHIP_E_STATE;   // a leapfrog run in flight has half-step velocities
     return enqueue_hermite(c, 0.f, 0);
 }
 
@@ -1501,7 +1573,7 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
     if (!(duration > 0.0) || !std::isfinite(duration) || !(eta > 0.0) || !(eta_start > 0.0) || !std::isfinite(dt_max) ||
         !(dt_max > 0.f) || !(dt_min >= 0.f) || dt_min > dt_max || max_steps == 0)
         return MURBHIP_E_INVALID;
-    if (!c->uploaded || c->integrator != 2) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->integrator != 2 || c->blk_open) return MURBHIP_E_STATE;
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
     Shard& sh = c->shards[0];
     RC_TRY(shard_alloc(sh, sh.herm_ctl, sizeof(MurbEvolveCtl)));
@@ -1579,10 +1651,107 @@ int murbhip_evolve_dts(murbhip_ctx* c, float* dts, unsigned long capacity, unsig
     return 0;
 }
 
+int murbhip_evolve_block(murbhip_ctx* c, float dt_max, unsigned long blocks, double eta, double eta_start, int kmax,
+                         unsigned long max_steps, double* out8)
+{
+    if (!c || !out8) return MURBHIP_E_INVALID;
+    if (!std::isfinite(dt_max) || !(dt_max > 0.f) || blocks == 0 || blocks > 0xfffffffful || !(eta > 0.0) || !(eta_start > 0.0) ||
+        kmax < 0 || kmax > 20 || max_steps == 0 || !std::isnormal(std::ldexp(dt_max, -kmax)))
+        return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->integrator != 2) return MURBHIP_E_STATE;
+    if (c->blk_open && (dt_max != c->blk_dt_max || kmax != c->blk_kmax)) return MURBHIP_E_STATE;   // the open block is another grid's
+    const bool resume = c->blk_open;
+    RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
+    Shard& sh = c->shards[0];
+    RC_TRY(ensure_block(c, sh));
+    const MurbBlockArgs a = block_args(c, sh);
+    hipLaunchKernelGGL(murb_block_begin_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl, a, dt_max, kmax, eta, (unsigned int)blocks,
+                       (unsigned long long)max_steps, block_units(c), (int)(c->in.slots / MURB_TILE_BODIES),
+                       (unsigned int)std::min<size_t>(sh.blk_rows, 0xffffffffu), resume ? 1 : 0);
+    RC_TRY(hip_rc(hipGetLastError()));
+    const bool retained = c->blk_have_levels == 1 && dt_max == c->blk_dt_max && kmax == c->blk_kmax;
+    const bool given = c->blk_have_levels == 2 && kmax == c->blk_kmax;
+    if (!resume && !retained && !given) {
+        hipLaunchKernelGGL(murb_block_start_kernel, dim3((unsigned)((sh.count + 255) / 256)), dim3(256), 0, sh.compute, a, sh.blk_ctl, eta_start);
+        RC_TRY(hip_rc(hipGetLastError()));
+    }
+    // Batches.  The first: what the last call's blocks took, 16 steps without one; then what the remaining ticks take at the
+    // rate seen so far.  A batch longer than the run needs ends in launches that find `done` set.
+    MurbBlockCtl& head = *sh.blk_ctl_host;
+    const double T = (double)(1u << kmax);
+    double est = c->blk_steps_per_block > 0.0 ? c->blk_steps_per_block * (double)blocks : 16.0;
+    for (;;) {
+        unsigned long batch = (unsigned long)std::min<double>(std::max(std::ceil(est), 1.0), (double)kBlockBatch);
+        if (c->evolve_batch > 0) batch = (unsigned long)c->evolve_batch;   // timing aid: fixed length, no-op tail and all
+        int rc = 0;
+        for (unsigned long k = 0; k < batch && rc == 0; ++k) rc = enqueue_block_step(c, sh, a);
+        // the bodies changed whatever happens next; every body's (a, j) at its own time stay with them
+        invalidate_cached_forces(c);
+        c->herm_current = true;
+        c->herm_in_acc_out = true;
+        c->blk_open = true;   // until the head says otherwise
+        c->blk_dt_max = dt_max;
+        c->blk_kmax = kmax;
+        RC_TRY(rc);
+        HIP_TRY(hipMemcpyAsync(&head, sh.blk_ctl, sizeof(MurbBlockCtl), hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (c->async_error) return c->async_error;
+        if (head.done) break;
+        const double left = (double)head.blocks_left * T - (double)head.clock;
+        est = head.ticks_done ? (double)head.steps * left / (double)head.ticks_done : 16.0;
+        est = std::min(est, (double)(head.max_steps - head.steps));
+    }
+    c->blk_open = head.clock != 0u;
+    c->blk_have_levels = c->blk_open ? 0 : 1;
+    if (head.ticks_done) c->blk_steps_per_block = (double)head.steps * T / (double)head.ticks_done;
+    c->blk_info[0] = (double)head.steps;
+    c->blk_info[1] = (double)head.body_steps;
+    c->blk_info[2] = (double)head.clamped;
+    c->blk_info[3] = (double)head.max_act;
+    out8[0] = (double)head.ticks_done * head.tick_sec;
+    out8[1] = (double)head.steps;
+    out8[2] = (double)head.body_steps;
+    out8[3] = (double)std::ldexp(dt_max, -(int)head.k_hi);
+    out8[4] = (double)std::ldexp(dt_max, -(int)head.k_lo);
+    out8[5] = (double)head.clamped;
+    out8[6] = (double)head.max_act;
+    out8[7] = c->blk_open ? 0.0 : 1.0;
+    return 0;
+}
+
+int murbhip_block_state(murbhip_ctx* c, unsigned int* ticks, int* levels)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->shards.size() != 1 || !c->shards[0].blk_ticks) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    if (ticks) HIP_TRY(hipMemcpy(ticks, sh.blk_ticks, c->in.n * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    if (levels) HIP_TRY(hipMemcpy(levels, sh.blk_levels, c->in.n * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int murbhip_block_set_levels(murbhip_ctx* c, const int* levels, int kmax)
+{
+    if (!c || !levels || kmax < 0 || kmax > 20) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; i < c->in.n; ++i)
+        if (levels[i] < 0 || levels[i] > kmax) return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->integrator != 2 || c->blk_open || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    RC_TRY(ensure_block(c, sh));
+    RC_TRY(murbhip_sync(c));
+    HIP_TRY(hipMemcpy(sh.blk_levels, levels, c->in.n * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(sh.blk_ticks, 0, c->in.slots * sizeof(unsigned int)));
+    c->blk_have_levels = 2;
+    c->blk_kmax = kmax;
+    return 0;
+}
+
 int murbhip_warmup(murbhip_ctx* c, double milliseconds)
 {
     if (!c || !(milliseconds >= 0.0) || milliseconds > 10000.0) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;
     // a COUNT fixed by n and the number of ranks, not a clock: in rank mode every evaluation carries collectives, and
     // all ranks must enqueue the same number of them
     const double per_eval_s = (double)c->in.n * (double)c->in.n / (5e12 * (double)c->in.world) + 10e-6;
@@ -1604,7 +1773,7 @@ int murbhip_step(murbhip_ctx* c, float dt)
 int murbhip_steps(murbhip_ctx* c, float dt, int iterations)
 {
     if (!c || iterations < 0) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;   // an open block (murbhip_evolve_block): the bodies sit at different times
     for (int i = 0; i < iterations; ++i) {
         if (c->integrator == 2) { RC_TRY(enqueue_hermite(c, dt, 1)); continue; }
         RC_TRY(enqueue_iteration(c, dt, 1));
@@ -1703,7 +1872,7 @@ int device_metrics(murbhip_ctx* c, bool want_phi, double (&sums)[MURB_METRIC_VAL
 int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
 {
     if (!c || !kinetic || !potential) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;
     const Plan main_plan = current_plan(c);
     if (main_plan.symmetric && !c->energy_sweep) {
         // Pair-symmetric plan: the potential energy comes out of a FORCE evaluation (murb_kernels_sym.h, PHI = 2: two more
@@ -1808,7 +1977,7 @@ int murbhip_energy(murbhip_ctx* c, double* kinetic, double* potential)
 int murbhip_moments(murbhip_ctx* c, double* out10)
 {
     if (!c || !out10) return MURBHIP_E_INVALID;
-    if (!c->uploaded) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;
     RC_TRY(ensure_acc_for_readout(c));
     double sums[MURB_METRIC_VALUES];
     RC_TRY(device_metrics(c, false, sums));
@@ -1855,6 +2024,10 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "evolve_batch") {
         if (value < 0 || value > kEvolveBatch) return MURBHIP_E_INVALID;
         c->evolve_batch = (int)value;
+    }
+    else if (k == "block_units") {
+        if (value < 0 || value > kBlockMaxUnits) return MURBHIP_E_INVALID;
+        c->block_units = (int)value;
     }
     else if (k == "solo_shard") c->solo_shard = (int)value;
     else if (k == "cu_reserve") {
@@ -1910,6 +2083,12 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
                                      : p.persistent ? (double)p.sched[0].nblocks / std::max(resident_blocks(c->in), 1)
                                                     : (double)(p.parts_local + p.parts_remote);
     else if (k == "hermite_parts") *value = hermite_parts(c->in);   // j chunks of the acceleration + jerk sweep
+    else if (k == "block_units") *value = block_units(c);
+    else if (k == "block_grid") *value = block_grid(c);
+    else if (k == "block_steps") *value = c->blk_info[0];
+    else if (k == "block_body_steps") *value = c->blk_info[1];
+    else if (k == "block_clamped") *value = c->blk_info[2];
+    else if (k == "block_max_active") *value = c->blk_info[3];
     else if (k == "sym_waves") *value = p.symmetric ? p.waves : 0;
     else if (k == "sym_wide") *value = p.symmetric && sym_wide_chosen(c->sym_wide, c->sym_wide_needed) ? 1 : 0;
     else if (k == "taper") *value = p.symmetric ? p.taper : 0;

@@ -74,7 +74,7 @@ void *murbhost_sim_create(unsigned long n, const char *scheme, float soft, float
     return h;
 }
 // --im hip+tracking (leapfrog = 0) / hip+leapfrog (1) / hip+hermite (2): the value is murbhip's option "integrator";
-// hip+hermite+adaptive (3): option 2 driven by murbhip_evolve
+// hip+hermite+adaptive (3): option 2 driven by murbhip_evolve; hip+hermite+block (4): by murbhip_evolve_block
 void *murbhost_tracking_create(unsigned long n, const char *scheme, float soft, float dt, int leapfrog, int ndev,
                                const int *devices, int exchange)
 {
@@ -118,7 +118,8 @@ int murbhost_history_csv(const char *path, int rows, const double *energy, const
     }
     return 0;
 }
-// hip+hermite+adaptive: {substeps so far, smallest dt, largest dt}.  0, or -1 for a simulation with fixed steps.
+// hip+hermite+adaptive: {substeps so far, smallest dt, largest dt}; hip+hermite+block: block steps so far and the range of
+// the bodies' own dt.  0, or -1 for a simulation with fixed steps.
 int murbhost_sim_substeps(void *p, double *out3)
 {
     auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
@@ -126,6 +127,25 @@ int murbhost_sim_substeps(void *p, double *out3)
     out3[0] = (double)t->getSubsteps();
     out3[1] = t->getSmallestDt();
     out3[2] = t->getLargestDt();
+    return 0;
+}
+// hip+hermite+block: accuracy parameter and deepest level, before the first iteration.  0, or -1 for another simulation.
+int murbhost_sim_set_block(void *p, double eta, int kmax)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->hasBlockSteps()) return -1;
+    t->setEta(eta);
+    t->setKmax(kmax);
+    return 0;
+}
+// hip+hermite+block: {block steps so far (murbhost_sim_substeps' count), body-steps, clamped steps}.  0, or -1.
+int murbhost_sim_block_counts(void *p, double *out3)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->hasBlockSteps()) return -1;
+    out3[0] = (double)t->getSubsteps();
+    out3[1] = (double)t->getBodySteps();
+    out3[2] = (double)t->getClampedSteps();
     return 0;
 }
 int murbhost_sim_history_csv(void *p, const char *path)

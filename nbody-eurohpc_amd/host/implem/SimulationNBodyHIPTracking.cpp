@@ -10,7 +10,8 @@ SimulationNBodyHIPTracking<T, Q>::SimulationNBodyHIPTracking(const BodiesAllocat
                                                              std::shared_ptr<SimulationHistory<Q>> history, const T soft,
                                                              const int integrator, const std::vector<int> &devices,
                                                              int exchange)
-    : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}, adaptive{integrator == 3}
+    : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}, adaptive{integrator == 3 || integrator == 4},
+      blockSteps{integrator == 4}
 {
     if (!this->history) this->history = std::make_shared<SimulationHistory<Q>>();
     if (integrator)
@@ -34,7 +35,17 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::computeOneIteration()
 {
     computeMetrics();
-    if (adaptive) {   // exactly dt of model time, in the substeps the criterion chooses; returns synchronised
+    if (blockSteps) {   // one block of dt: every body in steps of its own, all synchronised at the end
+        double out[8];
+        this->hipBodiesPtr->invalidateDataSoA();
+        murbhipCheck(murbhip_evolve_block(this->hipBodiesPtr->getContext(), this->dt, 1ul, eta, 0.01, kmax, ~0ul, out),
+                     "murbhip_evolve_block");
+        dtSmallest = substeps ? std::min(dtSmallest, out[3]) : out[3];
+        dtLargest = std::max(dtLargest, out[4]);
+        substeps += (unsigned long)out[1];
+        bodySteps += (unsigned long)out[2];
+        clampedSteps += (unsigned long)out[5];
+    } else if (adaptive) {   // exactly dt of model time, in the substeps the criterion chooses; returns synchronised
         double out[5];
         this->hipBodiesPtr->invalidateDataSoA();
         murbhipCheck(murbhip_evolve(this->hipBodiesPtr->getContext(), (double)this->dt, eta, 0.01, 0.f, this->dt, 1000000ul, out),

@@ -1,10 +1,11 @@
-// `--im hip+tracking`, `--im hip+leapfrog`, `--im hip+hermite` and `--im hip+hermite+adaptive`: the MI355X path with a
+// `--im hip+tracking`, `--im hip+leapfrog`, `--im hip+hermite`, `--im hip+hermite+adaptive` and `--im hip+hermite+block`: the MI355X path with a
 // per-iteration metrics history —
 // the counterparts of the reference's gpu+tracking (SimulationNBodyCUDAPropertyTracking.hpp, energy of
 // the state each iteration starts from, computeOneIteration() at .cu:121-133) and gpu+leapfrog
 // (SimulationNBodyCUDALeapfrog.hpp: same history, leapfrog integrator); hip+hermite has no counterpart there, nor has
 // hip+hermite+adaptive, whose iteration advances the driver's dt in as many Hermite substeps as murbhip_evolve's criterion
-// asks for (the history still has one row per iteration).
+// asks for (the history still has one row per iteration), nor hip+hermite+block, whose iteration is one block of
+// murbhip_evolve_block: every body takes steps of its own size dt 2^-k, and every iteration returns synchronised.
 //
 // Filled per iteration: energy (kinetic + potential, reference definitions), |angular momentum| and the
 // centre of mass — the reference reserves the last two columns but never computes them
@@ -22,14 +23,18 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
   protected:
     std::shared_ptr<SimulationHistory<Q>> history;
     int currentIteration = 0;
-    bool adaptive = false;            // integrator 3: "integrator" 2 driven by murbhip_evolve
+    bool adaptive = false;            // integrator 3: "integrator" 2 driven by murbhip_evolve; 4: by murbhip_evolve_block
+    bool blockSteps = false;          // integrator 4
+    int kmax = 12;                    // its deepest level (--kmax): steps down to dt 2^-kmax
+    unsigned long bodySteps = 0, clampedSteps = 0;   // integrator 4: bodies advanced, and steps the cap was too coarse for
     double eta = 0.02;                // its accuracy parameter (--eta); the first step of all uses eta_start = 0.01
     unsigned long substeps = 0;       // substeps of all iterations so far
     double dtSmallest = 0, dtLargest = 0;   // ... and the range of their sizes
 
   public:
     // integrator: murbhip option "integrator" — 0 (false) the reference's update, 1 (true) kick-drift-kick leapfrog,
-    // 2 4th-order Hermite, 3 option 2 with shared adaptive steps (murbhip_evolve).  The parameter used to be
+    // 2 4th-order Hermite, 3 option 2 with shared adaptive steps (murbhip_evolve), 4 option 2 with individual block steps
+    // (murbhip_evolve_block; `substeps` then counts block steps).  The parameter used to be
     // `bool leapfrog`: callers that pass a bool get 0 / 1 as before.
     SimulationNBodyHIPTracking(const BodiesAllocatorInterface<T> &allocator, std::shared_ptr<SimulationHistory<Q>> history,
                                const T soft = 0.035f, const int integrator = 0, const std::vector<int> &devices = {0},
@@ -40,7 +45,11 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     void computeMetrics();                 // fills row `currentIteration` (grows the history if needed)
     const std::shared_ptr<SimulationHistory<Q>> getHistory() const { return history; }
     void setEta(const double e) { eta = e; }
+    void setKmax(const int k) { kmax = k; }
     bool isAdaptive() const { return adaptive; }
+    bool hasBlockSteps() const { return blockSteps; }
+    unsigned long getBodySteps() const { return bodySteps; }
+    unsigned long getClampedSteps() const { return clampedSteps; }
     unsigned long getSubsteps() const { return substeps; }
     double getSmallestDt() const { return dtSmallest; }
     double getLargestDt() const { return dtLargest; }

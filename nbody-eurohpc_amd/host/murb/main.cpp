@@ -41,7 +41,8 @@ int NDevices = 0;        // --ngpu, hip+tile+multi only (0 = all visible)
 bool FreeRunning = false;   // --free: sync once at the end instead of once per iteration
 bool DeviceInit = false;    // --dinit: generate the initial conditions on the device (bit-identical to the host's)
 std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+hermite[+adaptive] save their history
-double Eta = 0.02;          // --eta: accuracy parameter of hip+hermite+adaptive's step criterion
+double Eta = 0.02;          // --eta: accuracy parameter of hip+hermite+adaptive's and hip+hermite+block's step criterion
+int Kmax = 12;              // --kmax: hip+hermite+block, the deepest level (steps down to dt 2^-kmax)
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -77,6 +78,8 @@ static std::vector<Option> optionTable()
          "\t\t\t                      about twice the arithmetic of the 20 N^2 flops per iteration reported)\n"
          "\t\t\t - \"hip+hermite+adaptive\"  hip+hermite, every iteration of --dt seconds in as many substeps as the\n"
          "\t\t\t                      step criterion asks for (--eta)\n"
+         "\t\t\t - \"hip+hermite+block\"  hip+hermite with individual block time steps: every iteration is one block of\n"
+         "\t\t\t                      --dt seconds, every body in steps of its own size dt 2^-k, k <= --kmax (--eta)\n"
          "\t\t\t ----"},
         {"-soft", "softeningFactor", false, "softening factor."},
         {"s", "bodies scheme", false, "bodies scheme (initial conditions can be \"galaxy\" or \"random\")."},
@@ -85,7 +88,8 @@ static std::vector<Option> optionTable()
         {"-free", "", false, "free-running timing: one device sync at the end, not one per iteration."},
         {"-dinit", "", false, "generate the initial conditions on the device (same bodies, bit for bit)."},
         {"-csv", "file", false, "hip+tracking / hip+leapfrog / hip+hermite: save the metrics history as CSV."},
-        {"-eta", "accuracy", false, "hip+hermite+adaptive: accuracy parameter of the step criterion (default is 0.02)."},
+        {"-eta", "accuracy", false, "hip+hermite+adaptive / hip+hermite+block: accuracy parameter of the step criterion (default is 0.02)."},
+        {"-kmax", "levels", false, "hip+hermite+block: deepest step level, 0 to 20 (default is 12)."},
     };
 }
 
@@ -121,6 +125,13 @@ static void argsReader(int argc, char **argv)
         Eta = stod(reader.get_argument("-eta"));
         if (!(Eta > 0.0)) {
             std::cout << "The accuracy parameter --eta must be positive... exiting." << std::endl;
+            exit(-1);
+        }
+    }
+    if (given("-kmax")) {
+        Kmax = stoi(reader.get_argument("-kmax"));
+        if (Kmax < 0 || Kmax > 20) {
+            std::cout << "The deepest level --kmax must be between 0 and 20... exiting." << std::endl;
             exit(-1);
         }
     }
@@ -164,14 +175,16 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
         return new SimulationNBodyHIP<T>(hipAllocator, Softening, devices, /*exchange: RCCL when distinct GPUs*/
                                          use <= visible ? 1 : 0);
     }
-    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite" || ImplTag == "hip+hermite+adaptive") {
+    if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite" || ImplTag == "hip+hermite+adaptive" ||
+        ImplTag == "hip+hermite+block") {
         // shaped like main.cpp:245-261
         const std::map<std::string, int> integrator = {{"hip+tracking", 0}, {"hip+leapfrog", 1}, {"hip+hermite", 2},
-                                                       {"hip+hermite+adaptive", 3}};
+                                                       {"hip+hermite+adaptive", 3}, {"hip+hermite+block", 4}};
         HIPBodiesAllocator<T> hipAllocator(NBodies, BodiesScheme);
         History = std::make_shared<SimulationHistory<double>>((int)NIterations);
         auto *tracking = new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening, integrator.at(ImplTag));
         tracking->setEta(Eta);
+        tracking->setKmax(Kmax);
         return tracking;
     }
     std::cout << "Implementation '" << ImplTag << "' does not exist... Exiting." << std::endl;
@@ -249,7 +262,11 @@ int main(int argc, char **argv)
     std::cout << "Entire simulation took " << perfTotal.getElapsedTime() << " ms "
               << "(" << perfTotal.getFPS(iIte - 1) << " FPS" << gflops.str() << ")" << std::endl;
 
-    if (const auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu); tracking && tracking->isAdaptive())
+    if (const auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu); tracking && tracking->hasBlockSteps())
+        std::cout << "Block steps: " << tracking->getSubsteps() << " block steps, " << tracking->getBodySteps() << " body-steps, dt from "
+                  << std::setprecision(6) << tracking->getSmallestDt() << " to " << tracking->getLargestDt() << " sec, "
+                  << tracking->getClampedSteps() << " clamped (eta " << Eta << ", kmax " << Kmax << ")" << std::endl;
+    else if (tracking && tracking->isAdaptive())
         std::cout << "Adaptive steps: " << tracking->getSubsteps() << " substeps, dt from " << std::setprecision(6)
                   << tracking->getSmallestDt() << " to " << tracking->getLargestDt() << " sec (eta " << Eta << ")" << std::endl;
     if (History && History->getNumIterations() > 1) {

@@ -67,6 +67,10 @@ def lib():
         L.murbhip_evolve.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_ulong,
                                      C.POINTER(C.c_double)]
         L.murbhip_evolve_dts.argtypes = [C.c_void_p, _fp, C.c_ulong, C.POINTER(C.c_ulong)]
+        L.murbhip_evolve_block.argtypes = [C.c_void_p, C.c_float, C.c_ulong, C.c_double, C.c_double, C.c_int, C.c_ulong,
+                                           C.POINTER(C.c_double)]
+        L.murbhip_block_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+        L.murbhip_block_set_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -85,6 +89,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_device_count murbhip_create murbhip_create_sharded murbhip_unique_id murbhip_create_rank "
            "murbhip_destroy murbhip_upload murbhip_init_bodies murbhip_download_mass murbhip_download_state murbhip_download_acc murbhip_compute_acc "
            "murbhip_compute_acc_jerk murbhip_download_jerk murbhip_evolve murbhip_evolve_dts "
+           "murbhip_evolve_block murbhip_block_state murbhip_block_set_levels "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -248,6 +253,28 @@ class Simulation:
             _check(lib().murbhip_evolve_dts(self._h, _ptr(dts), count.value, C.byref(count)), "murbhip_evolve_dts")
         return dts
 
+    def evolve_block(self, dt_max, blocks=1, eta=0.02, eta_start=0.01, kmax=12, max_steps=2 ** 62):
+        """Advance `blocks` blocks of dt_max seconds with Hermite steps of individual size dt_max 2^-k, k <= kmax
+        (include/murbhip.h: murbhip_evolve_block; "integrator" must be 2).  Returns after a sync."""
+        out = (C.c_double * 8)()
+        _check(lib().murbhip_evolve_block(self._h, dt_max, blocks, eta, eta_start, kmax, max_steps, out), "murbhip_evolve_block")
+        return {"time": out[0], "steps": int(out[1]), "body_steps": int(out[2]), "dt_min": out[3], "dt_max": out[4],
+                "clamped": int(out[5]), "max_active": int(out[6]), "synchronised": bool(out[7])}
+
+    def block_state(self):
+        """(ticks uint32, levels int32) of every body: its own time inside the block and its level (test hook)."""
+        ticks, levels = np.zeros(self.n, np.uint32), np.zeros(self.n, np.int32)
+        _check(lib().murbhip_block_state(self._h, ticks.ctypes.data_as(C.POINTER(C.c_uint)), levels.ctypes.data_as(C.POINTER(C.c_int))),
+               "murbhip_block_state")
+        return ticks, levels
+
+    def set_block_levels(self, levels, kmax):
+        """The next evolve_block(kmax=kmax) starts from these levels instead of the starting rule (test hook)."""
+        lv = np.ascontiguousarray(levels, np.int32)
+        if lv.shape[0] < self.n:
+            raise ValueError("levels shorter than n")
+        _check(lib().murbhip_block_set_levels(self._h, lv.ctypes.data_as(C.POINTER(C.c_int)), kmax), "murbhip_block_set_levels")
+
     def integrate_host_acc(self, acc, dt):
         a = [_f32(x) for x in acc]
         _check(lib().murbhip_integrate_host_acc(self._h, *[_ptr(x) for x in a], dt), "murbhip_integrate_host_acc")
@@ -340,6 +367,8 @@ def host_lib():
         H.murbhost_history_csv.argtypes = [C.c_char_p, C.c_int, _dp, _dp, _dp]
         H.murbhost_sim_history_csv.argtypes = [C.c_void_p, C.c_char_p]
         H.murbhost_sim_substeps.argtypes = [C.c_void_p, _dp]
+        H.murbhost_sim_set_block.argtypes = [C.c_void_p, C.c_double, C.c_int]
+        H.murbhost_sim_block_counts.argtypes = [C.c_void_p, _dp]
         _host = H
     return _host
 
@@ -378,10 +407,12 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False, integrator=None):
+                 leapfrog=False, integrator=None, eta=0.02, kmax=12):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
-        driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for)."""
+        driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
+        `hip+hermite+block`, option 2 driven by murbhip_evolve_block: an iteration is one block of dt, every body in steps of
+        its own size dt 2^-k, k <= kmax, with accuracy parameter eta)."""
         if integrator is None:
             integrator = int(bool(leapfrog))
         arr = (C.c_int * len(devices))(*devices)
@@ -392,6 +423,13 @@ class HostSim:
         else:
             self.h = self.H.murbhost_sim_create(n, scheme.encode(), soft, dt, len(devices), arr, ex)
         self.n = int(self.H.murbhost_sim_n(self.h))
+        if integrator == 4:
+            self.H.murbhost_sim_set_block(self.h, eta, kmax)
+
+    def block_counts(self):
+        """integrator=4: (block steps so far, body-steps, clamped steps); None for the other plugins."""
+        out = (C.c_double * 3)()
+        return tuple(int(x) for x in out[:]) if self.H.murbhost_sim_block_counts(self.h, out) == 0 else None
 
     def history(self):
         """dict of the tracked metrics, one entry per computed iteration (tracking sims only)."""
@@ -411,7 +449,8 @@ class HostSim:
         self.H.murbhost_sim_step(self.h, iterations)
 
     def substeps(self):
-        """integrator=3: (substeps taken so far, smallest dt, largest dt); None for the fixed-step plugins."""
+        """integrator=3: (substeps taken so far, smallest dt, largest dt); integrator=4: (block steps so far, smallest and
+        largest dt of any body); None for the fixed-step plugins."""
         out = (C.c_double * 3)()
         return tuple(out[:]) if self.H.murbhost_sim_substeps(self.h, out) == 0 else None
 
