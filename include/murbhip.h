@@ -271,6 +271,43 @@ int murbhip_evolve_block(murbhip_ctx* ctx, float dt_max, unsigned long blocks, d
 int murbhip_block_state(murbhip_ctx* ctx, unsigned int* ticks, int* levels);
 int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
 
+/* Nearest neighbours from the Hermite sweeps, and an encounter stop.
+ *   Option "nearest" (0 default, 1; one shard with "integrator" 2 only, MURBHIP_E_STATE otherwise).  With 1, every acceleration
+ *   and jerk evaluation — murbhip_compute_acc_jerk, the sweep of a Hermite murbhip_step, the sweeps of murbhip_evolve, the active
+ *   sweep and the starting evaluation of murbhip_evolve_block — also keeps, per real body i,
+ *       nn_i   the index (in the caller's order, not a slot) of the nearest other real body, and
+ *       r2_i   the sweep's own fp32 value fma(dz,dz, fma(dy,dy, fma(dx,dx, soft^2))) of that pair, d = q_j - q_i: softening
+ *              included, the very number the force arithmetic used.
+ *   Candidates are all real bodies j != i, massless ones included; never the body itself (its r2 = soft^2 is the smallest of
+ *   all) and never the zero-mass padding slots that fill the layout up to whole blocks of 1024.  The minimum is lexicographic
+ *   in (r2 as fp32, index): among equal r2 the lowest index wins, so the result does not depend on how the j range is cut
+ *   ("jsplit", "block_units", the order of the active list) nor on the run: equal bits.  r2(i,j) == r2(j,i) bit for bit
+ *   (negating the differences is exact).  A lone body (n = 1) gets index -1 and r2 = +inf.
+ *   The values belong to the evaluation that produced them: after a step they are taken at that step's predicted end state,
+ *   like (a1, j1).  Under block steps only the active bodies' entries are refreshed; an inactive body keeps its (nn, r2) bit
+ *   for bit, exactly as it keeps its (a0, j0).  Switching the option drops the remembered evaluation, so a remembered
+ *   (a0, j0) always has its neighbours beside it.  With 0 every result is what it was without the option, bit for bit.
+ *   The nearest-neighbour sweeps are kernels of their own (csrc/murb_kernels_hermite.h; DESIGN.md 4.9 has their cost).
+ * murbhip_download_nearest: n entries each, either pointer may be NULL; waits for enqueued work.  MURBHIP_E_STATE when
+ *   "nearest" is 0 or no such evaluation is current (murbhip_download_jerk's rule; while a block is open it returns every
+ *   body's values at its own time, like the other download hooks).
+ * murbhip_set_encounter: radius 0 (default) = off; radius > 0 needs "nearest" 1 (MURBHIP_E_STATE otherwise, and setting
+ *   "nearest" to 0 while a radius is set is refused the same way); not finite or < 0: MURBHIP_E_INVALID.  With
+ *       thr = (float)((double)radius * radius + (double)soft^2)
+ *   a step of murbhip_evolve or murbhip_evolve_block in which any body that took the step has r2_i <= thr is a hit: the step
+ *   completes as usual (corrector, clock, counters, levels), the run ends behind it and the call returns 0 with
+ *   out5[0] < duration, or with out8[7] == 0 if it stopped inside a block (the open block behaves exactly as after a
+ *   max_steps stop).  A call always takes at least one step.  murbhip_step(s) never stops; it only keeps the neighbours.
+ * murbhip_encounters: the pairs (i, nn_i, r2_i) of the hitting step, sorted by i; the device keeps at most 4096 of them,
+ *   *count says how many there were (0: the last evolve call ended otherwise); `time` = the model time advanced in that call
+ *   when the hit was seen.  The list is cleared at the head of every evolve call.  NULL arrays ask for the count (and time)
+ *   alone; MURBHIP_E_INVALID when capacity < min(*count, 4096).
+ * Not covered: several shards or ranks; the other integrators and the pair-symmetric force kernel; per-body radii
+ * (collisions by r_i + r_j); merging; full neighbour lists. */
+int murbhip_download_nearest(murbhip_ctx* ctx, int* idx, float* r2);
+int murbhip_set_encounter(murbhip_ctx* ctx, float radius);
+int murbhip_encounters(murbhip_ctx* ctx, int* i, int* j, float* r2, unsigned long capacity, unsigned long* count, double* time);
+
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
  * §4.5) — as long as the reference's whole 200-iteration run at N = 30 000.  Construction is outside the reference's timing
@@ -399,6 +436,10 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    is cut into at least: chunks = ceil(U / groups) clamped to [1, layout tiles].  0 (default) = one per
  *                    workgroup the chip holds at once (5 per CU; info "block_units" / "block_grid"); up to 65 536.  The
  *                    results depend on it only through the chunk cut of the fp32 row sums
+ *   "nearest"        0 (default), 1: the Hermite sweeps also keep every body's nearest neighbour and its r2 (see
+ *                    murbhip_download_nearest above).  One shard with "integrator" 2 only (MURBHIP_E_STATE otherwise; while it is
+ *                    1, "integrator" cannot leave 2, and it cannot return to 0 while an encounter radius is set).  Switching
+ *                    it drops the remembered evaluation.  The active sweep then runs on 4 workgroups per CU instead of 5
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real
@@ -433,7 +474,8 @@ int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 
 /* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "sym_wide" (the form of the pair factor in use: 0 or 1; 0 on a one-sided plan), "taper",
  * "block_units", "block_grid" (work units and workgroups of murbhip_evolve_block's active sweep), "block_steps", "block_body_steps",
- * "block_clamped", "block_max_active" (the last murbhip_evolve_block call's counts),
+ * "block_clamped", "block_max_active" (the last murbhip_evolve_block call's counts), "nearest" (the option), "encounter_count" (hits of
+ * the step that ended the last evolve call: murbhip_encounters' *count),
  * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
  * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):

@@ -100,6 +100,10 @@ struct Shard {
     float4* blk_vel = nullptr;
     float4* blk_part = nullptr;               // partial rows of the active sweep: blk_rows entries of accelerations, then of jerks
     size_t blk_rows = 0;
+    // "nearest" (Hermite sweeps), allocated on first use (ensure_hermite)
+    int* nn_idx = nullptr;                    // per slot: nearest other real body of the remembered evaluation, -1 = none
+    float* nn_r2 = nullptr;                   // ... and the sweep's r2 of that pair
+    MurbEncList* enc = nullptr;               // the encounter list of the last murbhip_evolve / murbhip_evolve_block
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -176,6 +180,11 @@ struct murbhip_ctx {
     int blk_kmax = 0;
     double blk_steps_per_block = 0; // block steps a block took in the last call (sizes the first batch of the next)
     double blk_info[4] = {0, 0, 0, 0};   // last call: block steps, body-steps, clamped steps, largest active set
+    // nearest neighbours and the encounter stop (Hermite sweeps)
+    int nearest = 0;                // "nearest": the sweeps keep every body's nearest neighbour beside (a, j)
+    float enc_radius = 0.f;         // murbhip_set_encounter; 0 = off
+    unsigned long enc_count = 0;    // hits of the step that ended the last evolve call (0: it ended otherwise)
+    double enc_time = 0.0;          // ... and the model time advanced in that call when they were seen
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

@@ -38,16 +38,17 @@ struct MurbJerkArgs {
 
 // ---- one i body against two j bodies (packed): acceleration and jerk ----------------------------------------------
 // 6 pk_add + 6 pk_fma (|d|^2 + soft^2, d.w) + 2 rsq + 5 pk_mul + 9 pk_fma
-__device__ __forceinline__ void murb_interact_jerk_pk(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
-                                                      const murb_f2 uj, const murb_f2 vj, const murb_f2 wj,
-                                                      const float xi, const float yi, const float zi,
-                                                      const float ui, const float vi, const float wi, const float soft2,
-                                                      murb_f2& ax, murb_f2& ay, murb_f2& az,
-                                                      murb_f2& jx, murb_f2& jy, murb_f2& jz)
+// (the _r2 form hands out the pair of |d|^2 + soft^2 the force arithmetic uses: the nearest-neighbour sweeps keep its minimum)
+__device__ __forceinline__ void murb_interact_jerk_pk_r2(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
+                                                         const murb_f2 uj, const murb_f2 vj, const murb_f2 wj,
+                                                         const float xi, const float yi, const float zi,
+                                                         const float ui, const float vi, const float wi, const float soft2,
+                                                         murb_f2& ax, murb_f2& ay, murb_f2& az,
+                                                         murb_f2& jx, murb_f2& jy, murb_f2& jz, murb_f2& r2)
 {
     const murb_f2 dx = xj - xi, dy = yj - yi, dz = zj - zi;
     const murb_f2 wx = uj - ui, wy = vj - vi, wz = wj - wi;
-    murb_f2 r2 = __builtin_elementwise_fma(dx, dx, (murb_f2)(soft2));
+    r2 = __builtin_elementwise_fma(dx, dx, (murb_f2)(soft2));
     r2 = __builtin_elementwise_fma(dy, dy, r2);
     r2 = __builtin_elementwise_fma(dz, dz, r2);
     murb_f2 dw = dx * wx;
@@ -68,11 +69,202 @@ __device__ __forceinline__ void murb_interact_jerk_pk(const murb_f2 xj, const mu
     jz = __builtin_elementwise_fma(s, __builtin_elementwise_fma(c, dz, wz), jz);
 }
 
+__device__ __forceinline__ void murb_interact_jerk_pk(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
+                                                      const murb_f2 uj, const murb_f2 vj, const murb_f2 wj,
+                                                      const float xi, const float yi, const float zi,
+                                                      const float ui, const float vi, const float wi, const float soft2,
+                                                      murb_f2& ax, murb_f2& ay, murb_f2& az,
+                                                      murb_f2& jx, murb_f2& jy, murb_f2& jz)
+{
+    murb_f2 r2;
+    murb_interact_jerk_pk_r2(xj, yj, zj, gj, uj, vj, wj, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, r2);
+}
+
+// ---- nearest neighbour beside the sweep (option "nearest"; include/murbhip.h has the definition) ----------------------------
+// Every lane keeps, per i body, the minimum of the r2 it has formed (one three-operand minimum per pair of interactions)
+// and the lane step S = 4 * tile + q / 64 at which that minimum last fell (a compare and a select).  j slots rise with S in a
+// lane, and the select takes a strictly smaller value only, so S is the EARLIEST step holding the lane's minimum.  After
+// the loop the lane forms that one step's two r2 again from the records in memory — the same subtractions and fused
+// multiply-adds, hence the same bits — and takes the first of the two that holds the minimum: the lowest slot.  The wave
+// then folds (r2 bits, slot) lexicographically, and lane r writes body r's pair into the fourth floats of its two
+// partial-row records; whoever adds the rows up takes the lexicographic minimum beside the sums (murb_nn_fold_row).
+// The body itself and the zero-mass padding are no candidates.  Testing that per pair would cost every pair; instead the
+// wave asks per tile (wave-uniform) whether it holds one of its i bodies or slots >= count, and only those tiles run the
+// masked form of the step, which replaces the r2 of such a slot by +inf before the minimum.
+#define MURB_F32_INF_BITS 0x7f800000u
+#define MURB_NN_NONE 0x7fffffffu   // "no candidate" in the rows (the public index is -1)
+#define MURB_ENC_CAP 4096          // pairs the encounter list keeps
+
+__device__ __forceinline__ unsigned int murb_wave_min_bits(const float v);   // below
+
+struct MurbNNJerkArgs : MurbJerkArgs {
+    int count;   // real bodies: slots >= count are padding
+};
+
+// (i, nn_i, r2_i) of the bodies whose r2 was within the encounter threshold in the step that ended the run; order unspecified
+struct MurbEncList {
+    int i[MURB_ENC_CAP], j[MURB_ENC_CAP];
+    float r2[MURB_ENC_CAP];
+};
+
+// The kernel's first argument read again from the kernel-argument segment (scalar loads).  Behind the sweep's loop this
+// re-makes what the fold and the stores need instead of holding it in scalar registers through the loop; the empty asm
+// makes the pointer a new value to the compiler.
+template <typename Args>
+__device__ __forceinline__ const __attribute__((address_space(4))) Args* murb_kernarg_again()
+{
+    unsigned long p = (unsigned long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (const __attribute__((address_space(4))) Args*)p;
+}
+
+// Does the tile hold padding or one of the wave's own bodies (self_tile: the layout tiles they lie in)?  Wave-uniform.
+template <int RT>
+__device__ __forceinline__ bool murb_nn_tile_masked(const int tile, const int (&self_tile)[RT], const int count)
+{
+    bool m = (tile + 1) * MURB_TILE_BODIES > count;
+#pragma unroll
+    for (int r = 0; r < RT; ++r) m |= self_tile[r] == tile;
+    return m;
+}
+
+// One staged tile against the wave's i bodies: the sweep's inner loop with the minimum beside it, no exclusion.  A masked
+// tile runs the same code with the minima's signs set: r2 >= 0, so nothing is smaller than -mn, the minimum stays and no
+// step is recorded; the signs are cleared behind the tile.  That is 8 vector instructions per masked or unmasked tile of
+// 1 900, and the loop nest keeps ONE copy of the arithmetic (a second, masked copy as the other arm of a branch made the
+// register allocator spill hundreds of values in both arms).  murb_nn_masked_tile looks at such a tile's pairs after the loop.
+template <int R>
+__device__ __forceinline__ void murb_nn_tile(const float4* tq, const float4* tv, const int lane, const int tile, const bool masked,
+                                             const float (&xi)[R], const float (&yi)[R], const float (&zi)[R],
+                                             const float (&ui)[R], const float (&vi)[R], const float (&wi)[R], const float soft2,
+                                             murb_f2 (&ax)[R], murb_f2 (&ay)[R], murb_f2 (&az)[R],
+                                             murb_f2 (&jx)[R], murb_f2 (&jy)[R], murb_f2 (&jz)[R],
+                                             float (&mn)[R], int (&st)[R])
+{
+    const float sign = masked ? -1.f : 1.f;   // wave-uniform
+#pragma unroll
+    for (int r = 0; r < R; ++r) mn[r] *= sign;
+#pragma unroll
+    for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
+        const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
+        const float4 VA = tv[q + lane], VB = tv[q + lane + MURB_TILE_PAIRS];
+        const murb_f2 xj = {A.x, A.y}, yj = {A.z, A.w}, zj = {B.x, B.y}, gj = {B.z, B.w};
+        const murb_f2 uj = {VA.x, VA.y}, vj = {VA.z, VA.w}, wj = {VB.x, VB.y};
+        const int S = tile * (MURB_TILE_PAIRS / 64) + q / 64;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            murb_f2 r2;
+            murb_interact_jerk_pk_r2(xj, yj, zj, gj, uj, vj, wj, xi[r], yi[r], zi[r], ui[r], vi[r], wi[r], soft2,
+                                     ax[r], ay[r], az[r], jx[r], jy[r], jz[r], r2);
+            const float m = __builtin_fminf(__builtin_fminf(mn[r], r2.x), r2.y);
+            st[r] = m < mn[r] ? S : st[r];
+            mn[r] = m;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) mn[r] = __builtin_fabsf(mn[r]);
+}
+
+// r2 of one i body and one j body behind the loop, in single instructions: the same three subtractions and three fused
+// multiply-adds as one half of the sweep's packed ones, hence the same bits.  Written as instructions so that the compiler
+// does not pack them two by two again: the kernels' packed arithmetic stays exactly the sweep's (the code-object tests
+// compare the instruction counts).
+__device__ __forceinline__ float murb_nn_r2_single(const float xj, const float yj, const float zj,
+                                                   const float xi, const float yi, const float zi, const float soft2)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    float dx, dy, dz, r2;
+    asm("v_subrev_f32 %0, %1, %2" : "=v"(dx) : "s"(xi), "v"(xj));
+    asm("v_subrev_f32 %0, %1, %2" : "=v"(dy) : "s"(yi), "v"(yj));
+    asm("v_subrev_f32 %0, %1, %2" : "=v"(dz) : "s"(zi), "v"(zj));
+    asm("v_fma_f32 %0, %1, %1, %2" : "=v"(r2) : "v"(dx), "v"(soft2));
+    asm("v_fma_f32 %0, %1, %1, %2" : "=v"(r2) : "v"(dy), "v"(r2));
+    asm("v_fma_f32 %0, %1, %1, %2" : "=v"(r2) : "v"(dz), "v"(r2));
+    return r2;
+#else
+    const float dx = xj - xi, dy = yj - yi, dz = zj - zi;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, soft2)));
+#endif
+}
+
+// The pairs of one masked tile, from the records in memory: r2 alone, formed like the sweep forms it (the same bits), with
+// the body itself and the padding left out.  Runs after the loop, so the steps no longer rise: an equal r2 at an earlier
+// step takes the place.
+template <int R>
+__device__ __forceinline__ void murb_nn_masked_tile(const float4* rec, const int lane, const int tile,
+                                                    const float (&xi)[R], const float (&yi)[R], const float (&zi)[R], const float soft2,
+                                                    float (&mn)[R], int (&st)[R], const int (&self)[R], const int count)
+{
+#pragma unroll 1
+    for (int qs = 0; qs < MURB_TILE_PAIRS / 64; ++qs) {
+        const unsigned long ra = (unsigned long)tile * MURB_TILE_F4 + qs * 64 + lane;
+        const float4 A = rec[ra], B = rec[ra + MURB_TILE_PAIRS];
+        const int S = tile * (MURB_TILE_PAIRS / 64) + qs;
+        const int j0 = tile * MURB_TILE_BODIES + 2 * (qs * 64 + lane);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float r2x = murb_nn_r2_single(A.x, A.z, B.x, xi[r], yi[r], zi[r], soft2);
+            float r2y = murb_nn_r2_single(A.y, A.w, B.y, xi[r], yi[r], zi[r], soft2);
+            if (j0 == self[r] || j0 >= count) r2x = __builtin_inff();
+            if (j0 + 1 == self[r] || j0 + 1 >= count) r2y = __builtin_inff();
+            const float m = __builtin_fminf(r2x, r2y);
+            if (m < mn[r] || (m == mn[r] && S < st[r])) { mn[r] = m; st[r] = S; }
+        }
+    }
+}
+
+// After the loop: the slot behind every lane's minimum, the fold over the wave; lane r gets body r's (r2 bits, slot).
+template <int R>
+__device__ __forceinline__ void murb_nn_finish(const float4* rec, const int lane, const float (&xi)[R], const float (&yi)[R],
+                                               const float (&zi)[R], const float soft2, const float (&mn)[R], const int (&st)[R],
+                                               const int (&self)[R], const int count, unsigned int& out_r2, unsigned int& out_idx)
+{
+    out_r2 = MURB_F32_INF_BITS;
+    out_idx = MURB_NN_NONE;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int p = st[r] * 64 + lane;   // the pair of slots of lane step st[r]
+        const unsigned long ra = murb_rec_a((unsigned long)p);
+        const float4 A = rec[ra], B = rec[ra + MURB_TILE_PAIRS];
+        const float r2x = murb_nn_r2_single(A.x, A.z, B.x, xi[r], yi[r], zi[r], soft2);
+        const int j0 = 2 * p;
+        const bool first = r2x == mn[r] && j0 != self[r] && j0 < count;
+        const unsigned int idx = mn[r] < __builtin_inff() ? (unsigned int)(first ? j0 : j0 + 1) : MURB_NN_NONE;
+        const unsigned int mb = murb_wave_min_bits(mn[r]);
+        const unsigned int cand = __builtin_bit_cast(unsigned int, mn[r]) == mb ? idx : MURB_NN_NONE;
+        const unsigned int ib = murb_wave_min_bits(__builtin_bit_cast(float, cand));   // an unsigned minimum of the bits
+        if (lane == r) { out_r2 = mb; out_idx = ib; }
+    }
+}
+
+// Where rows are added up in chunk order: the lexicographic minimum of (r2 bits, slot) beside the sums.
+__device__ __forceinline__ void murb_nn_fold_row(unsigned int& r2, unsigned int& idx, const float4 u, const float4 w)
+{
+    const unsigned int ub = __builtin_bit_cast(unsigned int, u.w), ib = __builtin_bit_cast(unsigned int, w.w);
+    if (ub < r2 || (ub == r2 && ib < idx)) { r2 = ub; idx = ib; }
+}
+
+__device__ __forceinline__ void murb_nn_store(int* nn_idx, float* nn_r2, const int s, const unsigned int r2, const unsigned int idx)
+{
+    nn_idx[s] = idx == MURB_NN_NONE ? -1 : (int)idx;
+    nn_r2[s] = idx == MURB_NN_NONE ? __builtin_inff() : __builtin_bit_cast(float, r2);
+}
+
+// A body that took the step with r2 <= thr is a hit: it takes a place in the list (a vector atomic, like the active list's).
+__device__ __forceinline__ void murb_enc_test(unsigned int* hits, MurbEncList* list, const float thr, const int i,
+                                              const unsigned int r2, const unsigned int idx)
+{
+    if (idx == MURB_NN_NONE || !(__builtin_bit_cast(float, r2) <= thr)) return;
+    const unsigned int at = atomicAdd(hits, 1u);
+    if (at < MURB_ENC_CAP) { list->i[at] = i; list->j[at] = (int)idx; list->r2[at] = __builtin_bit_cast(float, r2); }
+}
+
 // ---- the sweep -------------------------------------------------------------------------------------------------------
 // grid.x = i groups of WAVES*R bodies, grid.y = j chunks.  LDS: STAGE position tiles + STAGE velocity tiles (16 KiB a stage).
 // The body is a device function so that the adaptive launch (murb_force_jerk_adaptive_kernel, below) runs the same code.
-template <int R, int WAVES, int STAGE>
-__device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
+// NN: the nearest-neighbour form (Args = MurbNNJerkArgs); the plain form's code does not change with it.
+template <int R, int WAVES, int STAGE, bool NN = false, typename Args = MurbJerkArgs>
+__device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
 {
     static_assert(R % 2 == 0 && MURB_TILE_BODIES % (WAVES * R) == 0, "i groups must tile the layout");
     __shared__ float4 lds[2 * STAGE * MURB_TILE_F4];
@@ -115,6 +307,14 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
         ax[r] = (murb_f2)(0.f); ay[r] = (murb_f2)(0.f); az[r] = (murb_f2)(0.f);
         jx[r] = (murb_f2)(0.f); jy[r] = (murb_f2)(0.f); jz[r] = (murb_f2)(0.f);
     }
+    float mn[R];   // NN: the lane's smallest r2 per i body, and the lane step it fell at
+    int st[R], self_tile[1] = {0}, count = 0;
+    if constexpr (NN) {
+        count = a.count;
+        self_tile[0] = i_slot / MURB_TILE_BODIES;   // a wave's i bodies lie in one layout tile
+#pragma unroll
+        for (int r = 0; r < R; ++r) { mn[r] = __builtin_inff(); st[r] = 0; }
+    }
 
     for (int vs = vt0; vs < vt1; vs += STAGE) {
         const int nt = (vt1 - vs) < STAGE ? (vt1 - vs) : STAGE;
@@ -122,6 +322,16 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
         for (int t = 0; t < nt; ++t) {
             const float4* srcq = a.rec + (unsigned long)(vs + t) * MURB_TILE_F4;
             const float4* srcv = a.vel + (unsigned long)(vs + t) * MURB_TILE_F4;
+            if constexpr (NN) {   // whole rounds, like the active sweep's copy: no bounds tests held in scalar registers
+                static_assert(MURB_TILE_F4 % (WAVES * 64) == 0, "the workgroup copies a tile in whole rounds");
+#pragma unroll
+                for (int c = 0; c < MURB_TILE_F4 / (WAVES * 64); ++c) {
+                    const int k = threadIdx.x + c * WAVES * 64;
+                    lds[(2 * t) * MURB_TILE_F4 + k] = srcq[k];
+                    lds[(2 * t + 1) * MURB_TILE_F4 + k] = srcv[k];
+                }
+                continue;
+            }
 #pragma unroll
             for (int k = threadIdx.x; k < MURB_TILE_F4; k += WAVES * 64) {
                 lds[(2 * t) * MURB_TILE_F4 + k] = srcq[k];
@@ -132,6 +342,11 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
         for (int t = 0; t < nt; ++t) {
             const float4* tq = lds + (2 * t) * MURB_TILE_F4;
             const float4* tv = tq + MURB_TILE_F4;
+            if constexpr (NN) {
+                const bool masked = murb_nn_tile_masked<1>(vs + t, self_tile, count);   // wave-uniform
+                murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                continue;
+            }
 #pragma unroll
             for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
                 const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
@@ -146,6 +361,26 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
         }
     }
 
+    float nn_a = 0.f, nn_j = 0.f;   // the rows' fourth floats
+    if constexpr (NN) {
+        const auto* again = murb_kernarg_again<Args>();   // `a` is the nearest-neighbour kernel's first argument
+        const float4* const rec = again->rec;
+        const int cnt = again->count;
+        int self[R], first = i_slot;
+        asm volatile("" : "+s"(first));   // the bodies' slots are made here, not held through the loop
+#pragma unroll
+        for (int r = 0; r < R; ++r) self[r] = first + r;
+        const int tiles = again->tiles, nchunks = again->nchunks;
+        const int t0 = (int)(((long)tiles * chunk) / nchunks), t1 = (int)(((long)tiles * (chunk + 1)) / nchunks);   // vt0, vt1 again
+        const int own[1] = {first / MURB_TILE_BODIES};
+        for (int tile = t0; tile < t1; ++tile)
+            if (murb_nn_tile_masked<1>(tile, own, cnt)) murb_nn_masked_tile<R>(rec, lane, tile, xi, yi, zi, soft2, mn, st, self, cnt);
+        unsigned int nn_r2, nn_idx;
+        murb_nn_finish<R>(rec, lane, xi, yi, zi, soft2, mn, st, self, cnt, nn_r2, nn_idx);
+        nn_a = __builtin_bit_cast(float, nn_r2);
+        nn_j = __builtin_bit_cast(float, nn_idx);
+    }
+
     // fold the 64 lanes x 2 halves of every accumulator; lane r keeps body r's totals
     float oa[3] = {0.f, 0.f, 0.f}, oj[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -155,9 +390,16 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const MurbJerkArgs a)
         if (lane == r) { oa[0] = sx; oa[1] = sy; oa[2] = sz; oj[0] = tx; oj[1] = ty; oj[2] = tz; }
     }
     if (lane < R) {
-        const unsigned long at = (unsigned long)chunk * a.stride + (unsigned long)i_slot + lane;
-        a.part_a[at] = make_float4(oa[0], oa[1], oa[2], 0.f);
-        a.part_j[at] = make_float4(oj[0], oj[1], oj[2], 0.f);
+        if constexpr (NN) {
+            const auto* again = murb_kernarg_again<Args>();
+            const unsigned long at = (unsigned long)chunk * again->stride + (unsigned long)i_slot + lane;
+            again->part_a[at] = make_float4(oa[0], oa[1], oa[2], nn_a);
+            again->part_j[at] = make_float4(oj[0], oj[1], oj[2], nn_j);
+        } else {
+            const unsigned long at = (unsigned long)chunk * a.stride + (unsigned long)i_slot + lane;
+            a.part_a[at] = make_float4(oa[0], oa[1], oa[2], nn_a);
+            a.part_j[at] = make_float4(oj[0], oj[1], oj[2], nn_j);
+        }
     }
 }
 
@@ -187,6 +429,9 @@ struct MurbHermiteArgs {
     unsigned int stride;    // slots
     float dt;
     int update_state;       // corrector: 0 = only sum the rows into a0 / j0 (evaluation at the current state)
+    int* nn_idx;            // "nearest": every slot's nearest neighbour and its r2, folded beside the row sums; null = off
+    float* nn_r2;
+    MurbEncList* enc;       // ... and the encounter list of murbhip_evolve
 };
 
 __device__ __forceinline__ float murb_hermite_predict_q(float q, float v, float a, float j, double dt, double c2, double c3)
@@ -261,6 +506,7 @@ __global__ __launch_bounds__(256) void murb_hermite_predict_kernel(const MurbHer
 // The two evaluations a corrector thread holds for its two slots: [slot][component]
 struct MurbHermiteForces {
     float a0[2][3], j0[2][3], a1[2][3], j1[2][3];
+    unsigned int nn_r2[2], nn_idx[2];   // "nearest": (r2 bits, slot) of the evaluation that gave (a1, j1)
 };
 
 // Partial rows -> (a1, j1) in fixed order; (a0, j0) are read, then replaced by (a1, j1).
@@ -272,6 +518,8 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int k = 0; k < 3; ++k) { f.a1[h][k] = 0.f; f.j1[h][k] = 0.f; }
+    f.nn_r2[0] = f.nn_r2[1] = MURB_F32_INF_BITS;
+    f.nn_idx[0] = f.nn_idx[1] = MURB_NN_NONE;
     for (int p = 0; p < a.nparts; ++p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -279,7 +527,12 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
             const float4 w = a.part_j[(unsigned long)p * n + s0 + h];
             f.a1[h][0] += u.x; f.a1[h][1] += u.y; f.a1[h][2] += u.z;
             f.j1[h][0] += w.x; f.j1[h][1] += w.y; f.j1[h][2] += w.z;
+            murb_nn_fold_row(f.nn_r2[h], f.nn_idx[h], u, w);
         }
+    }
+    if (a.nn_idx) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) murb_nn_store(a.nn_idx, a.nn_r2, s0 + h, f.nn_r2[h], f.nn_idx[h]);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -356,7 +609,6 @@ __global__ __launch_bounds__(256) void murb_hermite_correct_kernel(const MurbHer
 // min_i dt_i rounded to fp32 — rounding is monotonic, so the minimum of the rounded values is the rounded minimum — and
 // positive floats order like their bit patterns, which is what the atomicMin compares.
 #define MURB_EVOLVE_RING 4096
-#define MURB_F32_INF_BITS 0x7f800000u
 
 struct MurbEvolveCtl {
     double t;                       // model time advanced in this call
@@ -371,6 +623,8 @@ struct MurbEvolveCtl {
     float used_min, used_max;       // smallest and largest step taken in this call
     int done;                       // duration reached or max_steps taken: every later launch of the batch is a no-op
     int last;                       // the step in flight ends at `duration` exactly
+    unsigned int enc_hits;          // bodies of the step just taken with r2 <= enc_thr ("nearest"): non-zero ends the run
+    float enc_thr;                  // radius^2 + soft^2, or -1: no encounter stop
     float ring[MURB_EVOLVE_RING];   // ring[k % MURB_EVOLVE_RING] = step k of this call
 };
 
@@ -462,8 +716,11 @@ __device__ __forceinline__ void murb_evolve_choose(MurbEvolveCtl* c)
 // Head of a call, one thread.  fresh: no proposal is retained for the remembered (a0, j0) — murb_evolve_first_kernel and
 // murb_evolve_start_kernel follow; otherwise `raw` is the previous adaptive step's and the first step is chosen here.
 __global__ void murb_evolve_begin_kernel(MurbEvolveCtl* c, const double duration, const double eta, const float dt_lo,
-                                         const float dt_hi, const unsigned long long max_steps, const int fresh)
+                                         const float dt_hi, const unsigned long long max_steps, const int fresh,
+                                         const float enc_thr)
 {
+    c->enc_hits = 0u;
+    c->enc_thr = enc_thr;
     c->t = 0.0;
     c->duration = duration;
     c->eta = eta;
@@ -514,7 +771,7 @@ __global__ void murb_evolve_book_kernel(MurbEvolveCtl* c)
     c->raw = __builtin_bit_cast(float, c->cand);
     c->cand = MURB_F32_INF_BITS;
     murb_evolve_choose(c);
-    if (was_last || c->steps >= c->max_steps) c->done = 1;
+    if (was_last || c->steps >= c->max_steps || c->enc_hits) c->done = 1;
 }
 
 __global__ __launch_bounds__(256) void murb_hermite_predict_adaptive_kernel(const MurbHermiteArgs a, const MurbEvolveCtl* ctl)
@@ -530,6 +787,14 @@ __global__ __launch_bounds__(WAVES * 64) void murb_force_jerk_adaptive_kernel(co
 {
     if (ctl->done) return;   // one wave-uniform load, before anything else
     murb_force_jerk_sweep<R, WAVES, STAGE>(a);
+}
+
+// The nearest-neighbour form of both launches (ctl null: the fixed-step one).  104+ vector registers: 4 waves per SIMD.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_nn_sweep_kernel(const MurbNNJerkArgs a, const MurbEvolveCtl* ctl)
+{
+    if (ctl && ctl->done) return;   // wave-uniform
+    murb_force_jerk_sweep<R, WAVES, STAGE, true, MurbNNJerkArgs>(a);
 }
 
 // The corrector of an adaptive step: murb_hermite_correct_kernel's work with dt from the control block, then the criterion.
@@ -557,6 +822,12 @@ __global__ __launch_bounds__(256) void murb_hermite_correct_adaptive_kernel(cons
 #pragma unroll
         for (int h = 0; h < 2; ++h)
             if (s0 + h < a.count) mine = fminf(mine, murb_evolve_body_step(f.a0[h], f.j0[h], f.a1[h], f.j1[h], (double)dt, eta));
+        if (a.nn_idx) {
+            const float thr = ctl->enc_thr;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (s0 + h < a.count) murb_enc_test(&ctl->enc_hits, a.enc, thr, s0 + h, f.nn_r2[h], f.nn_idx[h]);
+        }
     }
     murb_evolve_fold_min(ctl, mine);
 }
@@ -605,6 +876,10 @@ struct MurbBlockCtl {
     const float4* vel_act;
     float4* part_a;
     float4* part_j;
+    // "nearest"
+    const int* list;                 // the active list, where the nearest-neighbour sweep finds its i bodies' slots
+    unsigned int enc_hits;           // active bodies of the step just taken with r2 <= enc_thr: non-zero ends the run
+    float enc_thr;                   // radius^2 + soft^2, or -1: no encounter stop
 };
 
 struct MurbBlockArgs {
@@ -622,6 +897,9 @@ struct MurbBlockArgs {
     unsigned int* ticks;   // t_i
     int* levels;           // k_i
     int* list;             // active bodies, unordered
+    int* nn_idx;           // "nearest": every body's nearest neighbour and its r2 at its own time; null = off
+    float* nn_r2;
+    MurbEncList* enc;
     int count;
     unsigned int stride;   // slots
     float soft2;
@@ -632,6 +910,12 @@ struct MurbBlockSweepArgs {
     const float4* rec_pred;
     const float4* vel_pred;
     float soft2;
+};
+
+struct MurbBlockNNSweepArgs : MurbBlockSweepArgs {
+    int count;                  // real bodies: slots >= count are padding
+    int grid;                   // workgroups of the launch
+    const MurbBlockCtl* ctl;    // the control block once more: the sweep reads both here, once per unit (murb_kernarg_again)
 };
 
 // dt_max 2^-k: exact while the result is a normal number
@@ -668,8 +952,11 @@ __device__ __forceinline__ float* murb_block_slot(float4* recs, const unsigned i
 // Head of a call, one thread.  `resume`: a block is open, the clock and the bodies' ticks and levels go on.
 __global__ void murb_block_begin_kernel(MurbBlockCtl* c, const MurbBlockArgs a, const float dt_max, const int kmax, const double eta, const unsigned int blocks,
                                         const unsigned long long max_steps, const int units, const int tiles,
-                                        const unsigned int row_cap, const int resume)
+                                        const unsigned int row_cap, const int resume, const float enc_thr)
 {
+    c->list = a.list;
+    c->enc_hits = 0u;
+    c->enc_thr = enc_thr;
     c->tick_sec = (double)dt_max * (double)murb_block_dt(1.f, kmax);
     c->eta = eta;
     c->ticks_done = 0;
@@ -801,8 +1088,10 @@ __device__ __forceinline__ MurbBlockCtlK murb_block_ctl_now(const MurbBlockCtl* 
 // launch 4.  murb_force_jerk_sweep's mapping and inner loop; the i bodies come from the compact buffer, and the workgroup
 // walks units u = blockIdx.x, += gridDim.x with (group, chunk) = (u % groups, u / groups).  The entries behind the list's
 // end in its last group are whatever the buffer held: their rows are never read.
-template <int R, int WAVES, int STAGE>
-__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5))) void murb_force_jerk_block_kernel(const MurbBlockSweepArgs a, const MurbBlockCtl* ctl)
+// The body is a device function with the nearest-neighbour form behind a compile-time switch (NN, Args =
+// MurbBlockNNSweepArgs), like murb_force_jerk_sweep: the plain form's code does not change with it.
+template <int R, int WAVES, int STAGE, bool NN = false, typename Args = MurbBlockSweepArgs>
+__device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const MurbBlockCtl* ctl)  // NN: a is the kernel's first argument
 {
     static_assert(R % 2 == 0 && WAVES * R == MURB_BLOCK_GROUP, "a workgroup takes one group of the list");
     static_assert(MURB_TILE_F4 % (WAVES * 64) == 0, "the workgroup copies a tile in whole rounds");
@@ -813,12 +1102,24 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float soft2 = a.soft2;
 
-    for (int u = blockIdx.x;; u += gridDim.x) {
+    int stride_u = 0;
+    for (int u = blockIdx.x;; u += NN ? stride_u : (int)gridDim.x) {
+        if constexpr (NN) {   // the scalar registers are taken: the stride and the control block from the kernel arguments, per unit
+            const auto* again = murb_kernarg_again<Args>();
+            stride_u = again->grid;
+            ctl = again->ctl;
+        }
         const MurbBlockCtlK now = murb_block_ctl_now(ctl);
         const int groups = now->groups, chunks = now->chunks, tiles = now->tiles;
         if (u >= groups * chunks) break;   // workgroup-uniform
         const int chunk = u / groups, group = u - chunk * groups;
-        const int i_slot = (group * WAVES + wave) * R;   // list index, wave-uniform
+        int wave_now = wave;
+        if constexpr (NN) {   // made in every unit, like the fold's lane below: the scalar registers are taken
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            wave_now = __builtin_amdgcn_readfirstlane(tid >> 6);
+        }
+        const int i_slot = (group * WAVES + wave_now) * R;   // list index, wave-uniform
 
         float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
         {
@@ -832,6 +1133,20 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
                 xi[2 * h] = A.x; xi[2 * h + 1] = A.y; yi[2 * h] = A.z; yi[2 * h + 1] = A.w; zi[2 * h] = B.x; zi[2 * h + 1] = B.y;
                 ui[2 * h] = VA.x; ui[2 * h + 1] = VA.y; vi[2 * h] = VA.z; vi[2 * h + 1] = VA.w; wi[2 * h] = VB.x; wi[2 * h + 1] = VB.y;
             }
+        }
+        float mn[R];   // NN: the lane's smallest r2 per i body, and the lane step it fell at
+        int st[R];
+        // NN: the i bodies' slots in lanes 0 .. R - 1 of ONE vector register and the body count in lane R, read out lane by lane
+        // where they are needed: the scalar registers are taken (an entry behind the list's end is a slot of an earlier step or 0,
+        // its row is never read)
+        int who = 0;
+        if constexpr (NN) {
+            int l = threadIdx.x & 63;
+            asm volatile("" : "+v"(l));
+            const int slot = ((const int*)now->list)[i_slot + (l & (R - 1))];
+            who = l < R ? slot : murb_kernarg_again<Args>()->count;   // `a` is the kernel's first argument
+#pragma unroll
+            for (int r = 0; r < R; ++r) { mn[r] = __builtin_inff(); st[r] = 0; }
         }
 
         const int vt0 = (int)(((long)tiles * chunk) / chunks);
@@ -871,6 +1186,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
             for (int t = 0; t < nt; ++t) {
                 const float4* tq = lds + (2 * t) * MURB_TILE_F4;
                 const float4* tv = tq + MURB_TILE_F4;
+                if constexpr (NN) {
+                    int w = who, self_tile[R];
+                    asm volatile("" : "+v"(w));   // read out here, in every tile
+#pragma unroll
+                    for (int r = 0; r < R; ++r) self_tile[r] = __builtin_amdgcn_readlane(w, r) / MURB_TILE_BODIES;
+                    const bool masked = murb_nn_tile_masked<R>(vs + t, self_tile, __builtin_amdgcn_readlane(w, R));   // wave-uniform
+                    murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                    continue;
+                }
 #pragma unroll
                 for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
                     const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
@@ -891,6 +1215,22 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
         int fold_lane = threadIdx.x & 63;
         asm volatile("" : "+v"(zero), "+v"(fold_lane));
         float oa[3] = {zero, zero, zero}, oj[3] = {zero, zero, zero};
+        float nn_a = zero, nn_j = zero;   // the rows' fourth floats
+        if constexpr (NN) {
+            int w = who, self[R], self_tile[R];
+            const float4* rec_pred = a.rec_pred;
+            asm volatile("" : "+v"(w), "+s"(rec_pred));   // no address made from the pointer in front of the unit loop
+#pragma unroll
+            for (int r = 0; r < R; ++r) { self[r] = __builtin_amdgcn_readlane(w, r); self_tile[r] = self[r] / MURB_TILE_BODIES; }
+            const int count = __builtin_amdgcn_readlane(w, R);
+            for (int tile = vt0; tile < vt1; ++tile)
+                if (murb_nn_tile_masked<R>(tile, self_tile, count))
+                    murb_nn_masked_tile<R>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, mn, st, self, count);
+            unsigned int nn_r2, nn_idx;
+            murb_nn_finish<R>(rec_pred, fold_lane, xi, yi, zi, soft2, mn, st, self, count, nn_r2, nn_idx);
+            nn_a = __builtin_bit_cast(float, nn_r2);
+            nn_j = __builtin_bit_cast(float, nn_idx);
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const float sx = murb_wave_sum(ax[r].x + ax[r].y), sy = murb_wave_sum(ay[r].x + ay[r].y), sz = murb_wave_sum(az[r].x + az[r].y);
@@ -900,13 +1240,26 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
         if (fold_lane < R) {
             const MurbBlockCtlK end = murb_block_ctl_now(ctl);
             const unsigned long at = (unsigned long)chunk * end->stride + (unsigned long)i_slot + fold_lane;   // < groups * chunks * 16 <= row_cap
-            end->part_a[at] = make_float4(oa[0], oa[1], oa[2], zero);
-            end->part_j[at] = make_float4(oj[0], oj[1], oj[2], zero);
+            end->part_a[at] = make_float4(oa[0], oa[1], oa[2], nn_a);
+            end->part_j[at] = make_float4(oj[0], oj[1], oj[2], nn_j);
         }
     }
 #else
     (void)a; (void)ctl;
 #endif
+}
+
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5))) void murb_force_jerk_block_kernel(const MurbBlockSweepArgs a, const MurbBlockCtl* ctl)
+{
+    murb_force_jerk_block_sweep<R, WAVES, STAGE>(a, ctl);
+}
+
+// The nearest-neighbour form.  104+ vector registers: 4 waves per SIMD, so the host launches 4 workgroups per CU.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_nn_active_sweep_kernel(const MurbBlockNNSweepArgs a, const MurbBlockCtl* ctl)
+{
+    murb_force_jerk_block_sweep<R, WAVES, STAGE, true, MurbBlockNNSweepArgs>(a, ctl);
 }
 
 // launch 5: one thread per list entry.  The grid covers `count` entries; threads behind the list's end only take part in the
@@ -928,11 +1281,17 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
         const int s = a.list[at];
         const int k = a.levels[s];
         float a0[3], j0[3], a1[3] = {0.f, 0.f, 0.f}, j1[3] = {0.f, 0.f, 0.f};
+        unsigned int nn_r2 = MURB_F32_INF_BITS, nn_idx = MURB_NN_NONE;
         for (int p = 0; p < chunks; ++p) {
             const float4 u = a.part_a[(unsigned long)p * stride + at];
             const float4 w = a.part_j[(unsigned long)p * stride + at];
             a1[0] += u.x; a1[1] += u.y; a1[2] += u.z;
             j1[0] += w.x; j1[1] += w.y; j1[2] += w.z;
+            murb_nn_fold_row(nn_r2, nn_idx, u, w);
+        }
+        if (a.nn_idx) {
+            murb_nn_store(a.nn_idx, a.nn_r2, s, nn_r2, nn_idx);
+            murb_enc_test(&ctl->enc_hits, a.enc, ctl->enc_thr, s, nn_r2, nn_idx);
         }
         const float dt32 = murb_block_dt(dt_max, k);
         const double dt = (double)dt32, h2 = dt * 0.5, c12 = dt * dt / 12.0;
@@ -982,7 +1341,7 @@ __global__ void murb_block_book_kernel(MurbBlockCtl* c)
     }
     c->t_next = ~0u;
     c->n_act = 0u;
-    if (c->blocks_left == 0u || c->steps >= c->max_steps) c->done = 1;
+    if (c->blocks_left == 0u || c->steps >= c->max_steps || c->enc_hits) c->done = 1;
 }
 
 #endif

@@ -789,7 +789,18 @@ int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
         RC_TRY(shard_alloc(sh, sh.herm_part, (size_t)2 * rows * c->in.slots * sizeof(float4), sh.compute));
         sh.herm_rows = rows;
     }
+    if (c->nearest) {
+        RC_TRY(shard_alloc(sh, sh.nn_idx, c->in.slots * sizeof(int), sh.compute));
+        RC_TRY(shard_alloc(sh, sh.nn_r2, c->in.slots * sizeof(float), sh.compute));
+        RC_TRY(shard_alloc(sh, sh.enc, sizeof(MurbEncList), sh.compute));
+    }
     return 0;
+}
+
+// radius^2 + soft^2 as the kernels compare it with r2; -1 (no r2 is that small): no encounter stop
+inline float encounter_threshold(const murbhip_ctx* c)
+{
+    return c->enc_radius > 0.f ? (float)((double)c->enc_radius * (double)c->enc_radius + (double)c->soft2) : -1.f;
 }
 
 MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, float dt, int update_state)
@@ -807,6 +818,7 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
     a.stride = (unsigned int)c->in.slots;
     a.dt = dt;
     a.update_state = update_state;
+    if (c->nearest) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
     return a;
 }
 
@@ -814,7 +826,8 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
 // (enqueue_hermite_adaptive), which records no timing span.
 int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts, MurbEvolveCtl* ctl = nullptr)
 {
-    MurbJerkArgs a{};
+    MurbNNJerkArgs a{};   // the plain sweeps take its base
+    a.count = (int)sh.count;
     a.rec = rec;
     a.vel = vel;
     a.part_a = sh.herm_part;
@@ -829,14 +842,23 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
         int rc = 0;
         const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
         RC_TRY(rc);
-        hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a);
+        if (c->nearest)
+            hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                               (const MurbEvolveCtl*)nullptr);
+        else
+            hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute,
+                               (const MurbJerkArgs&)a);
         RC_TRY(hip_rc(hipGetLastError()));
         RC_TRY(span_end(sh, sp, sh.compute));
         note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
         return 0;
     }
-    hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute,
-                       a, ctl);
+    if (c->nearest)
+        hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                           (const MurbEvolveCtl*)ctl);
+    else
+        hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0,
+                           sh.compute, (const MurbJerkArgs&)a, (const MurbEvolveCtl*)ctl);
     return hip_rc(hipGetLastError());
 }
 
@@ -958,6 +980,7 @@ MurbBlockArgs block_args(const murbhip_ctx* c, const Shard& sh)
     a.ticks = sh.blk_ticks;
     a.levels = sh.blk_levels;
     a.list = sh.blk_list;
+    if (c->nearest) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
     a.count = (int)sh.count;
     a.stride = (unsigned int)c->in.slots;
     a.soft2 = c->soft2;
@@ -971,9 +994,18 @@ int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
     hipLaunchKernelGGL(murb_block_min_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_predict_kernel, dim3(per_pair), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_plan_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
-    const MurbBlockSweepArgs sa{a.rec_pred, a.vel_pred, a.soft2};
-    hipLaunchKernelGGL((murb_force_jerk_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)block_grid(c)),
-                       dim3(kHermiteWaves * 64), 0, sh.compute, sa, sh.blk_ctl);
+    if (c->nearest) {   // 4 waves per SIMD: 4 resident workgroups per CU
+        MurbBlockNNSweepArgs na{};
+        na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
+        na.grid = block_grid(c) / 5 * 4;
+        na.ctl = sh.blk_ctl;
+        hipLaunchKernelGGL((murb_nn_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
+                           dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
+    } else {
+        const MurbBlockSweepArgs sa{a.rec_pred, a.vel_pred, a.soft2};
+        hipLaunchKernelGGL((murb_force_jerk_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)block_grid(c)),
+                           dim3(kHermiteWaves * 64), 0, sh.compute, sa, sh.blk_ctl);
+    }
     hipLaunchKernelGGL(murb_block_correct_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_book_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
     return hip_rc(hipGetLastError());
@@ -1303,6 +1335,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.herm_rec, sh.herm_vel, sh.herm_a0, sh.herm_j0, sh.herm_part, sh.herm_ctl);
         if (sh.herm_ctl_host) (void)hipHostFree(sh.herm_ctl_host);
         release(sh.blk_ctl, sh.blk_ticks, sh.blk_levels, sh.blk_list, sh.blk_rec, sh.blk_vel, sh.blk_part);
+        release(sh.nn_idx, sh.nn_r2, sh.enc);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
         free_sym_set(sh, sh.sym_main); free_sym_set(sh, sh.sym_tri);
@@ -1566,6 +1599,55 @@ int murbhip_download_jerk(murbhip_ctx* c, float* jx, float* jy, float* jz)
     return 0;
 }
 
+int murbhip_download_nearest(murbhip_ctx* c, int* idx, float* r2)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->uploaded || !c->nearest || !c->herm_current) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    if (idx) HIP_TRY(hipMemcpy(idx, sh.nn_idx, c->in.n * sizeof(int), hipMemcpyDeviceToHost));
+    if (r2) HIP_TRY(hipMemcpy(r2, sh.nn_r2, c->in.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int murbhip_set_encounter(murbhip_ctx* c, float radius)
+{
+    if (!c || !std::isfinite(radius) || radius < 0.f) return MURBHIP_E_INVALID;
+    if (radius > 0.f && !c->nearest) return MURBHIP_E_STATE;
+    c->enc_radius = radius;
+    return 0;
+}
+
+int murbhip_encounters(murbhip_ctx* c, int* i, int* j, float* r2, unsigned long capacity, unsigned long* count, double* time)
+{
+    if (!c || !count) return MURBHIP_E_INVALID;
+    if (!c->uploaded) return MURBHIP_E_STATE;
+    *count = c->enc_count;
+    if (time) *time = c->enc_time;
+    const unsigned long kept = std::min<unsigned long>(c->enc_count, MURB_ENC_CAP);
+    if ((!i && !j && !r2) || kept == 0) return 0;
+    if (capacity < kept) return MURBHIP_E_INVALID;
+    Shard& sh = c->shards[0];
+    if (!sh.enc) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    HIP_TRY(hipSetDevice(sh.device));
+    std::vector<int> li(kept), lj(kept);
+    std::vector<float> lr(kept);
+    HIP_TRY(hipMemcpy(li.data(), sh.enc->i, kept * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lj.data(), sh.enc->j, kept * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lr.data(), sh.enc->r2, kept * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<unsigned long> order(kept);   // the device's order is that of its atomics: sort by i
+    for (unsigned long k = 0; k < kept; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](unsigned long a, unsigned long b) { return li[a] < li[b]; });
+    for (unsigned long k = 0; k < kept; ++k) {
+        if (i) i[k] = li[order[k]];
+        if (j) j[k] = lj[order[k]];
+        if (r2) r2[k] = lr[order[k]];
+    }
+    return 0;
+}
+
 int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start, float dt_min, float dt_max,
                    unsigned long max_steps, double* out5)
 {
@@ -1582,8 +1664,9 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
     const unsigned pairs = (unsigned)(c->in.slots / 2);
     const int fresh = c->herm_proposal ? 0 : 1;
     hipLaunchKernelGGL(murb_evolve_begin_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl, duration, eta, dt_min, dt_max,
-                       (unsigned long long)max_steps, fresh);
+                       (unsigned long long)max_steps, fresh, encounter_threshold(c));
     RC_TRY(hip_rc(hipGetLastError()));
+    c->enc_count = 0;
     if (fresh) {
         const MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 0);
         hipLaunchKernelGGL(murb_evolve_first_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl, eta_start);
@@ -1625,6 +1708,8 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
         batch = 0;
     }
     c->evolve_steps = (unsigned long)head.steps;
+    c->enc_count = head.enc_hits;
+    c->enc_time = head.t;
     out5[0] = head.t;
     out5[1] = (double)head.steps;
     out5[2] = (double)head.used_min;
@@ -1667,8 +1752,9 @@ int murbhip_evolve_block(murbhip_ctx* c, float dt_max, unsigned long blocks, dou
     const MurbBlockArgs a = block_args(c, sh);
     hipLaunchKernelGGL(murb_block_begin_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl, a, dt_max, kmax, eta, (unsigned int)blocks,
                        (unsigned long long)max_steps, block_units(c), (int)(c->in.slots / MURB_TILE_BODIES),
-                       (unsigned int)std::min<size_t>(sh.blk_rows, 0xffffffffu), resume ? 1 : 0);
+                       (unsigned int)std::min<size_t>(sh.blk_rows, 0xffffffffu), resume ? 1 : 0, encounter_threshold(c));
     RC_TRY(hip_rc(hipGetLastError()));
+    c->enc_count = 0;
     const bool retained = c->blk_have_levels == 1 && dt_max == c->blk_dt_max && kmax == c->blk_kmax;
     const bool given = c->blk_have_levels == 2 && kmax == c->blk_kmax;
     if (!resume && !retained && !given) {
@@ -1708,6 +1794,8 @@ int murbhip_evolve_block(murbhip_ctx* c, float dt_max, unsigned long blocks, dou
     c->blk_info[1] = (double)head.body_steps;
     c->blk_info[2] = (double)head.clamped;
     c->blk_info[3] = (double)head.max_act;
+    c->enc_count = head.enc_hits;
+    c->enc_time = (double)head.ticks_done * head.tick_sec;
     out8[0] = (double)head.ticks_done * head.tick_sec;
     out8[1] = (double)head.steps;
     out8[2] = (double)head.body_steps;
@@ -2019,11 +2107,21 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
         if (value == 2 && (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
+        if (value != 2 && c->nearest) return MURBHIP_E_STATE;   // "nearest" belongs to the Hermite sweeps: switch it off first
         c->integrator = (int)value;
     }
     else if (k == "evolve_batch") {
         if (value < 0 || value > kEvolveBatch) return MURBHIP_E_INVALID;
         c->evolve_batch = (int)value;
+    }
+    else if (k == "nearest") {
+        if (value != 0 && value != 1) return MURBHIP_E_INVALID;
+        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+        if (!value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
+        if ((int)value != c->nearest) {
+            c->nearest = (int)value;
+            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its neighbours beside it
+        }
     }
     else if (k == "block_units") {
         if (value < 0 || value > kBlockMaxUnits) return MURBHIP_E_INVALID;
@@ -2085,6 +2183,8 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "hermite_parts") *value = hermite_parts(c->in);   // j chunks of the acceleration + jerk sweep
     else if (k == "block_units") *value = block_units(c);
     else if (k == "block_grid") *value = block_grid(c);
+    else if (k == "nearest") *value = c->nearest;
+    else if (k == "encounter_count") *value = (double)c->enc_count;
     else if (k == "block_steps") *value = c->blk_info[0];
     else if (k == "block_body_steps") *value = c->blk_info[1];
     else if (k == "block_clamped") *value = c->blk_info[2];

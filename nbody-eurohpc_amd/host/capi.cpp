@@ -148,6 +148,30 @@ int murbhost_sim_block_counts(void *p, double *out3)
     out3[2] = (double)t->getClampedSteps();
     return 0;
 }
+// hip+hermite+adaptive / hip+hermite+block: SimulationNBodyHIPTracking::setEncounterRadius.  0, or -1 for another simulation.
+int murbhost_sim_set_encounter(void *p, float radius)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    return t && t->setEncounterRadius(radius) ? 0 : -1;
+}
+// ... the pairs of the substep that ended the last iteration (murbhip_encounters' arguments; NULL arrays ask for *count and
+// *time alone).  0, -1 for another simulation, -2 when capacity is smaller than the number of pairs kept.
+int murbhost_sim_encounters(void *p, int *i, int *j, float *r2, unsigned long capacity, unsigned long *count, double *time)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->isAdaptive()) return -1;
+    *count = t->getEncounterCount();
+    if (time) *time = t->getEncounterTime();
+    const auto &e = t->getEncounters();
+    if ((!i && !j && !r2) || e.empty()) return 0;
+    if (capacity < e.size()) return -2;
+    for (size_t k = 0; k < e.size(); ++k) {
+        if (i) i[k] = e[k].i;
+        if (j) j[k] = e[k].j;
+        if (r2) r2[k] = e[k].r2;
+    }
+    return 0;
+}
 int murbhost_sim_history_csv(void *p, const char *path)
 {
     try {

@@ -32,6 +32,29 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
     history->setDensityCenterAt(currentIteration, {(Q)(mom[6] / mass), (Q)(mom[7] / mass), (Q)(mom[8] / mass)});
 }
 
+template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setEncounterRadius(const T radius)
+{
+    if (!adaptive) return false;
+    murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
+    if (radius > 0) murbhipCheck(murbhip_set_option(ctx, "nearest", 1), "murbhip_set_option(nearest)");
+    murbhipCheck(murbhip_set_encounter(ctx, (float)radius), "murbhip_set_encounter");
+    encounterRadius = radius;
+    return true;
+}
+
+template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::readEncounters()
+{
+    murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
+    encounters.clear();
+    murbhipCheck(murbhip_encounters(ctx, nullptr, nullptr, nullptr, 0, &encounterCount, &encounterTime), "murbhip_encounters");
+    const unsigned long kept = std::min(encounterCount, 4096ul);
+    if (!kept) return;
+    std::vector<int> i(kept), j(kept);
+    std::vector<float> r2(kept);
+    murbhipCheck(murbhip_encounters(ctx, i.data(), j.data(), r2.data(), kept, &encounterCount, &encounterTime), "murbhip_encounters");
+    for (unsigned long k = 0; k < kept; ++k) encounters.push_back({i[k], j[k], r2[k]});
+}
+
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::computeOneIteration()
 {
     computeMetrics();
@@ -45,6 +68,7 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
         substeps += (unsigned long)out[1];
         bodySteps += (unsigned long)out[2];
         clampedSteps += (unsigned long)out[5];
+        if (encounterRadius > 0) readEncounters();
     } else if (adaptive) {   // exactly dt of model time, in the substeps the criterion chooses; returns synchronised
         double out[5];
         this->hipBodiesPtr->invalidateDataSoA();
@@ -53,6 +77,7 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
         dtSmallest = substeps ? std::min(dtSmallest, out[2]) : out[2];
         dtLargest = std::max(dtLargest, out[3]);
         substeps += (unsigned long)out[1];
+        if (encounterRadius > 0) readEncounters();
     } else SimulationNBodyHIP<T>::computeOneIteration();
     currentIteration++;
 }

@@ -20,6 +20,12 @@
 #include "implem/SimulationNBodyHIP.hpp"
 
 template <typename T, typename Q = double> class SimulationNBodyHIPTracking : public SimulationNBodyHIP<T> {
+  public:
+    struct Encounter {
+        int i, j;      // body and its nearest neighbour
+        float r2;      // the sweep's |q_j - q_i|^2 + soft^2 of the pair
+    };
+
   protected:
     std::shared_ptr<SimulationHistory<Q>> history;
     int currentIteration = 0;
@@ -30,6 +36,10 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     double eta = 0.02;                // its accuracy parameter (--eta); the first step of all uses eta_start = 0.01
     unsigned long substeps = 0;       // substeps of all iterations so far
     double dtSmallest = 0, dtLargest = 0;   // ... and the range of their sizes
+    T encounterRadius = 0;            // integrators 3 and 4: an iteration ends behind the substep in which two bodies come this close
+    std::vector<Encounter> encounters;   // the pairs (i, nearest of i) of that substep, sorted by i (the device keeps 4096)
+    unsigned long encounterCount = 0;    // ... how many there were; 0: the last iteration ran its whole dt
+    double encounterTime = 0;            // ... and the model time that iteration had advanced
 
   public:
     // integrator: murbhip option "integrator" — 0 (false) the reference's update, 1 (true) kick-drift-kick leapfrog,
@@ -43,6 +53,7 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
 
     void computeOneIteration() override;   // metrics of the current state -> history, then one step
     void computeMetrics();                 // fills row `currentIteration` (grows the history if needed)
+    void readEncounters();                 // after an evolve call: count, time and pairs of the substep that ended it
     const std::shared_ptr<SimulationHistory<Q>> getHistory() const { return history; }
     void setEta(const double e) { eta = e; }
     void setKmax(const int k) { kmax = k; }
@@ -53,6 +64,14 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     unsigned long getSubsteps() const { return substeps; }
     double getSmallestDt() const { return dtSmallest; }
     double getLargestDt() const { return dtLargest; }
+    // hip+hermite+adaptive / hip+hermite+block (murbhip_set_encounter; switches the "nearest" option on): an iteration in which a
+    // body that took a substep has its nearest neighbour within `radius` ends behind that substep, short of dt (under block
+    // steps possibly inside a block: the caller then goes on with murbhip_evolve_block or uploads).  0 = off.  false for the
+    // fixed-step integrators.
+    bool setEncounterRadius(const T radius);
+    unsigned long getEncounterCount() const { return encounterCount; }
+    double getEncounterTime() const { return encounterTime; }
+    const std::vector<Encounter> &getEncounters() const { return encounters; }
 };
 
 #endif

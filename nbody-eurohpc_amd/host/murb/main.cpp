@@ -7,6 +7,7 @@
 //
 // A maintainer of the reference adds the HIP path to the real driver with one branch in
 // createImplem() — see INTEGRATION.md; the branch below is that code.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <iomanip>
@@ -43,6 +44,7 @@ bool DeviceInit = false;    // --dinit: generate the initial conditions on the d
 std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+hermite[+adaptive] save their history
 double Eta = 0.02;          // --eta: accuracy parameter of hip+hermite+adaptive's and hip+hermite+block's step criterion
 int Kmax = 12;              // --kmax: hip+hermite+block, the deepest level (steps down to dt 2^-kmax)
+float Renc = 0.f;           // --renc: hip+hermite+adaptive / hip+hermite+block, encounter radius (0 = no encounter stop)
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -90,6 +92,7 @@ static std::vector<Option> optionTable()
         {"-csv", "file", false, "hip+tracking / hip+leapfrog / hip+hermite: save the metrics history as CSV."},
         {"-eta", "accuracy", false, "hip+hermite+adaptive / hip+hermite+block: accuracy parameter of the step criterion (default is 0.02)."},
         {"-kmax", "levels", false, "hip+hermite+block: deepest step level, 0 to 20 (default is 12)."},
+        {"-renc", "length", false, "hip+hermite+adaptive / hip+hermite+block: stop when two bodies come within this distance."},
     };
 }
 
@@ -132,6 +135,13 @@ static void argsReader(int argc, char **argv)
         Kmax = stoi(reader.get_argument("-kmax"));
         if (Kmax < 0 || Kmax > 20) {
             std::cout << "The deepest level --kmax must be between 0 and 20... exiting." << std::endl;
+            exit(-1);
+        }
+    }
+    if (given("-renc")) {
+        Renc = stof(reader.get_argument("-renc"));
+        if (!(Renc > 0.f) || !std::isfinite(Renc)) {
+            std::cout << "The encounter radius --renc must be positive and finite... exiting." << std::endl;
             exit(-1);
         }
     }
@@ -185,6 +195,10 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
         auto *tracking = new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening, integrator.at(ImplTag));
         tracking->setEta(Eta);
         tracking->setKmax(Kmax);
+        if (Renc > 0.f && !tracking->setEncounterRadius(Renc)) {
+            std::cout << "--renc needs hip+hermite+adaptive or hip+hermite+block... exiting." << std::endl;
+            exit(-1);
+        }
         return tracking;
     }
     std::cout << "Implementation '" << ImplTag << "' does not exist... Exiting." << std::endl;
@@ -245,6 +259,18 @@ int main(int argc, char **argv)
                       << std::setw(6) << perfTotal.getFPS(iIte) << " FPS" << gflops.str()
                       << "), physic time: " << strDate(physicTime) << "\r";
             if (iIte % 5 == 0) std::cout << std::flush;
+        }
+        // --renc: an iteration that ended by an encounter is the last one
+        if (const auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu);
+            tracking && Renc > 0.f && tracking->getEncounterCount() > 0) {
+            if (Verbose) std::cout << std::endl;
+            for (const auto &e : tracking->getEncounters())
+                std::cout << "encounter: " << e.i << " " << e.j << " " << std::setprecision(9)
+                          << std::sqrt(std::max(0.0, (double)e.r2 - (double)Softening * (double)Softening)) << " "
+                          << tracking->getEncounterTime() << std::endl;
+            if (History) History->setNumIterations((int)iIte);   // the rows of the iterations that ran
+            iIte++;   // this iteration counts
+            break;
         }
     }
     if (FreeRunning) {

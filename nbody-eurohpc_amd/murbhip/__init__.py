@@ -71,6 +71,10 @@ def lib():
                                            C.POINTER(C.c_double)]
         L.murbhip_block_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
         L.murbhip_block_set_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
+        L.murbhip_download_nearest.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp]
+        L.murbhip_set_encounter.argtypes = [C.c_void_p, C.c_float]
+        L.murbhip_encounters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong, C.POINTER(C.c_ulong),
+                                         C.POINTER(C.c_double)]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -90,6 +94,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_destroy murbhip_upload murbhip_init_bodies murbhip_download_mass murbhip_download_state murbhip_download_acc murbhip_compute_acc "
            "murbhip_compute_acc_jerk murbhip_download_jerk murbhip_evolve murbhip_evolve_dts "
            "murbhip_evolve_block murbhip_block_state murbhip_block_set_levels "
+           "murbhip_download_nearest murbhip_set_encounter murbhip_encounters "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -275,6 +280,30 @@ class Simulation:
             raise ValueError("levels shorter than n")
         _check(lib().murbhip_block_set_levels(self._h, lv.ctypes.data_as(C.POINTER(C.c_int)), kmax), "murbhip_block_set_levels")
 
+    def nearest(self):
+        """(index int32, r2 float32) of every body's nearest neighbour in the remembered evaluation (option "nearest" 1;
+        include/murbhip.h: murbhip_download_nearest)."""
+        idx, r2 = np.zeros(self.n, np.int32), np.zeros(self.n, np.float32)
+        _check(lib().murbhip_download_nearest(self._h, idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r2)), "murbhip_download_nearest")
+        return idx, r2
+
+    def set_encounter(self, radius):
+        """evolve() / evolve_block() end behind a step in which a body that took it has a neighbour within `radius`; 0 = off."""
+        _check(lib().murbhip_set_encounter(self._h, radius), "murbhip_set_encounter")
+
+    def encounters(self):
+        """dict of the step that ended the last evolve call by an encounter: i, j (int32), r2 (float32) sorted by i, the
+        count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
+        count, time = C.c_ulong(), C.c_double()
+        ip = C.POINTER(C.c_int)
+        _check(lib().murbhip_encounters(self._h, None, None, None, 0, C.byref(count), C.byref(time)), "murbhip_encounters")
+        kept = min(count.value, 4096)
+        i, j, r2 = np.zeros(kept, np.int32), np.zeros(kept, np.int32), np.zeros(kept, np.float32)
+        if kept:
+            _check(lib().murbhip_encounters(self._h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(r2), kept, C.byref(count),
+                                            C.byref(time)), "murbhip_encounters")
+        return {"i": i, "j": j, "r2": r2, "count": int(count.value), "time": time.value}
+
     def integrate_host_acc(self, acc, dt):
         a = [_f32(x) for x in acc]
         _check(lib().murbhip_integrate_host_acc(self._h, *[_ptr(x) for x in a], dt), "murbhip_integrate_host_acc")
@@ -369,6 +398,9 @@ def host_lib():
         H.murbhost_sim_substeps.argtypes = [C.c_void_p, _dp]
         H.murbhost_sim_set_block.argtypes = [C.c_void_p, C.c_double, C.c_int]
         H.murbhost_sim_block_counts.argtypes = [C.c_void_p, _dp]
+        H.murbhost_sim_set_encounter.argtypes = [C.c_void_p, C.c_float]
+        H.murbhost_sim_encounters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
+                                              C.POINTER(C.c_ulong), _dp]
         _host = H
     return _host
 
@@ -407,12 +439,13 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False, integrator=None, eta=0.02, kmax=12):
+                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
         driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
         `hip+hermite+block`, option 2 driven by murbhip_evolve_block: an iteration is one block of dt, every body in steps of
-        its own size dt 2^-k, k <= kmax, with accuracy parameter eta)."""
+        its own size dt 2^-k, k <= kmax, with accuracy parameter eta).  encounter=R (integrator 3 or 4): an iteration ends
+        behind the substep in which a body has its nearest neighbour within R; encounters() then has the pairs."""
         if integrator is None:
             integrator = int(bool(leapfrog))
         arr = (C.c_int * len(devices))(*devices)
@@ -425,6 +458,23 @@ class HostSim:
         self.n = int(self.H.murbhost_sim_n(self.h))
         if integrator == 4:
             self.H.murbhost_sim_set_block(self.h, eta, kmax)
+        if encounter:
+            if self.H.murbhost_sim_set_encounter(self.h, encounter) != 0:
+                raise ValueError("encounter= needs integrator 3 or 4")
+
+    def encounters(self):
+        """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
+        count 0 when it ran its whole dt); None for the fixed-step plugins."""
+        count, time = C.c_ulong(), C.c_double()
+        ip = C.POINTER(C.c_int)
+        if self.H.murbhost_sim_encounters(self.h, None, None, None, 0, C.byref(count), C.byref(time)) != 0:
+            return None
+        kept = min(count.value, 4096)
+        i, j, r2 = np.zeros(kept, np.int32), np.zeros(kept, np.int32), np.zeros(kept, np.float32)
+        if kept:
+            self.H.murbhost_sim_encounters(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(r2), kept, C.byref(count),
+                                           C.byref(time))
+        return {"i": i, "j": j, "r2": r2, "count": int(count.value), "time": time.value}
 
     def block_counts(self):
         """integrator=4: (block steps so far, body-steps, clamped steps); None for the other plugins."""

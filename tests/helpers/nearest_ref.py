@@ -1,0 +1,102 @@
+"""numpy restatement of the nearest-neighbour search beside the Hermite sweeps (option "nearest") and of the encounter
+threshold, written from the text of include/murbhip.h, not from the device code.
+
+Per real body i the nearest other real body j != i (massless ones included, never the body itself, never the zero-mass
+padding slots behind the n bodies), by the lexicographic minimum of (r2, index), r2 = |q_j - q_i|^2 + soft^2.  A lone body has
+index -1 and r2 = +inf."""
+import numpy as np
+
+TILE = 512   # body slots per layout tile: the unit in which the device cuts the j range into chunks
+
+
+def nearest(q, soft2, n=None, exact=False):
+    """Brute force over the first n bodies of q (3, >= n).
+    exact=True: q holds integers (a lattice), d2 is formed in int64 and r2 = float32(d2 + soft2), which is exact while
+    d2 + soft2 needs no more than 24 bits: returns (index int32, r2 float32), the lowest index among equal r2.
+    exact=False: fp64 arithmetic on the given values: returns (r2 fp64 minimum per body, candidates (n, n) bool): every j whose
+    d2 + soft2 lies within a relative 1e-6 of the minimum."""
+    q = np.asarray(q)
+    n = q.shape[1] if n is None else int(n)
+    q = q[:, :n]
+    if exact:
+        qi = q.astype(np.int64)
+        d = qi[:, None, :] - qi[:, :, None]
+        d2 = (d * d).sum(0)
+        r2 = (d2.astype(np.float64) + float(soft2)).astype(np.float32)
+        assert np.array_equal(r2.astype(np.float64), d2.astype(np.float64) + float(soft2)), "r2 is not exact in fp32"
+        r2[np.arange(n), np.arange(n)] = np.inf
+        if n == 1:
+            return np.array([-1], np.int32), np.array([np.inf], np.float32)
+        idx = r2.argmin(1).astype(np.int32)      # argmin returns the first (lowest) index of the minimum
+        return idx, r2[np.arange(n), idx]
+    q64 = q.astype(np.float64)
+    d = q64[:, None, :] - q64[:, :, None]
+    r2 = (d * d).sum(0) + float(soft2)
+    r2[np.arange(n), np.arange(n)] = np.inf
+    best = r2.min(1) if n > 1 else np.full(n, np.inf)
+    return best, r2 <= best[:, None] * (1.0 + 1e-6)
+
+
+def lex_min(r2_a, idx_a, r2_b, idx_b):
+    """Elementwise lexicographic minimum of (r2 as fp32, index); index -1 (no candidate, r2 = +inf) loses to everything."""
+    key_a = np.where(idx_a < 0, np.iinfo(np.int64).max, idx_a.astype(np.int64))
+    key_b = np.where(idx_b < 0, np.iinfo(np.int64).max, idx_b.astype(np.int64))
+    take_b = (r2_b < r2_a) | ((r2_b == r2_a) & (key_b < key_a))
+    return np.where(take_b, r2_b, r2_a), np.where(take_b, idx_b, idx_a)
+
+
+def chunked(q, soft2, n, tiles, chunks):
+    """The same search with the j range cut like the device cuts it: `tiles` layout tiles of 512 slots (slots >= n are
+    padding, no candidates) into `chunks` chunks [tiles * c // chunks, tiles * (c + 1) // chunks), each chunk's own
+    lexicographic minimum, then the fold over the chunks in index order.  Lattice input (exact r2)."""
+    qi = np.asarray(q)[:, :n].astype(np.int64)
+    best_r2 = np.full(n, np.inf, np.float32)
+    best_idx = np.full(n, -1, np.int32)
+    for c in range(chunks):
+        lo, hi = TILE * (tiles * c // chunks), min(TILE * (tiles * (c + 1) // chunks), n)
+        if hi <= lo:
+            continue
+        d = qi[:, None, lo:hi] - qi[:, :, None]
+        r2 = ((d * d).sum(0).astype(np.float64) + float(soft2)).astype(np.float32)
+        own = np.arange(n)
+        inside = (own >= lo) & (own < hi)
+        r2[own[inside], own[inside] - lo] = np.inf
+        k = r2.argmin(1)
+        r2_c = r2[own, k]
+        idx_c = np.where(np.isinf(r2_c), -1, k + lo).astype(np.int32)
+        best_r2, best_idx = lex_min(best_r2, best_idx, r2_c, idx_c)
+    return best_idx, best_r2
+
+
+def threshold(radius, soft2):
+    """thr = (float)((double)radius * radius + (double)soft2): a body with r2 <= thr has met its neighbour."""
+    return np.float32(float(np.float32(radius)) * float(np.float32(radius)) + float(np.float32(soft2)))
+
+
+def lattice(n, seed=1):
+    """(state dict, soft): n bodies on integer coordinates in [0, 1024]^3 with softening 0.5, so that every r2 is exact in fp32.
+      body 0        at the origin, where the padding slots lie; every other body is at least 300 away in each coordinate
+      bodies 5, 400 on the same point: a spacing below the softening, r2 = soft^2 like the body's own
+      body 7        massless, and the nearest of body 8 (one unit away)
+      body 20       has bodies 21 and 300 at the same distance 2: the lowest index wins
+      body 30       has bodies 100 and n - 1 at the same distance 3, in different layout tiles (n >= 513)
+    (the special bodies exist from n = 513 up; n = 2: the origin and one far body).  Velocities and masses are arbitrary."""
+    rng = np.random.default_rng(seed)
+    q = rng.integers(300, 1025, size=(3, n)).astype(np.int64)
+    q[:, 0] = 0
+    if n >= 513:
+        q[:, 400] = q[:, 5]
+        q[:, 8] = q[:, 7] + np.array([1, 0, 0]) * (1 if q[0, 7] < 1024 else -1)
+        q[:, 20] = (500, 600, 700)
+        q[:, 21] = (502, 600, 700)
+        q[:, 300] = (498, 600, 700)
+        q[:, 30] = (700, 400, 900)
+        q[:, 100] = (700, 403, 900)
+        q[:, n - 1] = (700, 400, 897)
+    v = rng.standard_normal((3, n)).astype(np.float32)
+    m = rng.uniform(1e20, 2e20, n).astype(np.float32)
+    if n >= 513:
+        m[7] = 0.0
+    s = {"qx": q[0].astype(np.float32), "qy": q[1].astype(np.float32), "qz": q[2].astype(np.float32),
+         "vx": v[0], "vy": v[1], "vz": v[2], "m": m}
+    return s, np.float32(0.5)

@@ -1,0 +1,126 @@
+"""CPU: nearest neighbours from the Hermite sweeps (option "nearest") and the encounter stop.  The library, the binding and the
+header carry the entry points; the numpy restatement (tests/helpers/nearest_ref.py, written from include/murbhip.h) gives the
+same answer however the j range is cut; the two nearest-neighbour kernels of a fresh gfx950 build use no scratch, spill
+nothing, keep the plain sweep's packed arithmetic, and leave the plain kernels' registers as they were."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import nearest_ref as N   # noqa: E402
+
+E_INVALID = -2000
+
+
+@pytest.fixture(scope="module")
+def mh():
+    import murbhip
+    murbhip.lib()
+    return murbhip
+
+
+def test_nearest_entry_points_are_exported(mh):
+    header = open(os.path.join(ROOT, "include", "murbhip.h")).read()
+    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.normpath(mh.LIB_PATH)], capture_output=True, text=True)
+    exported = set(re.findall(r" T (murbhip_[a-z_0-9]+)", nm.stdout))
+    for name in ("murbhip_download_nearest", "murbhip_set_encounter", "murbhip_encounters"):
+        assert name in exported, name + " not exported by libmurbhip.so"
+        assert name in mh.EXPORTS, name + " missing from murbhip.EXPORTS"
+        assert re.search(r"\bint\s+" + name + r"\s*\(", header), name + " not declared in include/murbhip.h"
+        assert hasattr(mh.lib(), name)
+    assert mh.lib().murbhip_version() == 103
+    for method in ("nearest", "set_encounter", "encounters"):
+        assert callable(getattr(mh.Simulation, method))
+    assert callable(mh.HostSim.encounters)
+    for name in ("murbhost_sim_set_encounter", "murbhost_sim_encounters"):
+        assert hasattr(mh.host_lib(), name)
+    # the argument checks that need no device: no context
+    count, time = C.c_ulong(), C.c_double()
+    assert mh.lib().murbhip_download_nearest(None, None, None) == E_INVALID
+    assert mh.lib().murbhip_set_encounter(None, 1.0) == E_INVALID
+    assert mh.lib().murbhip_encounters(None, None, None, None, 0, C.byref(count), C.byref(time)) == E_INVALID
+
+
+@pytest.mark.parametrize("n", [2, 513, 2049, 3072])
+def test_chunked_fold_equals_brute_force(n):
+    """6 layout tiles cut into 1, 3 and 6 chunks (and the device's own tile count): the lexicographic fold over the chunks
+    is the brute-force answer, on a lattice with deliberate ties (equal distances inside a tile and across tiles, two bodies
+    on one point, a body on the origin where the padding lies)."""
+    s, soft = N.lattice(n)
+    q = np.stack([s[k] for k in ("qx", "qy", "qz")])
+    idx, r2 = N.nearest(q, 0.25, exact=True)
+    assert (idx != np.arange(n)).all() and (idx >= 0).all() and (idx < n).all()
+    if n >= 513:
+        assert idx[8] == 7 and idx[20] == 21 and idx[30] == 100 and idx[5] == 400 and idx[400] == 5
+        assert r2[5] == np.float32(0.25) and r2[20] == np.float32(4.25) and r2[30] == np.float32(9.25)
+    for chunks in (1, 3, 6):
+        got_idx, got_r2 = N.chunked(q, 0.25, n, 6, chunks)
+        assert np.array_equal(got_idx, idx) and np.array_equal(got_r2.view(np.uint32), r2.view(np.uint32)), chunks
+    # the fp64 form agrees on a lattice: the exact index is a candidate, the minimum is the exact r2
+    best, cand = N.nearest(q, 0.25)
+    assert cand[np.arange(n), idx].all() and np.array_equal(best, r2.astype(np.float64))
+
+
+def test_lone_body_and_threshold():
+    idx, r2 = N.nearest(np.zeros((3, 1)), 0.25, exact=True)
+    assert idx[0] == -1 and np.isinf(r2[0])
+    idx, r2 = N.chunked(np.zeros((3, 1)), 0.25, 1, 2, 2)
+    assert idx[0] == -1 and np.isinf(r2[0])
+    assert N.threshold(3.0, 0.25) == np.float32(9.25)
+    r = float(np.float32(3e10))      # the radius is an fp32 argument; the square and the sum are fp64, one rounding at the end
+    assert N.threshold(3e10, np.float32(1e6) ** 2) == np.float32(r * r + float(np.float32(1e6) ** 2))
+    a, b = N.lex_min(np.float32([1, 2, 2]), np.int32([5, 5, 9]), np.float32([1, 3, 2]), np.int32([3, 1, 4]))
+    assert a.tolist() == [1, 2, 2] and b.tolist() == [3, 5, 4]
+
+
+PARENT_VGPRS = {"murb_force_jerk_kernel": 96, "murb_force_jerk_adaptive_kernel": 96, "murb_force_jerk_block_kernel": 95}
+
+
+def test_nearest_kernels_use_no_scratch():
+    """Code-object metadata of a fresh gfx950 build (the method of test_hermite_block_host.py): both nearest-neighbour sweeps are
+    there with 0 bytes of scratch and 0 spilled registers, their packed fp32 instructions, reciprocal square roots and LDS
+    reads are exactly the plain sweep's, and they fit 4 waves per SIMD (at most 128 vector registers; DESIGN.md 4.9 records
+    that decision and what it costs).  The plain kernels keep the register counts they had before the option existed."""
+    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    if not hipcc:
+        pytest.skip("hipcc is not installed: no code object to inspect")
+    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, "murbhip.s")
+        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
+                       check=True, stderr=subprocess.DEVNULL)
+        text = open(asm).read()
+    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_nn_|murb_force_jerk_)\S*)\n(.*?)\.wavefront_size", text, re.S))
+    fields = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")
+    seen = {}
+    for name, meta in kernels.items():
+        num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1)) for f in fields}
+        print(name, num)
+        assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
+        short = re.search(r"(murb_[a-z_]+_kernel)", name).group(1)
+        seen[short] = num["vgpr_count"]
+    for want in ("murb_nn_sweep_kernel", "murb_nn_active_sweep_kernel"):
+        assert want in seen, want + " missing from the code object"
+        assert seen[want] <= 128, want + " no longer fits 4 waves per SIMD"
+    for name, vgprs in PARENT_VGPRS.items():
+        assert seen[name] == vgprs, f"{name}: {seen[name]} vector registers, {vgprs} before the option existed"
+    assert sum("DESIGN" in f for f in os.listdir(ROOT)) and "4 waves per SIMD" in open(os.path.join(ROOT, "DESIGN.md")).read()
+
+    def packed(kernel):
+        body = text[text.index(kernel + ":"):]
+        body = body[:body.index(".Lfunc_end")]
+        return sorted(re.findall(r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b", body, re.M))
+
+    plain = packed(next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M)))
+    assert len(plain) > 100
+    for want in ("murb_nn_sweep_kernel", "murb_nn_active_sweep_kernel"):
+        assert packed(next(k for k in re.findall(r"^(_Z\w*" + want + r"\w*):", text, re.M))) == plain, want

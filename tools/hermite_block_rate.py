@@ -10,9 +10,10 @@ Host clock around calls that end in a device sync, K block steps a call in batch
 batch: one block step with "evolve_batch" 64 (63 x 6 launches find the done flag set) against "evolve_batch" 1.
 
     python tools/hermite_block_rate.py [--sizes 30000,200000] [--active 1,16,256,4096,0] [--units 0,256,640,2560,5120]
-                                       [--rounds 3] [--seconds 0.1]
+                                       [--rounds 3] [--seconds 0.1] [--nearest]
 
-(active 0 = all bodies, units 0 = the default.)  Prints per size a table of median microseconds per block step."""
+(active 0 = all bodies, units 0 = the default.  --nearest: every cell is timed twice in every round, with option "nearest" 0 and
+1, and a second table has the ratio 1 / 0.)  Prints per size a table of median microseconds per block step."""
 import argparse
 import os
 import statistics
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--units", default="0,256,640,2560,5120")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=0.1, help="length of one timed window (sets K per case)")
+    ap.add_argument("--nearest", action="store_true", help='also time every cell with option "nearest" 1')
     args = ap.parse_args()
     assert murbhip.device_count() > 0, "needs an MI355X: there is nothing to time without one"
     units = [int(x) for x in args.units.split(",")]
@@ -87,13 +89,22 @@ def main():
                 k_of[m] = max(64, min(2 ** KMAX - 64, int(args.seconds / t) // 64 * 64))
             k_fixed = max(8, int(args.seconds / fixed(sim, s, 8)))
             times = {(u, m): [] for u in units for m in active}
-            fix = []
+            near = {(u, m): [] for u in units for m in active}
+            fix, fix_near = [], []
             for _ in range(args.rounds):
                 fix.append(fixed(sim, s, k_fixed))
+                if args.nearest:
+                    sim.set_option("nearest", 1)
+                    fix_near.append(fixed(sim, s, k_fixed))
+                    sim.set_option("nearest", 0)
                 for u in units:
                     sim.set_option("block_units", u)
                     for m in active:
                         times[(u, m)].append(block(sim, s, levels[m], k_of[m]))
+                        if args.nearest:
+                            sim.set_option("nearest", 1)
+                            near[(u, m)].append(block(sim, s, levels[m], k_of[m]))
+                            sim.set_option("nearest", 0)
             sim.set_option("block_units", 0)
             tail = [block(sim, s, levels[active[0]], 1, 64) - block(sim, s, levels[active[0]], 1, 1) for _ in range(max(args.rounds, 5))]
         mf = statistics.median(fix)
@@ -102,6 +113,14 @@ def main():
         print("    units \\ active " + "".join(f"{m:>12d}" for m in active))
         for u in units:
             print(f"    {u:>14d} " + "".join(f"{statistics.median(times[(u, m)]) * 1e6:12.1f}" for m in active))
+        if args.nearest:
+            mn = statistics.median(fix_near)
+            print(f"  murbhip_steps with \"nearest\" 1: median {mn * 1e6:.1f} ({mn / mf:.3f} of the plain step)   rounds: "
+                  + ", ".join(f"{x * 1e6:.1f}" for x in fix_near))
+            print("  block step with \"nearest\" 1, median, and its ratio to \"nearest\" 0")
+            for u in units:
+                print(f"    {u:>14d} " + "".join(f"{statistics.median(near[(u, m)]) * 1e6:12.1f}" for m in active))
+                print(f"    {'ratio':>14s} " + "".join(f"{statistics.median(near[(u, m)]) / statistics.median(times[(u, m)]):12.3f}" for m in active))
         full = statistics.median(times[(units[0], active[-1])])
         if active[-1] == n:
             print(f"  block step of all bodies / fixed step = {full / mf:.3f}")
