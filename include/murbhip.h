@@ -155,7 +155,8 @@ int murbhip_upload(murbhip_ctx* ctx, const float* qx, const float* qy, const flo
  * AVX2, 0 = the SSE2 one; -1, default = what this host's libm would pick). */
 int murbhip_init_bodies(murbhip_ctx* ctx, const char* scheme, unsigned long seed);
 
-/* Masses (and, after murbhip_init_bodies, radii; `r` may be NULL) of all n bodies, device -> host: what a host mirror
+/* Masses (and, after murbhip_init_bodies or murbhip_upload_radii, radii; `r` may be NULL; MURBHIP_E_STATE when it is not and no
+ * radii were ever set) of all n bodies, device -> host: what a host mirror
  * needs to complete its dataSoA when the bodies were created on the device (rank mode: own slice only). */
 int murbhip_download_mass(murbhip_ctx* ctx, float* m, float* r);
 
@@ -302,11 +303,52 @@ int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
  *   *count says how many there were (0: the last evolve call ended otherwise); `time` = the model time advanced in that call
  *   when the hit was seen.  The list is cleared at the head of every evolve call.  NULL arrays ask for the count (and time)
  *   alone; MURBHIP_E_INVALID when capacity < min(*count, 4096).
- * Not covered: several shards or ranks; the other integrators and the pair-symmetric force kernel; per-body radii
- * (collisions by r_i + r_j); merging; full neighbour lists. */
+ * Not covered: several shards or ranks; the other integrators and the pair-symmetric force kernel; full neighbour lists
+ * (per-body radii: "contact" below). */
 int murbhip_download_nearest(murbhip_ctx* ctx, int* idx, float* r2);
 int murbhip_set_encounter(murbhip_ctx* ctx, float radius);
 int murbhip_encounters(murbhip_ctx* ctx, int* i, int* j, float* r2, unsigned long capacity, unsigned long* count, double* time);
+
+/* Contacts by the bodies' radii from the Hermite sweeps, and a contact stop.
+ *   Definition.  For real bodies i != j take r2_ij as the sweep's own fp32 value fma(dz,dz, fma(dy,dy, fma(dx,dx, soft2))) and
+ *   soft2 as the fp32 the sweep uses.  Then, each line one fp32 operation:
+ *       s_ij    = R_i + R_j
+ *       e_ij    = r2_ij - soft2
+ *       gap2_ij = fmaf(-s_ij, s_ij, e_ij)
+ *   gap2 is the squared centre distance minus the squared sum of radii; the pair is in contact iff gap2_ij <= 0.
+ *   gap2_ij == gap2_ji bit for bit (r2 is symmetric, the add commutes); a result of -0 cannot arise, so values compare as fp32
+ *   numbers.  Per real body i the sweep keeps (cp_i, gap2_i): the lexicographic minimum of (gap2 as fp32, index in the caller's
+ *   order) over all real bodies j != i, massless ones included; never the body itself, never the zero-mass padding slots.  A
+ *   lone body gets -1 and +inf.  With all radii 0 cp_i is the geometrically nearest body.  In general it is NOT the nearest
+ *   neighbour: a large body further away can overlap a body whose nearest neighbour does not touch it.  The bits do not depend
+ *   on "jsplit", "block_units", the order of the active list, or the run.  The values belong to the evaluation that produced
+ *   them (after a step: its predicted end state, like (a1, j1)); under block steps only the active bodies' entries are
+ *   refreshed and an inactive body keeps its (cp, gap2) bit for bit.  Domain: radii finite and >= 0, s*s a finite fp32; r2's
+ *   own rules are unchanged.
+ *   Option "contact" (0 default, 1, 2; other values MURBHIP_E_INVALID; one shard with "integrator" 2 only, MURBHIP_E_STATE
+ *   otherwise, and while it is non-zero "integrator" cannot leave 2).  1 keeps (cp, gap2) beside every acceleration + jerk
+ *   evaluation — the evaluations "nearest" lists; 2 also turns the contact stop on.  It excludes "nearest": setting either to
+ *   non-zero while the other is non-zero is MURBHIP_E_STATE (both use the same storage).  Switching between 0 and non-zero
+ *   drops the remembered evaluation and is refused (MURBHIP_E_STATE) while a block is open; switching between 1 and 2 keeps
+ *   the evaluation and an open block.  With 0 every result is what it was without the option, bit for bit.
+ * murbhip_upload_radii: n radii in the caller's order.  MURBHIP_E_INVALID for NULL, a value that is not finite or a negative
+ *   one; MURBHIP_E_STATE while a block is open or on a context of several shards or ranks.  Radii are 0 until first set;
+ *   murbhip_upload leaves them as they are, murbhip_init_bodies replaces them with the scheme's.  Drops the remembered
+ *   evaluation when "contact" is non-zero.  murbhip_download_mass(m, r) returns them afterwards.
+ * murbhip_download_contact: murbhip_download_nearest's rules: n entries each, either pointer may be NULL; waits for enqueued
+ *   work; MURBHIP_E_STATE when "contact" is 0 or no such evaluation is current; while a block is open it returns every body's
+ *   values at its own time.
+ * Contact stop ("contact" 2): a step of murbhip_evolve or murbhip_evolve_block in which any body that took the step has
+ *   gap2_i <= 0 is a hit: the step completes as usual, the run ends behind it, with out5 / out8 and the open block exactly as
+ *   after an encounter hit.  A call always takes at least one step.  murbhip_step(s) never stops.
+ * murbhip_contacts: murbhip_encounters' semantics for the triples (i, cp_i, gap2_i) of the hitting step: sorted by i, at most
+ *   4096 kept, *count says how many there were, cleared at the head of every evolve call.  While "contact" is non-zero
+ *   murbhip_encounters reports 0, and murbhip_contacts reports 0 while it is 0.
+ * Not covered: several shards or ranks; the other integrators; merging or removing bodies on the device (the Python helper
+ *   murbhip.merge_contacts resolves a hit list on the host); restitution; "nearest" and "contact" at once. */
+int murbhip_upload_radii(murbhip_ctx* ctx, const float* r);
+int murbhip_download_contact(murbhip_ctx* ctx, int* idx, float* gap2);
+int murbhip_contacts(murbhip_ctx* ctx, int* i, int* j, float* gap2, unsigned long capacity, unsigned long* count, double* time);
 
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
@@ -440,6 +482,9 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    murbhip_download_nearest above).  One shard with "integrator" 2 only (MURBHIP_E_STATE otherwise; while it is
  *                    1, "integrator" cannot leave 2, and it cannot return to 0 while an encounter radius is set).  Switching
  *                    it drops the remembered evaluation.  The active sweep then runs on 4 workgroups per CU instead of 5
+ *   "contact"        0 (default), 1, 2: the Hermite sweeps also keep every body's contact partner by radii and its gap2; 2 adds
+ *                    the contact stop (see murbhip_upload_radii above).  One shard with "integrator" 2 only; excludes "nearest".
+ *                    The active sweep then runs on 4 workgroups per CU instead of 5
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real
@@ -475,7 +520,7 @@ int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 /* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "sym_wide" (the form of the pair factor in use: 0 or 1; 0 on a one-sided plan), "taper",
  * "block_units", "block_grid" (work units and workgroups of murbhip_evolve_block's active sweep), "block_steps", "block_body_steps",
  * "block_clamped", "block_max_active" (the last murbhip_evolve_block call's counts), "nearest" (the option), "encounter_count" (hits of
- * the step that ended the last evolve call: murbhip_encounters' *count),
+ * the step that ended the last evolve call: murbhip_encounters' *count), "contact" (the option), "contact_count" (murbhip_contacts' *count),
  * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
  * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):

@@ -60,7 +60,7 @@ struct Shard {
     float* acc_out = nullptr;
     float* phi_out = nullptr;    // murbhip_energy's potential sweep (same shape as acc_out), allocated on first use
     float* mass = nullptr;       // masses of the local slice as uploaded (metrics)
-    float* radius = nullptr;     // radii of the local slice: only after murbhip_init_bodies (the host never sent them)
+    float* radius = nullptr;     // radii of the local slice: after murbhip_init_bodies or murbhip_upload_radii
     double* metrics = nullptr;   // block sums of murb_metrics_kernel, then murbhip_energy's pair potentials (metrics_doubles)
     double* metrics_host = nullptr;   // its pinned host copy: the read-out is one asynchronous copy behind the kernels
     // pair-symmetric kernel: item table and partial-row layouts (built by build_sym_schedule for one plan)
@@ -185,6 +185,8 @@ struct murbhip_ctx {
     float enc_radius = 0.f;         // murbhip_set_encounter; 0 = off
     unsigned long enc_count = 0;    // hits of the step that ended the last evolve call (0: it ended otherwise)
     double enc_time = 0.0;          // ... and the model time advanced in that call when they were seen
+    // contact by radii (Hermite sweeps); shares the per-slot arrays, the hit list and the counters above with "nearest"
+    int contact = 0;                // "contact": 1 the sweeps keep every body's (cp, gap2) beside (a, j), 2 also the contact stop
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

@@ -259,13 +259,149 @@ __device__ __forceinline__ void murb_enc_test(unsigned int* hits, MurbEncList* l
     if (at < MURB_ENC_CAP) { list->i[at] = i; list->j[at] = (int)idx; list->r2[at] = __builtin_bit_cast(float, r2); }
 }
 
+// ---- contact by radii beside the sweep (option "contact"; include/murbhip.h has the definition) ------------------------------
+// The nearest-neighbour scheme with gap2 = (r2 - soft2) - (R_i + R_j)^2 in r2's place: a packed add for the sum of radii (the
+// j radii ride in the two spare lanes of the velocity B record, the i radii in scalar registers), a packed add for r2 - soft2
+// and a packed fma, then the minimum, the compare and the select of the lane step.  gap2 may be negative, so the sign trick of
+// murb_nn_tile does not carry over: a masked tile subtracts -inf instead of soft2 (a wave-uniform select per tile), every
+// gap2 of it is +inf and nothing is recorded.  Where (gap2, slot) are folded they travel as an order-preserving unsigned key
+// (murb_ct_key); the per-slot store decodes it.
+#define MURB_CT_NONE_KEY 0xff800000u   // the key of +inf: "no candidate"
+
+__device__ __forceinline__ unsigned int murb_ct_key(const float g)
+{
+    const unsigned int b = __builtin_bit_cast(unsigned int, g);
+    return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u);
+}
+
+__device__ __forceinline__ float murb_ct_value(const unsigned int k)
+{
+    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+template <int R>
+__device__ __forceinline__ void murb_ct_tile(const float4* tq, const float4* tv, const int lane, const int tile, const bool masked,
+                                             const float (&xi)[R], const float (&yi)[R], const float (&zi)[R],
+                                             const float (&ui)[R], const float (&vi)[R], const float (&wi)[R],
+                                             const float (&ri)[R], const float soft2,
+                                             murb_f2 (&ax)[R], murb_f2 (&ay)[R], murb_f2 (&az)[R],
+                                             murb_f2 (&jx)[R], murb_f2 (&jy)[R], murb_f2 (&jz)[R],
+                                             float (&mn)[R], int (&st)[R])
+{
+    float c = masked ? -__builtin_inff() : soft2;   // wave-uniform, kept in a vector register: no scalar one is free
+    asm volatile("" : "+v"(c));
+#pragma unroll
+    for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
+        const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
+        const float4 VA = tv[q + lane], VB = tv[q + lane + MURB_TILE_PAIRS];
+        const murb_f2 xj = {A.x, A.y}, yj = {A.z, A.w}, zj = {B.x, B.y}, gj = {B.z, B.w};
+        const murb_f2 uj = {VA.x, VA.y}, vj = {VA.z, VA.w}, wj = {VB.x, VB.y}, rj = {VB.z, VB.w};
+        const int S = tile * (MURB_TILE_PAIRS / 64) + q / 64;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            murb_f2 r2;
+            murb_interact_jerk_pk_r2(xj, yj, zj, gj, uj, vj, wj, xi[r], yi[r], zi[r], ui[r], vi[r], wi[r], soft2,
+                                     ax[r], ay[r], az[r], jx[r], jy[r], jz[r], r2);
+            const murb_f2 s = rj + ri[r];
+            const murb_f2 e = r2 - c;
+            const murb_f2 g = __builtin_elementwise_fma(-s, s, e);
+            const float m = __builtin_fminf(__builtin_fminf(mn[r], g.x), g.y);
+            st[r] = m < mn[r] ? S : st[r];
+            mn[r] = m;
+        }
+    }
+}
+
+// gap2 of one i body and one j body behind the loop, in single instructions that give the packed ones' bits (murb_nn_r2_single)
+__device__ __forceinline__ float murb_ct_gap2_single(const float xj, const float yj, const float zj, const float rj,
+                                                     const float xi, const float yi, const float zi, const float ri, const float soft2)
+{
+    const float r2 = murb_nn_r2_single(xj, yj, zj, xi, yi, zi, soft2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    float s, e, g;
+    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(ri), "v"(rj));
+    asm("v_subrev_f32 %0, %1, %2" : "=v"(e) : "v"(soft2), "v"(r2));
+    asm("v_fma_f32 %0, -%1, %1, %2" : "=v"(g) : "v"(s), "v"(e));
+    return g;
+#else
+    const float s = rj + ri, e = r2 - soft2;
+    return __builtin_fmaf(-s, s, e);
+#endif
+}
+
+// The pairs of one masked tile from the records in memory, the body itself and the padding left out (murb_nn_masked_tile).
+template <int R>
+__device__ __forceinline__ void murb_ct_masked_tile(const float4* rec, const float4* vel, const int lane, const int tile,
+                                                    const float (&xi)[R], const float (&yi)[R], const float (&zi)[R],
+                                                    const float (&ri)[R], const float soft2,
+                                                    float (&mn)[R], int (&st)[R], const int (&self)[R], const int count)
+{
+#pragma unroll 1
+    for (int qs = 0; qs < MURB_TILE_PAIRS / 64; ++qs) {
+        const unsigned long ra = (unsigned long)tile * MURB_TILE_F4 + qs * 64 + lane;
+        const float4 A = rec[ra], B = rec[ra + MURB_TILE_PAIRS], VB = vel[ra + MURB_TILE_PAIRS];
+        const int S = tile * (MURB_TILE_PAIRS / 64) + qs;
+        const int j0 = tile * MURB_TILE_BODIES + 2 * (qs * 64 + lane);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float gx = murb_ct_gap2_single(A.x, A.z, B.x, VB.z, xi[r], yi[r], zi[r], ri[r], soft2);
+            float gy = murb_ct_gap2_single(A.y, A.w, B.y, VB.w, xi[r], yi[r], zi[r], ri[r], soft2);
+            if (j0 == self[r] || j0 >= count) gx = __builtin_inff();
+            if (j0 + 1 == self[r] || j0 + 1 >= count) gy = __builtin_inff();
+            const float m = __builtin_fminf(gx, gy);
+            if (m < mn[r] || (m == mn[r] && S < st[r])) { mn[r] = m; st[r] = S; }
+        }
+    }
+}
+
+// After the loop: the slot behind every lane's minimum, the fold over the wave; lane r gets body r's (key of gap2, slot).
+template <int R>
+__device__ __forceinline__ void murb_ct_finish(const float4* rec, const float4* vel, const int lane,
+                                               const float (&xi)[R], const float (&yi)[R], const float (&zi)[R], const float (&ri)[R],
+                                               const float soft2, const float (&mn)[R], const int (&st)[R],
+                                               const int (&self)[R], const int count, unsigned int& out_key, unsigned int& out_idx)
+{
+    out_key = MURB_CT_NONE_KEY;
+    out_idx = MURB_NN_NONE;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int p = st[r] * 64 + lane;   // the pair of slots of lane step st[r]
+        const unsigned long ra = murb_rec_a((unsigned long)p);
+        const float4 A = rec[ra], B = rec[ra + MURB_TILE_PAIRS], VB = vel[ra + MURB_TILE_PAIRS];
+        const float gx = murb_ct_gap2_single(A.x, A.z, B.x, VB.z, xi[r], yi[r], zi[r], ri[r], soft2);
+        const int j0 = 2 * p;
+        const bool first = gx == mn[r] && j0 != self[r] && j0 < count;
+        const unsigned int idx = mn[r] < __builtin_inff() ? (unsigned int)(first ? j0 : j0 + 1) : MURB_NN_NONE;
+        const unsigned int key = murb_ct_key(mn[r]);
+        const unsigned int kb = murb_wave_min_bits(__builtin_bit_cast(float, key));   // an unsigned minimum of the bits
+        const unsigned int cand = key == kb ? idx : MURB_NN_NONE;
+        const unsigned int ib = murb_wave_min_bits(__builtin_bit_cast(float, cand));
+        if (lane == r) { out_key = kb; out_idx = ib; }
+    }
+}
+
+// The per-slot store and the hit test of the correctors: the key decoded; a body that took the step with gap2 <= 0 is a hit.
+__device__ __forceinline__ void murb_ct_store(int* nn_idx, float* nn_r2, const int s, const unsigned int key, const unsigned int idx)
+{
+    nn_idx[s] = idx == MURB_NN_NONE ? -1 : (int)idx;
+    nn_r2[s] = idx == MURB_NN_NONE ? __builtin_inff() : murb_ct_value(key);
+}
+
+__device__ __forceinline__ void murb_ct_test(unsigned int* hits, MurbEncList* list, const int i, const unsigned int key, const unsigned int idx)
+{
+    if (idx == MURB_NN_NONE || !(murb_ct_value(key) <= 0.f)) return;
+    const unsigned int at = atomicAdd(hits, 1u);
+    if (at < MURB_ENC_CAP) { list->i[at] = i; list->j[at] = (int)idx; list->r2[at] = murb_ct_value(key); }
+}
+
 // ---- the sweep -------------------------------------------------------------------------------------------------------
 // grid.x = i groups of WAVES*R bodies, grid.y = j chunks.  LDS: STAGE position tiles + STAGE velocity tiles (16 KiB a stage).
 // The body is a device function so that the adaptive launch (murb_force_jerk_adaptive_kernel, below) runs the same code.
-// NN: the nearest-neighbour form (Args = MurbNNJerkArgs); the plain form's code does not change with it.
-template <int R, int WAVES, int STAGE, bool NN = false, typename Args = MurbJerkArgs>
+// MODE 1: the nearest-neighbour form, 2: the contact form (Args = MurbNNJerkArgs); the plain form's code does not change with them.
+template <int R, int WAVES, int STAGE, int MODE = 0, typename Args = MurbJerkArgs>
 __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
 {
+    constexpr bool NN = MODE != 0, CT = MODE == 2;
     static_assert(R % 2 == 0 && MURB_TILE_BODIES % (WAVES * R) == 0, "i groups must tile the layout");
     __shared__ float4 lds[2 * STAGE * MURB_TILE_F4];
 
@@ -274,7 +410,7 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
     const int i_slot = (blockIdx.x * WAVES + wave) * R;   // wave-uniform; the host keeps the grid inside the slots
 
     // the wave's R i bodies -> scalar registers
-    float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
+    float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], ri[R];   // ri: the contact form's radii
     {
         const unsigned long ra = murb_rec_a((unsigned long)(i_slot >> 1));
 #pragma unroll
@@ -283,6 +419,7 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
             const float4 VA = a.vel[ra + h], VB = a.vel[ra + h + MURB_TILE_PAIRS];
             xi[2 * h] = A.x; xi[2 * h + 1] = A.y; yi[2 * h] = A.z; yi[2 * h + 1] = A.w; zi[2 * h] = B.x; zi[2 * h + 1] = B.y;
             ui[2 * h] = VA.x; ui[2 * h + 1] = VA.y; vi[2 * h] = VA.z; vi[2 * h + 1] = VA.w; wi[2 * h] = VB.x; wi[2 * h + 1] = VB.y;
+            if constexpr (CT) { ri[2 * h] = VB.z; ri[2 * h + 1] = VB.w; }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -292,6 +429,7 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
             ui[r] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ui[r])));
             vi[r] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, vi[r])));
             wi[r] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wi[r])));
+            if constexpr (CT) asm volatile("" : "+v"(ri[r]));   // every lane has loaded it: it stays in a vector register (no scalar one is free)
         }
     }
 
@@ -344,7 +482,8 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
             const float4* tv = tq + MURB_TILE_F4;
             if constexpr (NN) {
                 const bool masked = murb_nn_tile_masked<1>(vs + t, self_tile, count);   // wave-uniform
-                murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                if constexpr (CT) murb_ct_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, ri, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                else murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
                 continue;
             }
 #pragma unroll
@@ -373,10 +512,17 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
         const int tiles = again->tiles, nchunks = again->nchunks;
         const int t0 = (int)(((long)tiles * chunk) / nchunks), t1 = (int)(((long)tiles * (chunk + 1)) / nchunks);   // vt0, vt1 again
         const int own[1] = {first / MURB_TILE_BODIES};
-        for (int tile = t0; tile < t1; ++tile)
-            if (murb_nn_tile_masked<1>(tile, own, cnt)) murb_nn_masked_tile<R>(rec, lane, tile, xi, yi, zi, soft2, mn, st, self, cnt);
         unsigned int nn_r2, nn_idx;
-        murb_nn_finish<R>(rec, lane, xi, yi, zi, soft2, mn, st, self, cnt, nn_r2, nn_idx);
+        if constexpr (CT) {
+            const float4* const vel = again->vel;
+            for (int tile = t0; tile < t1; ++tile)
+                if (murb_nn_tile_masked<1>(tile, own, cnt)) murb_ct_masked_tile<R>(rec, vel, lane, tile, xi, yi, zi, ri, soft2, mn, st, self, cnt);
+            murb_ct_finish<R>(rec, vel, lane, xi, yi, zi, ri, soft2, mn, st, self, cnt, nn_r2, nn_idx);
+        } else {
+            for (int tile = t0; tile < t1; ++tile)
+                if (murb_nn_tile_masked<1>(tile, own, cnt)) murb_nn_masked_tile<R>(rec, lane, tile, xi, yi, zi, soft2, mn, st, self, cnt);
+            murb_nn_finish<R>(rec, lane, xi, yi, zi, soft2, mn, st, self, cnt, nn_r2, nn_idx);
+        }
         nn_a = __builtin_bit_cast(float, nn_r2);
         nn_j = __builtin_bit_cast(float, nn_idx);
     }
@@ -432,6 +578,7 @@ struct MurbHermiteArgs {
     int* nn_idx;            // "nearest": every slot's nearest neighbour and its r2, folded beside the row sums; null = off
     float* nn_r2;
     MurbEncList* enc;       // ... and the encounter list of murbhip_evolve
+    int contact;            // "contact": the rows' fourth floats are (key of gap2, slot), kept in nn_idx / nn_r2; 2 = with the contact stop
 };
 
 __device__ __forceinline__ float murb_hermite_predict_q(float q, float v, float a, float j, double dt, double c2, double c3)
@@ -506,7 +653,7 @@ __global__ __launch_bounds__(256) void murb_hermite_predict_kernel(const MurbHer
 // The two evaluations a corrector thread holds for its two slots: [slot][component]
 struct MurbHermiteForces {
     float a0[2][3], j0[2][3], a1[2][3], j1[2][3];
-    unsigned int nn_r2[2], nn_idx[2];   // "nearest": (r2 bits, slot) of the evaluation that gave (a1, j1)
+    unsigned int nn_r2[2], nn_idx[2];   // "nearest": (r2 bits, slot) of the evaluation that gave (a1, j1); "contact": (key of gap2, slot)
 };
 
 // Partial rows -> (a1, j1) in fixed order; (a0, j0) are read, then replaced by (a1, j1).
@@ -518,7 +665,7 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int k = 0; k < 3; ++k) { f.a1[h][k] = 0.f; f.j1[h][k] = 0.f; }
-    f.nn_r2[0] = f.nn_r2[1] = MURB_F32_INF_BITS;
+    f.nn_r2[0] = f.nn_r2[1] = a.contact ? MURB_CT_NONE_KEY : MURB_F32_INF_BITS;
     f.nn_idx[0] = f.nn_idx[1] = MURB_NN_NONE;
     for (int p = 0; p < a.nparts; ++p) {
 #pragma unroll
@@ -532,7 +679,10 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
     }
     if (a.nn_idx) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) murb_nn_store(a.nn_idx, a.nn_r2, s0 + h, f.nn_r2[h], f.nn_idx[h]);
+        for (int h = 0; h < 2; ++h) {
+            if (a.contact) murb_ct_store(a.nn_idx, a.nn_r2, s0 + h, f.nn_r2[h], f.nn_idx[h]);
+            else murb_nn_store(a.nn_idx, a.nn_r2, s0 + h, f.nn_r2[h], f.nn_idx[h]);
+        }
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -794,7 +944,15 @@ template <int R, int WAVES, int STAGE>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_nn_sweep_kernel(const MurbNNJerkArgs a, const MurbEvolveCtl* ctl)
 {
     if (ctl && ctl->done) return;   // wave-uniform
-    murb_force_jerk_sweep<R, WAVES, STAGE, true, MurbNNJerkArgs>(a);
+    murb_force_jerk_sweep<R, WAVES, STAGE, 1, MurbNNJerkArgs>(a);
+}
+
+// The contact form of both launches (ctl null: the fixed-step one); 4 waves per SIMD like the nearest-neighbour form.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_contact_sweep_kernel(const MurbNNJerkArgs a, const MurbEvolveCtl* ctl)
+{
+    if (ctl && ctl->done) return;   // wave-uniform
+    murb_force_jerk_sweep<R, WAVES, STAGE, 2, MurbNNJerkArgs>(a);
 }
 
 // The corrector of an adaptive step: murb_hermite_correct_kernel's work with dt from the control block, then the criterion.
@@ -822,7 +980,11 @@ __global__ __launch_bounds__(256) void murb_hermite_correct_adaptive_kernel(cons
 #pragma unroll
         for (int h = 0; h < 2; ++h)
             if (s0 + h < a.count) mine = fminf(mine, murb_evolve_body_step(f.a0[h], f.j0[h], f.a1[h], f.j1[h], (double)dt, eta));
-        if (a.nn_idx) {
+        if (a.contact == 2) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (s0 + h < a.count) murb_ct_test(&ctl->enc_hits, a.enc, s0 + h, f.nn_r2[h], f.nn_idx[h]);
+        } else if (a.nn_idx && !a.contact) {
             const float thr = ctl->enc_thr;
 #pragma unroll
             for (int h = 0; h < 2; ++h)
@@ -903,6 +1065,7 @@ struct MurbBlockArgs {
     int count;
     unsigned int stride;   // slots
     float soft2;
+    int contact;           // "contact": see MurbHermiteArgs
 };
 
 // what the active sweep holds of it through its inner loop
@@ -1051,6 +1214,7 @@ __global__ __launch_bounds__(256) void murb_block_predict_kernel(const MurbBlock
                 *murb_block_slot(a.rec_act, at, k) = q[h][k];
                 *murb_block_slot(a.vel_act, at, k) = v[h][k];
             }
+            if (a.contact) murb_block_slot(a.vel_act, at, 2)[2] = h ? VB.w : VB.z;   // the radius: the active sweep's i side reads it there
         }
     }
     a.rec_pred[ra] = make_float4(q[0][0], q[1][0], q[0][1], q[1][1]);
@@ -1089,10 +1253,11 @@ __device__ __forceinline__ MurbBlockCtlK murb_block_ctl_now(const MurbBlockCtl* 
 // walks units u = blockIdx.x, += gridDim.x with (group, chunk) = (u % groups, u / groups).  The entries behind the list's
 // end in its last group are whatever the buffer held: their rows are never read.
 // The body is a device function with the nearest-neighbour form behind a compile-time switch (NN, Args =
-// MurbBlockNNSweepArgs), like murb_force_jerk_sweep: the plain form's code does not change with it.
-template <int R, int WAVES, int STAGE, bool NN = false, typename Args = MurbBlockSweepArgs>
+// MurbBlockNNSweepArgs; MODE 1) and the contact form (MODE 2), like murb_force_jerk_sweep: the plain form's code does not change.
+template <int R, int WAVES, int STAGE, int MODE = 0, typename Args = MurbBlockSweepArgs>
 __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const MurbBlockCtl* ctl)  // NN: a is the kernel's first argument
 {
+    constexpr bool NN = MODE != 0, CT = MODE == 2;
     static_assert(R % 2 == 0 && WAVES * R == MURB_BLOCK_GROUP, "a workgroup takes one group of the list");
     static_assert(MURB_TILE_F4 % (WAVES * 64) == 0, "the workgroup copies a tile in whole rounds");
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass knows no constant address space to read through
@@ -1106,7 +1271,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
     for (int u = blockIdx.x;; u += NN ? stride_u : (int)gridDim.x) {
         if constexpr (NN) {   // the scalar registers are taken: the stride and the control block from the kernel arguments, per unit
             const auto* again = murb_kernarg_again<Args>();
-            stride_u = again->grid;
+            if constexpr (!CT) stride_u = again->grid;   // the contact form reads it at the unit's end: one scalar register less
             ctl = again->ctl;
         }
         const MurbBlockCtlK now = murb_block_ctl_now(ctl);
@@ -1121,7 +1286,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
         }
         const int i_slot = (group * WAVES + wave_now) * R;   // list index, wave-uniform
 
-        float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R];
+        float xi[R], yi[R], zi[R], ui[R], vi[R], wi[R], ri[R];   // ri: the contact form's radii
         {
             const unsigned long ra = murb_rec_a((unsigned long)(i_slot >> 1));
             // written by the launch before this one and wave-uniform: scalar loads, straight into scalar registers
@@ -1132,6 +1297,10 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
                 const float4 VA = vel_act[ra + h], VB = vel_act[ra + h + MURB_TILE_PAIRS];
                 xi[2 * h] = A.x; xi[2 * h + 1] = A.y; yi[2 * h] = A.z; yi[2 * h + 1] = A.w; zi[2 * h] = B.x; zi[2 * h + 1] = B.y;
                 ui[2 * h] = VA.x; ui[2 * h + 1] = VA.y; vi[2 * h] = VA.z; vi[2 * h + 1] = VA.w; wi[2 * h] = VB.x; wi[2 * h + 1] = VB.y;
+                if constexpr (CT) {   // to vector registers: no scalar one is free
+                    ri[2 * h] = VB.z; ri[2 * h + 1] = VB.w;
+                    asm volatile("" : "+v"(ri[2 * h]), "+v"(ri[2 * h + 1]));
+                }
             }
         }
         float mn[R];   // NN: the lane's smallest r2 per i body, and the lane step it fell at
@@ -1192,7 +1361,8 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
 #pragma unroll
                     for (int r = 0; r < R; ++r) self_tile[r] = __builtin_amdgcn_readlane(w, r) / MURB_TILE_BODIES;
                     const bool masked = murb_nn_tile_masked<R>(vs + t, self_tile, __builtin_amdgcn_readlane(w, R));   // wave-uniform
-                    murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                    if constexpr (CT) murb_ct_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, ri, soft2, ax, ay, az, jx, jy, jz, mn, st);
+                    else murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
                     continue;
                 }
 #pragma unroll
@@ -1223,11 +1393,20 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
 #pragma unroll
             for (int r = 0; r < R; ++r) { self[r] = __builtin_amdgcn_readlane(w, r); self_tile[r] = self[r] / MURB_TILE_BODIES; }
             const int count = __builtin_amdgcn_readlane(w, R);
-            for (int tile = vt0; tile < vt1; ++tile)
-                if (murb_nn_tile_masked<R>(tile, self_tile, count))
-                    murb_nn_masked_tile<R>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, mn, st, self, count);
             unsigned int nn_r2, nn_idx;
-            murb_nn_finish<R>(rec_pred, fold_lane, xi, yi, zi, soft2, mn, st, self, count, nn_r2, nn_idx);
+            if constexpr (CT) {
+                const float4* vel_pred = a.vel_pred;
+                asm volatile("" : "+s"(vel_pred));
+                for (int tile = vt0; tile < vt1; ++tile)
+                    if (murb_nn_tile_masked<R>(tile, self_tile, count))
+                        murb_ct_masked_tile<R>(rec_pred, vel_pred, fold_lane, tile, xi, yi, zi, ri, soft2, mn, st, self, count);
+                murb_ct_finish<R>(rec_pred, vel_pred, fold_lane, xi, yi, zi, ri, soft2, mn, st, self, count, nn_r2, nn_idx);
+            } else {
+                for (int tile = vt0; tile < vt1; ++tile)
+                    if (murb_nn_tile_masked<R>(tile, self_tile, count))
+                        murb_nn_masked_tile<R>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, mn, st, self, count);
+                murb_nn_finish<R>(rec_pred, fold_lane, xi, yi, zi, soft2, mn, st, self, count, nn_r2, nn_idx);
+            }
             nn_a = __builtin_bit_cast(float, nn_r2);
             nn_j = __builtin_bit_cast(float, nn_idx);
         }
@@ -1243,9 +1422,10 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
             end->part_a[at] = make_float4(oa[0], oa[1], oa[2], nn_a);
             end->part_j[at] = make_float4(oj[0], oj[1], oj[2], nn_j);
         }
+        if constexpr (CT) stride_u = murb_kernarg_again<Args>()->grid;
     }
 #else
-    (void)a; (void)ctl;
+    (void)a; (void)ctl; (void)NN; (void)CT;
 #endif
 }
 
@@ -1259,7 +1439,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(5)))
 template <int R, int WAVES, int STAGE>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_nn_active_sweep_kernel(const MurbBlockNNSweepArgs a, const MurbBlockCtl* ctl)
 {
-    murb_force_jerk_block_sweep<R, WAVES, STAGE, true, MurbBlockNNSweepArgs>(a, ctl);
+    murb_force_jerk_block_sweep<R, WAVES, STAGE, 1, MurbBlockNNSweepArgs>(a, ctl);
+}
+
+// The contact form: the i bodies' radii come from the compact velocity buffer, where the block predictor puts them.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_contact_active_sweep_kernel(const MurbBlockNNSweepArgs a, const MurbBlockCtl* ctl)
+{
+    murb_force_jerk_block_sweep<R, WAVES, STAGE, 2, MurbBlockNNSweepArgs>(a, ctl);
 }
 
 // launch 5: one thread per list entry.  The grid covers `count` entries; threads behind the list's end only take part in the
@@ -1281,7 +1468,7 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
         const int s = a.list[at];
         const int k = a.levels[s];
         float a0[3], j0[3], a1[3] = {0.f, 0.f, 0.f}, j1[3] = {0.f, 0.f, 0.f};
-        unsigned int nn_r2 = MURB_F32_INF_BITS, nn_idx = MURB_NN_NONE;
+        unsigned int nn_r2 = a.contact ? MURB_CT_NONE_KEY : MURB_F32_INF_BITS, nn_idx = MURB_NN_NONE;
         for (int p = 0; p < chunks; ++p) {
             const float4 u = a.part_a[(unsigned long)p * stride + at];
             const float4 w = a.part_j[(unsigned long)p * stride + at];
@@ -1289,7 +1476,10 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
             j1[0] += w.x; j1[1] += w.y; j1[2] += w.z;
             murb_nn_fold_row(nn_r2, nn_idx, u, w);
         }
-        if (a.nn_idx) {
+        if (a.contact) {
+            murb_ct_store(a.nn_idx, a.nn_r2, s, nn_r2, nn_idx);
+            if (a.contact == 2) murb_ct_test(&ctl->enc_hits, a.enc, s, nn_r2, nn_idx);
+        } else if (a.nn_idx) {
             murb_nn_store(a.nn_idx, a.nn_r2, s, nn_r2, nn_idx);
             murb_enc_test(&ctl->enc_hits, a.enc, ctl->enc_thr, s, nn_r2, nn_idx);
         }
@@ -1322,6 +1512,18 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
         atomicMax(&ctl->k_hi, (unsigned int)ctl->kmax - hi_inv);
         if (nclamped) atomicAdd(&ctl->clamped, nclamped);
     }
+}
+
+// The radii in the velocity records ("contact"): lanes z, w of a pair's B record = {R0, R1}; radius null: 0 in both (option
+// off, or no radii set yet), as in the padding slots.  One thread per pair of slots.
+__global__ __launch_bounds__(256) void murb_radii_lanes_kernel(float4* vel, const float* radius, const int count, const unsigned int slots)
+{
+    const unsigned int lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (2u * lp >= slots) return;
+    const int s0 = (int)(2u * lp);
+    float* const b = (float*)(vel + murb_rec_a((unsigned long)lp) + MURB_TILE_PAIRS);
+    b[2] = radius && s0 < count ? radius[s0] : 0.f;
+    b[3] = radius && s0 + 1 < count ? radius[s0 + 1] : 0.f;
 }
 
 // launch 6, one thread: the step in flight has been taken

@@ -789,7 +789,7 @@ int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
         RC_TRY(shard_alloc(sh, sh.herm_part, (size_t)2 * rows * c->in.slots * sizeof(float4), sh.compute));
         sh.herm_rows = rows;
     }
-    if (c->nearest) {
+    if (c->nearest || c->contact) {
         RC_TRY(shard_alloc(sh, sh.nn_idx, c->in.slots * sizeof(int), sh.compute));
         RC_TRY(shard_alloc(sh, sh.nn_r2, c->in.slots * sizeof(float), sh.compute));
         RC_TRY(shard_alloc(sh, sh.enc, sizeof(MurbEncList), sh.compute));
@@ -818,7 +818,8 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
     a.stride = (unsigned int)c->in.slots;
     a.dt = dt;
     a.update_state = update_state;
-    if (c->nearest) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
+    if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
+    a.contact = c->contact;
     return a;
 }
 
@@ -842,7 +843,10 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
         int rc = 0;
         const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
         RC_TRY(rc);
-        if (c->nearest)
+        if (c->contact)
+            hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                               (const MurbEvolveCtl*)nullptr);
+        else if (c->nearest)
             hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
                                (const MurbEvolveCtl*)nullptr);
         else
@@ -853,7 +857,10 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
         note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
         return 0;
     }
-    if (c->nearest)
+    if (c->contact)
+        hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                           (const MurbEvolveCtl*)ctl);
+    else if (c->nearest)
         hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
                            (const MurbEvolveCtl*)ctl);
     else
@@ -980,7 +987,8 @@ MurbBlockArgs block_args(const murbhip_ctx* c, const Shard& sh)
     a.ticks = sh.blk_ticks;
     a.levels = sh.blk_levels;
     a.list = sh.blk_list;
-    if (c->nearest) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
+    if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
+    a.contact = c->contact;
     a.count = (int)sh.count;
     a.stride = (unsigned int)c->in.slots;
     a.soft2 = c->soft2;
@@ -994,11 +1002,15 @@ int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
     hipLaunchKernelGGL(murb_block_min_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_predict_kernel, dim3(per_pair), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_plan_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
-    if (c->nearest) {   // 4 waves per SIMD: 4 resident workgroups per CU
+    if (c->nearest || c->contact) {   // 4 waves per SIMD: 4 resident workgroups per CU
         MurbBlockNNSweepArgs na{};
         na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
         na.grid = block_grid(c) / 5 * 4;
         na.ctl = sh.blk_ctl;
+        if (c->contact)
+            hipLaunchKernelGGL((murb_contact_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
+        else
         hipLaunchKernelGGL((murb_nn_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
                            dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
     } else {
@@ -1143,6 +1155,48 @@ void bodies_loaded(murbhip_ctx* c)
     c->uploaded = true;
     c->lf_half = false;
     invalidate_cached_forces(c);
+}
+
+// "contact": the bodies' radii into the two spare lanes of the velocity B records (0 with the option off or no radii set), on
+// the compute stream.  One shard; runs at the option's switch and wherever the velocity records or the radii are replaced.
+int enqueue_radii_lanes(murbhip_ctx* c)
+{
+    if (!c->uploaded || c->shards.size() != 1 || c->in.world != 1) return 0;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
+    hipLaunchKernelGGL(murb_radii_lanes_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, sh.vel,
+                       c->contact ? (const float*)sh.radius : (const float*)nullptr, (int)sh.count, (unsigned int)c->in.slots);
+    return hip_rc(hipGetLastError());
+}
+
+// The hit list of the last evolve call (encounters or contacts: the options exclude each other), sorted by i.
+int read_hit_list(murbhip_ctx* c, bool mine, int* i, int* j, float* v, unsigned long capacity, unsigned long* count, double* time)
+{
+    const unsigned long hits = mine ? c->enc_count : 0ul;
+    *count = hits;
+    if (time) *time = c->enc_time;
+    const unsigned long kept = std::min<unsigned long>(hits, MURB_ENC_CAP);
+    if ((!i && !j && !v) || kept == 0) return 0;
+    if (capacity < kept) return MURBHIP_E_INVALID;
+    Shard& sh = c->shards[0];
+    if (!sh.enc) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    HIP_TRY(hipSetDevice(sh.device));
+    std::vector<int> li(kept), lj(kept);
+    std::vector<float> lr(kept);
+    HIP_TRY(hipMemcpy(li.data(), sh.enc->i, kept * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lj.data(), sh.enc->j, kept * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lr.data(), sh.enc->r2, kept * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<unsigned long> order(kept);   // the device's order is that of its atomics: sort by i
+    for (unsigned long k = 0; k < kept; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](unsigned long a, unsigned long b) { return li[a] < li[b]; });
+    for (unsigned long k = 0; k < kept; ++k) {
+        if (i) i[k] = li[order[k]];
+        if (j) j[k] = lj[order[k]];
+        if (v) v[k] = lr[order[k]];
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1384,6 +1438,7 @@ int murbhip_upload(murbhip_ctx* c, const float* qx, const float* qy, const float
         HIP_TRY(hipMemcpy(sh.mass, mass.data(), mass.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     bodies_loaded(c);
+    if (c->contact) RC_TRY(enqueue_radii_lanes(c));   // the velocity records were replaced; the radii stay
     return 0;
 }
 
@@ -1457,6 +1512,7 @@ int murbhip_init_bodies(murbhip_ctx* c, const char* scheme, unsigned long seed)
     }
     c->sym_wide_needed = false;   // the reference's schemes span 1e9 m: the fast form of the pair-symmetric kernel ("sym_wide")
     bodies_loaded(c);
+    if (c->contact) RC_TRY(enqueue_radii_lanes(c));   // the scheme's radii
     return 0;
 }
 
@@ -1471,7 +1527,7 @@ int murbhip_download_mass(murbhip_ctx* c, float* m, float* r)
         HIP_TRY(hipMemcpy(buf.data(), sh.mass, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
         std::memcpy(m + sh.first, buf.data(), sh.count * sizeof(float));
         if (r) {
-            if (!sh.radius) return MURBHIP_E_STATE;   // radii exist on the device only after murbhip_init_bodies
+            if (!sh.radius) return MURBHIP_E_STATE;   // radii exist on the device only after murbhip_init_bodies or murbhip_upload_radii
             HIP_TRY(hipMemcpy(buf.data(), sh.radius, buf.size() * sizeof(float), hipMemcpyDeviceToHost));
             std::memcpy(r + sh.first, buf.data(), sh.count * sizeof(float));
         }
@@ -1623,27 +1679,44 @@ int murbhip_encounters(murbhip_ctx* c, int* i, int* j, float* r2, unsigned long 
 {
     if (!c || !count) return MURBHIP_E_INVALID;
     if (!c->uploaded) return MURBHIP_E_STATE;
-    *count = c->enc_count;
-    if (time) *time = c->enc_time;
-    const unsigned long kept = std::min<unsigned long>(c->enc_count, MURB_ENC_CAP);
-    if ((!i && !j && !r2) || kept == 0) return 0;
-    if (capacity < kept) return MURBHIP_E_INVALID;
-    Shard& sh = c->shards[0];
-    if (!sh.enc) return MURBHIP_E_STATE;
+    return read_hit_list(c, !c->contact, i, j, r2, capacity, count, time);
+}
+
+int murbhip_contacts(murbhip_ctx* c, int* i, int* j, float* gap2, unsigned long capacity, unsigned long* count, double* time)
+{
+    if (!c || !count) return MURBHIP_E_INVALID;
+    if (!c->uploaded) return MURBHIP_E_STATE;
+    return read_hit_list(c, c->contact != 0, i, j, gap2, capacity, count, time);
+}
+
+int murbhip_download_contact(murbhip_ctx* c, int* idx, float* gap2)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->uploaded || !c->contact || !c->herm_current) return MURBHIP_E_STATE;
     RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
     HIP_TRY(hipSetDevice(sh.device));
-    std::vector<int> li(kept), lj(kept);
-    std::vector<float> lr(kept);
-    HIP_TRY(hipMemcpy(li.data(), sh.enc->i, kept * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(lj.data(), sh.enc->j, kept * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(lr.data(), sh.enc->r2, kept * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<unsigned long> order(kept);   // the device's order is that of its atomics: sort by i
-    for (unsigned long k = 0; k < kept; ++k) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](unsigned long a, unsigned long b) { return li[a] < li[b]; });
-    for (unsigned long k = 0; k < kept; ++k) {
-        if (i) i[k] = li[order[k]];
-        if (j) j[k] = lj[order[k]];
-        if (r2) r2[k] = lr[order[k]];
+    if (idx) HIP_TRY(hipMemcpy(idx, sh.nn_idx, c->in.n * sizeof(int), hipMemcpyDeviceToHost));
+    if (gap2) HIP_TRY(hipMemcpy(gap2, sh.nn_r2, c->in.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int murbhip_upload_radii(murbhip_ctx* c, const float* r)
+{
+    if (!c || !r) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; i < c->in.n; ++i)
+        if (!std::isfinite(r[i]) || r[i] < 0.f) return MURBHIP_E_INVALID;
+    if (c->blk_open || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    RC_TRY(shard_alloc(sh, sh.radius, c->in.slice * sizeof(float)));
+    std::vector<float> buf(c->in.slice, 0.f);
+    std::copy(r, r + c->in.n, buf.begin());
+    HIP_TRY(hipMemcpy(sh.radius, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (c->contact) {
+        invalidate_cached_forces(c);   // the remembered (cp, gap2) belong to the old radii
+        RC_TRY(enqueue_radii_lanes(c));
     }
     return 0;
 }
@@ -2107,7 +2180,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
         if (value == 2 && (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
-        if (value != 2 && c->nearest) return MURBHIP_E_STATE;   // "nearest" belongs to the Hermite sweeps: switch it off first
+        if (value != 2 && (c->nearest || c->contact)) return MURBHIP_E_STATE;   // they belong to the Hermite sweeps: switch them off first
         c->integrator = (int)value;
     }
     else if (k == "evolve_batch") {
@@ -2117,11 +2190,26 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "nearest") {
         if (value != 0 && value != 1) return MURBHIP_E_INVALID;
         if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+        if (value && c->contact) return MURBHIP_E_STATE;   // both use the rows' fourth floats and the per-slot arrays
         if (!value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
         if ((int)value != c->nearest) {
             c->nearest = (int)value;
             invalidate_cached_forces(c);   // a remembered (a0, j0) always has its neighbours beside it
         }
+    }
+    else if (k == "contact") {
+        if (value < 0 || value > 2) return MURBHIP_E_INVALID;
+        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+        if (value && c->nearest) return MURBHIP_E_STATE;   // both use the rows' fourth floats and the per-slot arrays
+        const bool was = c->contact != 0, now = value != 0;
+        if (was != now) {
+            if (c->blk_open) return MURBHIP_E_STATE;   // the open block's velocity records carry the radii or do not
+            c->contact = (int)value;
+            c->enc_count = 0;
+            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its contact partners beside it
+            RC_TRY(enqueue_radii_lanes(c));
+        }
+        c->contact = (int)value;   // 1 <-> 2: only the stop; the evaluation and an open block stay
     }
     else if (k == "block_units") {
         if (value < 0 || value > kBlockMaxUnits) return MURBHIP_E_INVALID;
@@ -2184,7 +2272,9 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "block_units") *value = block_units(c);
     else if (k == "block_grid") *value = block_grid(c);
     else if (k == "nearest") *value = c->nearest;
-    else if (k == "encounter_count") *value = (double)c->enc_count;
+    else if (k == "encounter_count") *value = c->contact ? 0.0 : (double)c->enc_count;
+    else if (k == "contact") *value = c->contact;
+    else if (k == "contact_count") *value = c->contact ? (double)c->enc_count : 0.0;
     else if (k == "block_steps") *value = c->blk_info[0];
     else if (k == "block_body_steps") *value = c->blk_info[1];
     else if (k == "block_clamped") *value = c->blk_info[2];

@@ -172,6 +172,31 @@ int murbhost_sim_encounters(void *p, int *i, int *j, float *r2, unsigned long ca
     }
     return 0;
 }
+// hip+hermite+adaptive / hip+hermite+block: SimulationNBodyHIPTracking::setContactStop.  0, or -1 where it does not apply
+// (another simulation, an encounter radius set, a scale that is not finite and positive).
+int murbhost_sim_set_contact(void *p, int on, float rscale)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    return t && t->setContactStop(on != 0, rscale) ? 0 : -1;
+}
+// ... the triples (i, contact partner, gap2) of the substep that ended the last iteration (murbhip_contacts' arguments).
+// 0, -1 for a simulation without a contact stop, -2 when capacity is smaller than the number kept.
+int murbhost_sim_contacts(void *p, int *i, int *j, float *gap2, unsigned long capacity, unsigned long *count, double *time)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->isAdaptive() || !t->hasContactStop()) return -1;
+    *count = t->getContactCount();
+    if (time) *time = t->getContactTime();
+    const auto &e = t->getContacts();
+    if ((!i && !j && !gap2) || e.empty()) return 0;
+    if (capacity < e.size()) return -2;
+    for (size_t k = 0; k < e.size(); ++k) {
+        if (i) i[k] = e[k].i;
+        if (j) j[k] = e[k].j;
+        if (gap2) gap2[k] = e[k].r2;
+    }
+    return 0;
+}
 int murbhost_sim_history_csv(void *p, const char *path)
 {
     try {
@@ -198,6 +223,9 @@ void murbhost_sim_init_on_device(void *p, unsigned long seed)
 {
     auto *h = static_cast<Sim *>(p);
     std::dynamic_pointer_cast<HIPBodies<float>>(h->sim->getBodies())->initOnDevice(h->scheme, seed);
+    // the device now holds the scheme's radii: a contact stop gets its scaled ones back
+    if (auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(h->sim); t && t->hasContactStop())
+        t->setContactStop(true, t->getContactScale());
 }
 unsigned long murbhost_sim_n(void *p) { return static_cast<Sim *>(p)->sim->getBodies()->getN(); }
 float murbhost_sim_flops_per_ite(void *p) { return static_cast<Sim *>(p)->sim->getFlopsPerIte(); }

@@ -34,12 +34,42 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
 
 template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setEncounterRadius(const T radius)
 {
-    if (!adaptive) return false;
+    if (!adaptive || (radius > 0 && contactStop)) return false;
     murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
     if (radius > 0) murbhipCheck(murbhip_set_option(ctx, "nearest", 1), "murbhip_set_option(nearest)");
     murbhipCheck(murbhip_set_encounter(ctx, (float)radius), "murbhip_set_encounter");
     encounterRadius = radius;
     return true;
+}
+
+template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setContactStop(const bool on, const T scale)
+{
+    if (!adaptive || encounterRadius > 0 || !(scale > 0) || !std::isfinite((double)scale)) return false;
+    murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
+    if (on) {
+        const auto &r = this->hipBodiesPtr->getDataSoA().r;
+        const unsigned long n = this->hipBodiesPtr->getN();
+        std::vector<float> radii(n);
+        for (unsigned long k = 0; k < n; ++k) radii[k] = (float)(r[k] * scale);
+        murbhipCheck(murbhip_upload_radii(ctx, radii.data()), "murbhip_upload_radii");
+    }
+    murbhipCheck(murbhip_set_option(ctx, "contact", on ? 2 : 0), "murbhip_set_option(contact)");
+    contactStop = on;
+    contactScale = scale;
+    return true;
+}
+
+template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::readContacts()
+{
+    murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
+    contacts.clear();
+    murbhipCheck(murbhip_contacts(ctx, nullptr, nullptr, nullptr, 0, &contactCount, &contactTime), "murbhip_contacts");
+    const unsigned long kept = std::min(contactCount, 4096ul);
+    if (!kept) return;
+    std::vector<int> i(kept), j(kept);
+    std::vector<float> gap2(kept);
+    murbhipCheck(murbhip_contacts(ctx, i.data(), j.data(), gap2.data(), kept, &contactCount, &contactTime), "murbhip_contacts");
+    for (unsigned long k = 0; k < kept; ++k) contacts.push_back({i[k], j[k], gap2[k]});
 }
 
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::readEncounters()
@@ -69,6 +99,7 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
         bodySteps += (unsigned long)out[2];
         clampedSteps += (unsigned long)out[5];
         if (encounterRadius > 0) readEncounters();
+        if (contactStop) readContacts();
     } else if (adaptive) {   // exactly dt of model time, in the substeps the criterion chooses; returns synchronised
         double out[5];
         this->hipBodiesPtr->invalidateDataSoA();
@@ -78,6 +109,7 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
         dtLargest = std::max(dtLargest, out[3]);
         substeps += (unsigned long)out[1];
         if (encounterRadius > 0) readEncounters();
+        if (contactStop) readContacts();
     } else SimulationNBodyHIP<T>::computeOneIteration();
     currentIteration++;
 }

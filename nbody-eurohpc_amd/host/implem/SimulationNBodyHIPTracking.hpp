@@ -40,6 +40,11 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     std::vector<Encounter> encounters;   // the pairs (i, nearest of i) of that substep, sorted by i (the device keeps 4096)
     unsigned long encounterCount = 0;    // ... how many there were; 0: the last iteration ran its whole dt
     double encounterTime = 0;            // ... and the model time that iteration had advanced
+    bool contactStop = false;            // integrators 3 and 4: an iteration ends behind the substep in which two bodies touch
+    T contactScale = 1;                  // ... their radii being the bodies' own times this
+    std::vector<Encounter> contacts;     // (i, contact partner of i, gap2) of that substep, sorted by i (the device keeps 4096)
+    unsigned long contactCount = 0;
+    double contactTime = 0;
 
   public:
     // integrator: murbhip option "integrator" — 0 (false) the reference's update, 1 (true) kick-drift-kick leapfrog,
@@ -72,6 +77,18 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     unsigned long getEncounterCount() const { return encounterCount; }
     double getEncounterTime() const { return encounterTime; }
     const std::vector<Encounter> &getEncounters() const { return encounters; }
+    // hip+hermite+adaptive / hip+hermite+block (murbhip_upload_radii, option "contact" 2): uploads the bodies' own radii
+    // (dataSoA.r) times `scale` and ends an iteration behind the substep in which a body that took it touches another:
+    // |q_j - q_i|^2 <= (r_i + r_j)^2, formed as include/murbhip.h defines gap2.  Excludes an encounter radius.  false for the
+    // fixed-step integrators, for a scale that is not finite and positive, and beside an encounter radius.  In getContacts()
+    // the member r2 of an entry holds gap2.
+    bool setContactStop(const bool on, const T scale = 1);
+    bool hasContactStop() const { return contactStop; }
+    T getContactScale() const { return contactScale; }
+    void readContacts();
+    unsigned long getContactCount() const { return contactCount; }
+    double getContactTime() const { return contactTime; }
+    const std::vector<Encounter> &getContacts() const { return contacts; }
 };
 
 #endif

@@ -45,6 +45,8 @@ std::string MetricsFile;    // --csv: where hip+tracking / hip+leapfrog / hip+he
 double Eta = 0.02;          // --eta: accuracy parameter of hip+hermite+adaptive's and hip+hermite+block's step criterion
 int Kmax = 12;              // --kmax: hip+hermite+block, the deepest level (steps down to dt 2^-kmax)
 float Renc = 0.f;           // --renc: hip+hermite+adaptive / hip+hermite+block, encounter radius (0 = no encounter stop)
+bool Collide = false;       // --collide: hip+hermite+adaptive / hip+hermite+block, stop when two bodies touch (radii times --rscale)
+float Rscale = 1.f;         // --rscale
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -93,6 +95,8 @@ static std::vector<Option> optionTable()
         {"-eta", "accuracy", false, "hip+hermite+adaptive / hip+hermite+block: accuracy parameter of the step criterion (default is 0.02)."},
         {"-kmax", "levels", false, "hip+hermite+block: deepest step level, 0 to 20 (default is 12)."},
         {"-renc", "length", false, "hip+hermite+adaptive / hip+hermite+block: stop when two bodies come within this distance."},
+        {"-collide", "", false, "hip+hermite+adaptive / hip+hermite+block: stop when two bodies touch (sum of their radii)."},
+        {"-rscale", "factor", false, "--collide: the bodies' radii are multiplied by this factor (default is 1)."},
     };
 }
 
@@ -144,6 +148,22 @@ static void argsReader(int argc, char **argv)
             std::cout << "The encounter radius --renc must be positive and finite... exiting." << std::endl;
             exit(-1);
         }
+    }
+    Collide = given("-collide");
+    if (given("-rscale")) {
+        Rscale = stof(reader.get_argument("-rscale"));
+        if (!(Rscale > 0.f) || !std::isfinite(Rscale)) {
+            std::cout << "The radius factor --rscale must be positive and finite... exiting." << std::endl;
+            exit(-1);
+        }
+        if (!Collide) {
+            std::cout << "--rscale needs --collide... exiting." << std::endl;
+            exit(-1);
+        }
+    }
+    if (Collide && Renc > 0.f) {
+        std::cout << "--collide cannot be combined with --renc... exiting." << std::endl;
+        exit(-1);
     }
     if (given("-soft")) {
         Softening = stof(reader.get_argument("-soft"));
@@ -205,6 +225,17 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
     exit(-1);
 }
 
+// --collide, once the bodies are final (after --dinit): the radii go to the device and the contact stop is on
+static void applyCollide(SimulationNBodyHIP<float> *simu)
+{
+    if (!Collide) return;
+    auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu);
+    if (!tracking || !tracking->setContactStop(true, Rscale)) {
+        std::cout << "--collide needs hip+hermite+adaptive or hip+hermite+block... exiting." << std::endl;
+        exit(-1);
+    }
+}
+
 int main(int argc, char **argv)
 {
     argsReader(argc, argv);
@@ -216,6 +247,7 @@ int main(int argc, char **argv)
         }
         std::dynamic_pointer_cast<HIPBodies<float>>(simu->getBodies())->initOnDevice(BodiesScheme, 0);
     }
+    applyCollide(simu);
     NBodies = simu->getBodies()->getN();
     const float Mbytes = simu->getAllocatedBytes() / 1024.f / 1024.f;
 
@@ -268,6 +300,17 @@ int main(int argc, char **argv)
                 std::cout << "encounter: " << e.i << " " << e.j << " " << std::setprecision(9)
                           << std::sqrt(std::max(0.0, (double)e.r2 - (double)Softening * (double)Softening)) << " "
                           << tracking->getEncounterTime() << std::endl;
+            if (History) History->setNumIterations((int)iIte);   // the rows of the iterations that ran
+            iIte++;   // this iteration counts
+            break;
+        }
+        // --collide: likewise an iteration that ended by a contact
+        if (const auto *tracking = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(simu);
+            tracking && Collide && tracking->getContactCount() > 0) {
+            if (Verbose) std::cout << std::endl;
+            for (const auto &e : tracking->getContacts())
+                std::cout << "contact: " << e.i << " " << e.j << " " << std::setprecision(9) << e.r2 << " "
+                          << tracking->getContactTime() << std::endl;
             if (History) History->setNumIterations((int)iIte);   // the rows of the iterations that ran
             iIte++;   // this iteration counts
             break;

@@ -75,6 +75,10 @@ def lib():
         L.murbhip_set_encounter.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_encounters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong, C.POINTER(C.c_ulong),
                                          C.POINTER(C.c_double)]
+        L.murbhip_upload_radii.argtypes = [C.c_void_p, _fp]
+        L.murbhip_download_contact.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp]
+        L.murbhip_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong, C.POINTER(C.c_ulong),
+                                       C.POINTER(C.c_double)]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -95,6 +99,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_compute_acc_jerk murbhip_download_jerk murbhip_evolve murbhip_evolve_dts "
            "murbhip_evolve_block murbhip_block_state murbhip_block_set_levels "
            "murbhip_download_nearest murbhip_set_encounter murbhip_encounters "
+           "murbhip_upload_radii murbhip_download_contact murbhip_contacts "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -304,6 +309,33 @@ class Simulation:
                                             C.byref(time)), "murbhip_encounters")
         return {"i": i, "j": j, "r2": r2, "count": int(count.value), "time": time.value}
 
+    def upload_radii(self, r):
+        """The bodies' radii, n values in the caller's order (include/murbhip.h: murbhip_upload_radii)."""
+        r = _f32(r)
+        if r.shape[0] < self.n:
+            raise ValueError("radii shorter than n")
+        _check(lib().murbhip_upload_radii(self._h, _ptr(r)), "murbhip_upload_radii")
+
+    def contact(self):
+        """(index int32, gap2 float32) of every body's contact partner by radii in the remembered evaluation (option
+        "contact" 1 or 2; include/murbhip.h: murbhip_download_contact).  gap2 <= 0: the two touch."""
+        idx, gap2 = np.zeros(self.n, np.int32), np.zeros(self.n, np.float32)
+        _check(lib().murbhip_download_contact(self._h, idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(gap2)), "murbhip_download_contact")
+        return idx, gap2
+
+    def contacts(self):
+        """dict of the step that ended the last evolve call by a contact ("contact" 2): i, j (int32), gap2 (float32) sorted by
+        i, the count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
+        count, time = C.c_ulong(), C.c_double()
+        ip = C.POINTER(C.c_int)
+        _check(lib().murbhip_contacts(self._h, None, None, None, 0, C.byref(count), C.byref(time)), "murbhip_contacts")
+        kept = min(count.value, 4096)
+        i, j, gap2 = np.zeros(kept, np.int32), np.zeros(kept, np.int32), np.zeros(kept, np.float32)
+        if kept:
+            _check(lib().murbhip_contacts(self._h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(gap2), kept, C.byref(count),
+                                          C.byref(time)), "murbhip_contacts")
+        return {"i": i, "j": j, "gap2": gap2, "count": int(count.value), "time": time.value}
+
     def integrate_host_acc(self, acc, dt):
         a = [_f32(x) for x in acc]
         _check(lib().murbhip_integrate_host_acc(self._h, *[_ptr(x) for x in a], dt), "murbhip_integrate_host_acc")
@@ -350,6 +382,54 @@ class Simulation:
             self.close()
         except Exception:
             pass
+
+
+def merge_contacts(state, radii, i, j):
+    """Host-side resolution of a contact list (Simulation.contacts()): the pairs (i[k], j[k]) are joined transitively into
+    groups, and every group becomes ONE body in the place of its lowest index: mass = the sum, position and velocity = the
+    mass-weighted means (the plain means for an all-massless group), formed in fp64 and rounded once to fp32, radius =
+    cbrt(sum R^3).  The other members are removed; the order of the rest is kept.  n is fixed per context, so the result goes
+    into a new Simulation.  Returns (new state dict, new radii, for every old index the new index it went to)."""
+    radii = np.asarray(radii, np.float32)
+    n = radii.shape[0]
+    parent = np.arange(n)
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for a, b in zip(np.asarray(i, np.int64), np.asarray(j, np.int64)):
+        if not (0 <= a < n and 0 <= b < n):
+            raise ValueError("contact index out of range")
+        ra, rb = find(int(a)), find(int(b))
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)   # the root of a group is its lowest index
+    root = np.array([find(k) for k in range(n)], np.int64)
+    keep = root == np.arange(n)
+    index_map = (np.cumsum(keep) - 1)[root].astype(np.int64)
+    k_new = int(keep.sum())
+    m = np.asarray(state["m"], np.float64)[:n]
+    mass = np.zeros(k_new)
+    np.add.at(mass, index_map, m)
+    members = np.zeros(k_new)
+    np.add.at(members, index_map, 1.0)
+    massless = mass == 0.0
+    weight = np.where(massless[index_map], 1.0, m)          # an all-massless group: the plain mean
+    norm = np.where(massless, members, mass)
+    out = {}
+    for key in FIELDS[:6]:
+        acc = np.zeros(k_new)
+        np.add.at(acc, index_map, weight * np.asarray(state[key], np.float64)[:n])
+        out[key] = (acc / norm).astype(np.float32)
+    out["m"] = mass.astype(np.float32)
+    r3 = np.zeros(k_new)
+    np.add.at(r3, index_map, radii.astype(np.float64) ** 3)
+    new_radii = np.cbrt(r3).astype(np.float32)
+    if "r" in state:
+        out["r"] = new_radii.copy()
+    return out, new_radii, index_map
 
 
 # ====================================================================== host mirror (libmurbhost.so)
@@ -401,6 +481,9 @@ def host_lib():
         H.murbhost_sim_set_encounter.argtypes = [C.c_void_p, C.c_float]
         H.murbhost_sim_encounters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                               C.POINTER(C.c_ulong), _dp]
+        H.murbhost_sim_set_contact.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
+                                            C.POINTER(C.c_ulong), _dp]
         _host = H
     return _host
 
@@ -439,15 +522,23 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0):
+                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
         driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
         `hip+hermite+block`, option 2 driven by murbhip_evolve_block: an iteration is one block of dt, every body in steps of
         its own size dt 2^-k, k <= kmax, with accuracy parameter eta).  encounter=R (integrator 3 or 4): an iteration ends
-        behind the substep in which a body has its nearest neighbour within R; encounters() then has the pairs."""
+        behind the substep in which a body has its nearest neighbour within R; encounters() then has the pairs.  contact=True
+        (integrator 3 or 4, not beside encounter=): it ends behind the substep in which two bodies touch, their radii being
+        the scheme's times rscale; contacts() then has the pairs."""
         if integrator is None:
             integrator = int(bool(leapfrog))
+        if contact and integrator not in (3, 4):
+            raise ValueError("contact= needs integrator 3 or 4")
+        if contact and encounter:
+            raise ValueError("contact= cannot be combined with encounter=")
+        if contact and not (np.isfinite(rscale) and rscale > 0):
+            raise ValueError("rscale= must be finite and positive")
         arr = (C.c_int * len(devices))(*devices)
         self.H = host_lib()
         ex = {"copy": 0, "rccl": 1}[exchange]
@@ -461,6 +552,9 @@ class HostSim:
         if encounter:
             if self.H.murbhost_sim_set_encounter(self.h, encounter) != 0:
                 raise ValueError("encounter= needs integrator 3 or 4")
+        if contact:
+            if self.H.murbhost_sim_set_contact(self.h, 1, rscale) != 0:
+                raise ValueError("contact= needs integrator 3 or 4")
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
@@ -475,6 +569,20 @@ class HostSim:
             self.H.murbhost_sim_encounters(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(r2), kept, C.byref(count),
                                            C.byref(time))
         return {"i": i, "j": j, "r2": r2, "count": int(count.value), "time": time.value}
+
+    def contacts(self):
+        """integrator 3 / 4 with contact=True: dict of the substep that ended the last iteration by a contact
+        (Simulation.contacts' keys; count 0 when it ran its whole dt); None where the feature does not apply."""
+        count, time = C.c_ulong(), C.c_double()
+        ip = C.POINTER(C.c_int)
+        if self.H.murbhost_sim_contacts(self.h, None, None, None, 0, C.byref(count), C.byref(time)) != 0:
+            return None
+        kept = min(count.value, 4096)
+        i, j, gap2 = np.zeros(kept, np.int32), np.zeros(kept, np.int32), np.zeros(kept, np.float32)
+        if kept:
+            self.H.murbhost_sim_contacts(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(gap2), kept, C.byref(count),
+                                         C.byref(time))
+        return {"i": i, "j": j, "gap2": gap2, "count": int(count.value), "time": time.value}
 
     def block_counts(self):
         """integrator=4: (block steps so far, body-steps, clamped steps); None for the other plugins."""

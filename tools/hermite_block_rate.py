@@ -10,10 +10,10 @@ Host clock around calls that end in a device sync, K block steps a call in batch
 batch: one block step with "evolve_batch" 64 (63 x 6 launches find the done flag set) against "evolve_batch" 1.
 
     python tools/hermite_block_rate.py [--sizes 30000,200000] [--active 1,16,256,4096,0] [--units 0,256,640,2560,5120]
-                                       [--rounds 3] [--seconds 0.1] [--nearest]
+                                       [--rounds 3] [--seconds 0.1] [--nearest | --contact]
 
 (active 0 = all bodies, units 0 = the default.  --nearest: every cell is timed twice in every round, with option "nearest" 0 and
-1, and a second table has the ratio 1 / 0.)  Prints per size a table of median microseconds per block step."""
+1, and a second table has the ratio 1 / 0; --contact: the same with option "contact" and the scheme's own radii.)  Prints per size a table of median microseconds per block step."""
 import argparse
 import os
 import statistics
@@ -62,7 +62,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=0.1, help="length of one timed window (sets K per case)")
     ap.add_argument("--nearest", action="store_true", help='also time every cell with option "nearest" 1')
+    ap.add_argument("--contact", action="store_true", help='also time every cell with option "contact" 1 (not beside --nearest)')
     args = ap.parse_args()
+    assert not (args.nearest and args.contact), "--nearest and --contact exclude each other, like the options"
+    extra = "contact" if args.contact else "nearest" if args.nearest else None
     assert murbhip.device_count() > 0, "needs an MI355X: there is nothing to time without one"
     units = [int(x) for x in args.units.split(",")]
     print(f"# {args.rounds} alternating rounds, windows of ~{args.seconds} s, host clock around synced calls; microseconds per step")
@@ -72,6 +75,8 @@ def main():
         with murbhip.Simulation(n) as sim:
             sim.set_option("integrator", 2)
             sim.upload(s)
+            if args.contact:
+                sim.upload_radii(s["r"])
             sim.warmup(100.0)
             print(f"N = {n}: {int(sim.info('cu_count'))} CUs, sweep grid {int(sim.info('block_grid'))} workgroups, default "
                   f"block_units {int(sim.info('block_units'))}, {int(sim.info('slots')) // 512} layout tiles")
@@ -93,18 +98,18 @@ def main():
             fix, fix_near = [], []
             for _ in range(args.rounds):
                 fix.append(fixed(sim, s, k_fixed))
-                if args.nearest:
-                    sim.set_option("nearest", 1)
+                if extra:
+                    sim.set_option(extra, 1)
                     fix_near.append(fixed(sim, s, k_fixed))
-                    sim.set_option("nearest", 0)
+                    sim.set_option(extra, 0)
                 for u in units:
                     sim.set_option("block_units", u)
                     for m in active:
                         times[(u, m)].append(block(sim, s, levels[m], k_of[m]))
-                        if args.nearest:
-                            sim.set_option("nearest", 1)
+                        if extra:
+                            sim.set_option(extra, 1)
                             near[(u, m)].append(block(sim, s, levels[m], k_of[m]))
-                            sim.set_option("nearest", 0)
+                            sim.set_option(extra, 0)
             sim.set_option("block_units", 0)
             tail = [block(sim, s, levels[active[0]], 1, 64) - block(sim, s, levels[active[0]], 1, 1) for _ in range(max(args.rounds, 5))]
         mf = statistics.median(fix)
@@ -113,11 +118,11 @@ def main():
         print("    units \\ active " + "".join(f"{m:>12d}" for m in active))
         for u in units:
             print(f"    {u:>14d} " + "".join(f"{statistics.median(times[(u, m)]) * 1e6:12.1f}" for m in active))
-        if args.nearest:
+        if extra:
             mn = statistics.median(fix_near)
-            print(f"  murbhip_steps with \"nearest\" 1: median {mn * 1e6:.1f} ({mn / mf:.3f} of the plain step)   rounds: "
+            print(f"  murbhip_steps with \"{extra}\" 1: median {mn * 1e6:.1f} ({mn / mf:.3f} of the plain step)   rounds: "
                   + ", ".join(f"{x * 1e6:.1f}" for x in fix_near))
-            print("  block step with \"nearest\" 1, median, and its ratio to \"nearest\" 0")
+            print(f"  block step with \"{extra}\" 1, median, and its ratio to \"{extra}\" 0")
             for u in units:
                 print(f"    {u:>14d} " + "".join(f"{statistics.median(near[(u, m)]) * 1e6:12.1f}" for m in active))
                 print(f"    {'ratio':>14s} " + "".join(f"{statistics.median(near[(u, m)]) / statistics.median(times[(u, m)]):12.3f}" for m in active))

@@ -2,10 +2,11 @@
 """Rate of the Hermite integrator's acceleration + jerk sweep against the one-sided force kernel ("variant" 1), timed
 with HIP events ("profile" 1, force_ms_avg) in the same process after murbhip_warmup, alternating A B A B.
 
-    python tools/hermite_rate.py [--sizes 30000,200000] [--reps 10] [--rounds 2] [--nearest]
+    python tools/hermite_rate.py [--sizes 30000,200000] [--reps 10] [--rounds 2] [--nearest] [--contact]
 
 Prints, per size: ms per sweep, pairs per second (N^2 / time) and the ratio of the two kernels.  --nearest: a third leg in
-every round, the sweep with option "nearest" 1 (the nearest-neighbour kernel), and its ratio to the plain sweep."""
+every round, the sweep with option "nearest" 1 (the nearest-neighbour kernel), and its ratio to the plain sweep.  --contact:
+likewise a leg with option "contact" 1 (the contact kernel) and the scheme's own radii."""
 import argparse
 import os
 import sys
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--nearest", action="store_true", help='also time the sweep with option "nearest" 1')
+    ap.add_argument("--contact", action="store_true", help='also time the sweep with option "contact" 1')
     args = ap.parse_args()
     print(f"# {murbhip.device_count()} device(s); reps {args.reps}, rounds {args.rounds}; times are HIP-event spans of single launches")
     for n in (int(x) for x in args.sizes.split(",")):
@@ -36,7 +38,9 @@ def main():
             sim.upload(s)
             sim.set_option("fuse_integrate", 0)   # the yardstick's span is the force launch alone, as the sweep's is
             sim.warmup(100.0)
-            one, herm, near = [], [], []
+            if args.contact:
+                sim.upload_radii(s["r"])
+            one, herm, near, cont = [], [], [], []
             for _ in range(args.rounds):
                 sim.set_option("integrator", 0)
                 sim.set_option("variant", 1)
@@ -48,6 +52,10 @@ def main():
                     sim.set_option("nearest", 1)
                     near.append(timed(sim, args.reps, 3600.0))
                     sim.set_option("nearest", 0)
+                if args.contact:
+                    sim.set_option("contact", 1)
+                    cont.append(timed(sim, args.reps, 3600.0))
+                    sim.set_option("contact", 0)
             sim.set_option("profile", 0)
             cus = int(sim.info("cu_count"))
         a = sum(t for t, _ in one) / len(one)
@@ -64,6 +72,11 @@ def main():
             print(f"  sweep with nearest neighbours     : {c:9.4f} ms per sweep  {pairs / c * 1e3:.3e} pairs/s   rounds: "
                   + ", ".join(f"{t:.4f} ms x {k}" for t, k in near))
             print(f"  ratio nearest 1 / nearest 0       : {c / b:.3f}")
+        if cont:
+            c = sum(t for t, _ in cont) / len(cont)
+            print(f"  sweep with contacts by radii      : {c:9.4f} ms per sweep  {pairs / c * 1e3:.3e} pairs/s   rounds: "
+                  + ", ".join(f"{t:.4f} ms x {k}" for t, k in cont))
+            print(f"  ratio contact 1 / contact 0       : {c / b:.3f}")
 
 
 if __name__ == "__main__":
