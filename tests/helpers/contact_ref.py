@@ -115,3 +115,23 @@ def check_candidates(idx, gap2, q, radii, soft2, rows=None):
     accepted = (gj <= best[rows] + bj).all()
     err = np.abs(gap2[rows].astype(np.float64) - gj) / bj
     return bool(accepted), float(err.max()) if len(rows) else 0.0
+
+
+dense_lattice, shifted = N.dense_lattice, N.shifted      # the same bodies and the same shift serve both searches
+
+
+def dense_radii(n, seed=1):
+    """Radii for dense_lattice(n, seed): multiples of 0.5 from {0, 0.5, 1, 1.5} with weights (.5, .3, .15, .05), so that grid
+    neighbours (one unit apart) overlap, touch exactly (s = 1) or miss each other, many of them at equal gap2, and a larger
+    body further away often beats the nearest one."""
+    rng = np.random.default_rng(seed + 104729)
+    return rng.choice(np.array([0.0, 0.5, 1.0, 1.5], np.float32), size=n, p=[0.5, 0.3, 0.15, 0.05]).astype(np.float32)
+
+
+def gap2_matrix(q_int, radii, soft2):
+    """fp32 gap2 (n, n) of a lattice, +inf on the diagonal; _exact_gap2's asserts hold for every pair."""
+    qi = np.asarray(q_int, np.int64)
+    n = qi.shape[1]
+    g = _exact_gap2(qi, np.asarray(radii, np.float32)[:n], soft2, 0, n)
+    g[np.arange(n), np.arange(n)] = np.inf
+    return g

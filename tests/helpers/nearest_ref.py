@@ -100,3 +100,107 @@ def lattice(n, seed=1):
     s = {"qx": q[0].astype(np.float32), "qy": q[1].astype(np.float32), "qz": q[2].astype(np.float32),
          "vx": v[0], "vy": v[1], "vz": v[2], "m": m}
     return s, np.float32(0.5)
+
+
+def dense_side(n):
+    """The smallest side of a cubic grid with side^3 >= 1.07 n cells."""
+    side = 1
+    while side ** 3 < 1.07 * n:
+        side += 1
+    return side
+
+
+DENSE_PAIRS = ((10, 11), (12, 1500))      # (kept, moved onto it): inside a slot pair, across tiles; (13, n - 2) is the third
+DENSE_TRIPLE = (14, 600, 1100)            # one point, three tiles
+DENSE_PARTNER = 700                       # the body of tile 1 that body n - 1 sits next to
+DENSE_MASSLESS = (12, 700)                # the winners of bodies 1500 and n - 1
+
+
+def shifted(q_int, seed=1):
+    """(q2_int, k): q2 = q_int[:, pi] for a seeded permutation pi of the bodies, the same points held by other bodies, and
+    k = q2 - q_int (integers).  With dt = 2^-30 and velocities k 2^30 (exact in fp32) the Hermite predictor takes every body
+    from q to q2 exactly: v dt = k, and the acceleration and jerk terms stay far below half an ulp of a coordinate >= 1."""
+    q_int = np.asarray(q_int, np.int64)
+    pi = np.random.default_rng(seed + 7919).permutation(q_int.shape[1])
+    q2 = q_int[:, pi].copy()
+    return q2, q2 - q_int
+
+
+def dense_lattice(n, seed=1):
+    """(state dict, soft, q_int): n >= 2049 bodies on n cells of a full cubic grid of spacing 1 (dense_side(n) cells a side,
+    coordinates from 3 up), chosen and ordered by a seeded permutation, so that the six neighbours of a cell carry unrelated
+    indices: nearly every body has several nearest bodies at the same r2 = 1.25, in several layout tiles, lanes and lane steps.
+    Softening 0.5, masses from [1, 2), integer coordinates >= 1: every r2 is exact in fp32.  Written over grid bodies:
+      body 0                   at (1, 1, 1), alone: the padding slots at the origin would be its nearest if they were candidates
+      bodies n - 1 and 700     one unit apart, 4 and more beyond the grid's far corner: each is the other's only nearest; n - 1
+                               lies in the last tile that holds bodies, 700 in tile 1
+      bodies 10 = 11, 12 = 1500, 13 = n - 2      on one point each: inside a slot pair, across tiles, with the last but one
+      bodies 14 = 600 = 1100   one point in three tiles; for all of these r2 = soft^2 exactly, like the body's own term
+      bodies 12 and 700        massless, and the winners of bodies 1500 and n - 1
+    The velocities are shifted(q_int, seed)'s k times 2^30: one predictor step of 2^-30 moves the bodies onto q2."""
+    assert n >= 2049
+    rng = np.random.default_rng(seed)
+    side = dense_side(n)
+    g = np.arange(side, dtype=np.int64)
+    cells = np.stack(np.meshgrid(g, g, g, indexing="ij")).reshape(3, -1) + 3
+    q = cells[:, rng.permutation(side ** 3)[:n]].copy()
+    q[:, 0] = 1
+    far = side + 6
+    q[:, DENSE_PARTNER] = (far, far, far)
+    q[:, n - 1] = (far, far, far + 1)
+    for a, b in DENSE_PAIRS + ((13, n - 2),):
+        q[:, b] = q[:, a]
+    for b in DENSE_TRIPLE[1:]:
+        q[:, b] = q[:, DENSE_TRIPLE[0]]
+    m = rng.uniform(1.0, 2.0, n).astype(np.float32)
+    m[list(DENSE_MASSLESS)] = 0.0
+    _, k = shifted(q, seed)
+    v = (k.astype(np.float64) * 2.0 ** 30).astype(np.float32)
+    assert q.min() >= 1 and np.array_equal(v.astype(np.float64), k * 2.0 ** 30)
+    s = {"qx": q[0].astype(np.float32), "qy": q[1].astype(np.float32), "qz": q[2].astype(np.float32),
+         "vx": v[0], "vy": v[1], "vz": v[2], "m": m}
+    return s, np.float32(0.5), q
+
+
+def r2_matrix(q_int, soft2):
+    """fp32 r2 (n, n) of a lattice, +inf on the diagonal; asserts that every value is exact in fp32."""
+    qi = np.asarray(q_int, np.int64)
+    n = qi.shape[1]
+    d2 = np.zeros((n, n), np.int64)
+    for c in qi:
+        d = c[None, :] - c[:, None]
+        d2 += d * d
+    want = d2.astype(np.float64) + float(soft2)
+    r2 = want.astype(np.float32)
+    assert np.array_equal(r2.astype(np.float64), want), "r2 is not exact in fp32"
+    r2[np.arange(n), np.arange(n)] = np.inf
+    return r2
+
+
+def tie_stats(values):
+    """Of an (n, n) matrix of candidate values (+inf on the diagonal), per row: the number of candidates at the row's minimum,
+    the number of layout tiles they lie in, and whether one lies in the row's own tile and another outside it."""
+    n = values.shape[0]
+    tie = values == values.min(1)[:, None]
+    per_tile = np.stack([tie[:, lo:lo + TILE].any(1) for lo in range(0, n, TILE)], 1)
+    own = per_tile[np.arange(n), np.arange(n) // TILE]
+    span = per_tile.sum(1)
+    return tie.sum(1), span, own & (span >= 2)
+
+
+def highest_index_wins(values):
+    """A deliberately wrong rule: the highest index among equal values."""
+    n = values.shape[0]
+    return (n - 1 - values[:, ::-1].argmin(1)).astype(np.int32)
+
+
+def later_tile_wins(values):
+    """A deliberately wrong rule: every tile's own (correct) minimum, but in the fold over the tiles a later tile wins a tie."""
+    n = values.shape[0]
+    best, idx = np.full(n, np.inf, values.dtype), np.full(n, -1, np.int32)
+    for lo in range(0, n, TILE):
+        k = values[:, lo:lo + TILE].argmin(1)
+        v = values[np.arange(n), k + lo]
+        take = v <= best
+        best, idx = np.where(take, v, best), np.where(take, k + lo, idx).astype(np.int32)
+    return idx

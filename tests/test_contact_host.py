@@ -10,6 +10,7 @@ import shutil
 import subprocess
 import sys
 import tempfile
+from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -188,3 +189,52 @@ def test_contact_kernels_use_no_scratch():
         records = 4 * 4      # lane steps of a tile x records of a lane step
         assert plain_lds["ds_read_b128"] <= got_lds["ds_read_b128"] <= records, f"{want}: {dict(got_lds)}, plain sweep {dict(plain_lds)}"
         assert sum(got_lds.values()) <= records, f"{want}: LDS reads {dict(got_lds)}: more than one per record"
+
+
+# ------------------------------------------------------------------------------------------------------ the dense tie lattice
+DENSE_N = (2049, 2561, 4609)
+
+
+@lru_cache(maxsize=None)
+def dense(n):
+    """(q, q2, radii, gap2 matrix of q, of q2): conditions on the inputs of tests/test_tie_lattice_gpu.py, not measurements.
+    Forming the matrices runs _exact_gap2's asserts on every pair: r2, e, s and gap2 are exact in fp32."""
+    s, soft, q = CR.dense_lattice(n)
+    q2, _ = CR.shifted(q)
+    radii = CR.dense_radii(n)
+    assert set(np.unique(radii)) <= {0.0, 0.5, 1.0, 1.5}
+    return q, q2, radii, CR.gap2_matrix(q, radii, 0.25), CR.gap2_matrix(q2, radii, 0.25)
+
+
+@pytest.mark.parametrize("n", DENSE_N)
+def test_dense_lattice_contacts(n):
+    """Overlaps, exact touches and misses all occur, many rows are ties, most partners are not the nearest body, and the wrong
+    tie rule changes the answer."""
+    q, q2, radii, gm, gm2 = dense(n)
+    idx, gap2 = CR.contact(q, radii, 0.25)
+    assert np.array_equal(idx, gm.argmin(1)) and np.array_equal(bits(gap2), bits(gm.min(1))) and not np.signbit(gap2[gap2 == 0]).any()
+    cnt, span, own = N.tie_stats(gm)
+    high = N.highest_index_wins(gm)
+    nn = N.nearest(q, 0.25, exact=True)[0]
+    idx2 = CR.contact(q2, radii, 0.25)[0]
+    frac = [float(np.mean(c)) for c in (gap2 < 0, gap2 == 0, gap2 > 0)]
+    print(f"n = {n}: gap2 < 0 / == 0 / > 0: {frac[0]:.3f} / {frac[1]:.3f} / {frac[2]:.3f}; ties {np.mean(cnt >= 2):.3f} (over >= 2 "
+          f"tiles {np.mean(span >= 2):.3f}); partner is not the nearest {np.mean(idx != nn):.3f}; highest index changes "
+          f"{np.mean(high != idx):.3f}; shift changes {np.mean(idx2 != idx):.3f}")
+    assert min(frac) >= 0.05
+    assert np.mean(cnt >= 2) >= 0.20 and np.mean(idx != nn) >= 0.50 and np.mean(high != idx) >= 0.20
+    assert np.mean(idx2 != idx) >= 0.90, "a refresh that does nothing would not show"
+    assert (gap2[idx] <= gap2).all()
+    for a, b in N.DENSE_PAIRS + ((13, n - 2),) + tuple(zip(N.DENSE_TRIPLE, N.DENSE_TRIPLE[1:])):      # on one point: e = 0
+        assert gm[a, b] == -np.float32(radii[a] + radii[b]) ** 2
+
+
+@pytest.mark.parametrize("n", DENSE_N)
+def test_dense_lattice_chunked(n):
+    q, q2, radii, gm, gm2 = dense(n)
+    tiles = -(-n // 1024) * 2
+    for pos, m in ((q, gm), (q2, gm2)):
+        idx, gap2 = m.argmin(1).astype(np.int32), m.min(1)
+        for chunks in (1, 2, 3, 4, 6, 8):
+            got_idx, got_gap2 = CR.chunked(pos, radii, 0.25, n, tiles, chunks)
+            assert np.array_equal(got_idx, idx) and np.array_equal(bits(got_gap2), bits(gap2)), chunks

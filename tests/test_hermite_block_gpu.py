@@ -20,6 +20,7 @@ import hermite_adaptive_ref as A   # noqa: E402
 import hermite_block_ref as B      # noqa: E402
 import hermite_probe as P          # noqa: E402
 import hermite_ref as H            # noqa: E402
+from active_sets import active_sets   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -209,18 +210,6 @@ def test_single_step_replay(gpu, O, name, steps):
 # ------------------------------------------------------------------------------------------------------- 3. active-set shapes
 SHAPE_KMAX = 2                         # the active bodies at level 2 (steps of one tick), the others at level 0
 SHAPE_DT_MAX = np.float32(4.0) * DT    # ... so that the step is DT for the active ones
-SIZES = (1, 3, 4, 5, 15, 16, 17, 64, 65)
-
-
-def active_sets(n):
-    """Active sets of 1 ... n bodies.  The places: slot 0, both halves of a pair, the last slot of a tile and the first of the
-    next, the last real body before the padding; the rest spread evenly."""
-    special = [0, n - 1, 511, 512, 1022, 1023, 1, 1024]
-    spread = [int(x) for x in np.linspace(2, n - 2, 97).astype(np.int64) if int(x) not in special]
-    order = special + spread
-    sets = [[b] for b in (0, 511, 512, n - 1)] + [[1022, 1023]] + [order[:m] for m in SIZES if m > 1]
-    sets += [list(range(1, n)), list(range(n))]
-    return [np.array(sorted(set(x)), np.int64) for x in sets]
 
 
 @lru_cache(maxsize=None)

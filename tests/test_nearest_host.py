@@ -9,6 +9,7 @@ import shutil
 import subprocess
 import sys
 import tempfile
+from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -124,3 +125,75 @@ def test_nearest_kernels_use_no_scratch():
     assert len(plain) > 100
     for want in ("murb_nn_sweep_kernel", "murb_nn_active_sweep_kernel"):
         assert packed(next(k for k in re.findall(r"^(_Z\w*" + want + r"\w*):", text, re.M))) == plain, want
+
+
+# ------------------------------------------------------------------------------------------------------ the dense tie lattice
+DENSE_N = (2049, 2561, 4609)
+
+
+@lru_cache(maxsize=None)
+def dense(n):
+    """(state, q, q2, k, r2 matrix of q, of q2): conditions on the inputs of tests/test_tie_lattice_gpu.py, not measurements."""
+    s, soft, q = N.dense_lattice(n)
+    assert soft == np.float32(0.5)
+    q2, k = N.shifted(q)
+    return s, q, q2, k, N.r2_matrix(q, 0.25), N.r2_matrix(q2, 0.25)
+
+
+@pytest.mark.parametrize("n", DENSE_N)
+def test_dense_lattice_ties(n):
+    """Nearly every row of the dense lattice is a tie, most ties span tiles and cross the border of the body's own tile, and a
+    wrong tie rule changes the answer almost everywhere."""
+    s, q, q2, k, r2m, r2m2 = dense(n)
+    idx, r2 = N.nearest(q, 0.25, exact=True)
+    assert np.array_equal(idx, r2m.argmin(1)) and np.array_equal(r2, r2m.min(1))
+    cnt, span, own = N.tie_stats(r2m)
+    high, later = N.highest_index_wins(r2m), N.later_tile_wins(r2m)
+    idx2 = N.nearest(q2, 0.25, exact=True)[0]
+    print(f"n = {n}: ties {np.mean(cnt >= 2):.3f}, over >= 2 tiles {np.mean(span >= 2):.3f}, own tile and outside {np.mean(own):.3f}; "
+          f"highest index changes {np.mean(high != idx):.3f}, later tile {np.mean(later != idx):.3f}; shift changes {np.mean(idx2 != idx):.3f}")
+    assert np.mean(cnt >= 2) >= 0.90 and np.mean(span >= 2) >= 0.80
+    # A tie mate lies in the body's own tile with probability 511 / (n - 1) under the random order: with the 4 to 5 mates of a
+    # grid body that is 1 - (1 - 511 / (n - 1))^c = 0.68 ... 0.76 of the rows at 2 049 (5 tiles), 0.59 ... 0.67 at 2 561 (6) and
+    # 0.38 ... 0.44 at 4 609 (10).  The tie tests on the device run at the first two sizes, where the floor is one half; the
+    # third only fills the hit lists, and its floor keeps the same distance from what the order can give.
+    assert np.mean(own) >= (0.50 if n < 4609 else 0.30)
+    assert np.mean(high != idx) >= 0.90 and np.mean(later != idx) >= 0.80
+    assert np.mean(idx2 != idx) >= 0.90, "a refresh that does nothing would not show"
+    assert (idx >= 0).all() and (idx < n).all() and (idx != np.arange(n)).all()
+
+
+@pytest.mark.parametrize("n", DENSE_N)
+def test_dense_lattice_specials(n):
+    s, q, q2, k, r2m, r2m2 = dense(n)
+    idx, r2 = N.nearest(q, 0.25, exact=True)
+    assert q.min() >= 1 and q2.min() >= 1 and (q[:, 0] == 1).all() and r2[0] > 3.25 and 0 < idx[0] < n
+    assert np.flatnonzero(idx == n - 1).tolist() == [N.DENSE_PARTNER] and idx[n - 1] == N.DENSE_PARTNER
+    assert (r2m[n - 1] == r2[n - 1]).sum() == 1 and (r2m[N.DENSE_PARTNER] == r2[N.DENSE_PARTNER]).sum() == 1
+    assert N.DENSE_PARTNER // N.TILE == 1 and (n - 1) // N.TILE == (n - 1) // 512 and (n - 1) % N.TILE < N.TILE - 1
+    for a, b in N.DENSE_PAIRS + ((13, n - 2),):
+        assert idx[a] == b and idx[b] == a and r2[a] == r2[b] == np.float32(0.25)
+    assert N.DENSE_PAIRS[0][0] // 2 == N.DENSE_PAIRS[0][1] // 2 and N.DENSE_PAIRS[1][0] // N.TILE != N.DENSE_PAIRS[1][1] // N.TILE
+    t = N.DENSE_TRIPLE
+    assert len({b // N.TILE for b in t}) == 3 and (r2[list(t)] == np.float32(0.25)).all()
+    assert idx[t[0]] == t[1] and idx[t[1]] == t[0] and idx[t[2]] == t[0]
+    for b in N.DENSE_MASSLESS:
+        assert s["m"][b] == 0.0 and (idx == b).any()
+    assert (s["m"] == 0.0).sum() == 2 and s["m"].max() < 2.0 and s["m"][s["m"] > 0].min() >= 1.0
+    # the shift: the same points held by other bodies, and velocities that carry every body there in one step of 2^-30
+    assert np.array_equal(np.sort(q2.T.tolist(), 0), np.sort(q.T.tolist(), 0)) and np.array_equal(q + k, q2)
+    v = np.stack([s[f] for f in ("vx", "vy", "vz")]).astype(np.float64)
+    assert np.array_equal(v * 2.0 ** -30, k) and np.abs(v).max() <= 2.0 ** 35
+    assert np.array_equal(np.stack([s[f] for f in ("qx", "qy", "qz")]).astype(np.int64), q)
+
+
+@pytest.mark.parametrize("n", DENSE_N)
+def test_dense_lattice_chunked(n):
+    """However the tiles are cut into chunks, the fold gives the brute force, before and after the shift."""
+    s, q, q2, k, r2m, r2m2 = dense(n)
+    tiles = -(-n // 1024) * 2
+    for pos, m in ((q, r2m), (q2, r2m2)):
+        idx, r2 = m.argmin(1).astype(np.int32), m.min(1)
+        for chunks in (1, 2, 3, 4, 6, 8):
+            got_idx, got_r2 = N.chunked(pos, 0.25, n, tiles, chunks)
+            assert np.array_equal(got_idx, idx) and np.array_equal(got_r2.view(np.uint32), r2.view(np.uint32)), chunks
