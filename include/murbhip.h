@@ -350,6 +350,41 @@ int murbhip_upload_radii(murbhip_ctx* ctx, const float* r);
 int murbhip_download_contact(murbhip_ctx* ctx, int* idx, float* gap2);
 int murbhip_contacts(murbhip_ctx* ctx, int* i, int* j, float* gap2, unsigned long capacity, unsigned long* count, double* time);
 
+/* Per-body potential beside the Hermite sweeps ("integrator" 2): the quantity the force arithmetic forms on the way to the
+ * pair factor, kept instead of thrown away — one more packed instruction per pair of interactions, no second N^2 pass.
+ *   Definition.  For every real body i, massless ones included,
+ *       phi_i = sum over real bodies j != i of  G m_j * inv_ij
+ *   with inv_ij the sweep's own v_rsq_f32 of its own fp32 r2_ij = fma(dz,dz, fma(dy,dy, fma(dx,dx, soft2))): every term is the
+ *   sweep's own G m_j * inv.  The sign is positive, like the "energy_sweep" potential phi_i = sum_j G m_j / r.  The body's own
+ *   term G m_i / soft is left out BY SLOT: it is never added to an fp32 sum and subtracted again (with a small softening it is
+ *   orders of magnitude above the pair terms and would take their low bits with it).  Another real body at the same position
+ *   does count, with G m_j / soft: the exclusion is by slot, not by d == 0 or r2 == soft2.  Padding has G m = 0 and adds
+ *   exactly +0.  A lone body gets +0.0f; with soft == 0 the forces' rule holds (NaN).  Summation is fp32 throughout — the
+ *   lanes, the wave, then the partial rows in chunk order beside (a1, j1) — so the value depends on "jsplit" / "block_units"
+ *   only through that cut, like the accelerations, and is bit-reproducible from run to run.  Domain: G m / r a normal fp32
+ *   number, as murbhip_create already requires.  The values belong to the evaluation that produced them, like (a1, j1) and
+ *   (nn, r2): after murbhip_compute_acc_jerk the current state, after a step that step's PREDICTED end state; under block
+ *   steps only the active bodies' entries are refreshed and an inactive body keeps its phi bit for bit (at a synchronised
+ *   boundary every body was active in the last block step, so all values belong to one state).
+ *   Option "potential" (0 default, 1; other values MURBHIP_E_INVALID; one shard with "integrator" 2 only, MURBHIP_E_STATE
+ *   otherwise, and while it is 1 "integrator" cannot leave 2).  It excludes "nearest" and "contact": setting it to non-zero
+ *   while either is non-zero is MURBHIP_E_STATE, and so is setting either to non-zero while it is 1 (all three use the
+ *   partial rows' fourth floats).  Switching it drops the remembered evaluation and is refused (MURBHIP_E_STATE) while a block
+ *   is open.  With 0 every result is what it was without the option, bit for bit; with 1 accelerations, jerks, states, step
+ *   sizes, levels and ticks are bit-identical to those with 0 under the same "jsplit" / "block_units".
+ * murbhip_download_potential: n entries in the caller's order; waits for enqueued work.  MURBHIP_E_STATE when "potential" is 0
+ *   or no such evaluation is current (murbhip_download_jerk's rule); while a block is open it returns every body's value at
+ *   its own time.
+ * murbhip_potential_energy: *w = -1/2 sum_i m_i phi_i of the remembered evaluation, summed in fp64 on the device in fixed
+ *   order (the block sums of murbhip_energy's metrics, the masses as uploaded).  The download's state rules.  It is allowed
+ *   while a block is open — a diagnostic where murbhip_energy refuses; the bodies' values then sit at their own times.  After
+ *   a step the value belongs to the step's PREDICTED end state, not the corrected one: murbhip_energy remains the energy of
+ *   the current state.
+ * Not covered: several shards or ranks; the other integrators and the pair-symmetric kernel; "potential" together with
+ *   "nearest" or "contact". */
+int murbhip_download_potential(murbhip_ctx* ctx, float* phi);
+int murbhip_potential_energy(murbhip_ctx* ctx, double* w);
+
 /* Untimed device warm-up for about `milliseconds` (0 ... 10 000) of force evaluations on the current state, then a sync.
  * An MI355X needs ~40 ms of work to reach its steady clock after an idle spell (the first 12 ms run 25 % slow, DESIGN.md
  * §4.5) — as long as the reference's whole 200-iteration run at N = 30 000.  Construction is outside the reference's timing
@@ -485,6 +520,9 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *   "contact"        0 (default), 1, 2: the Hermite sweeps also keep every body's contact partner by radii and its gap2; 2 adds
  *                    the contact stop (see murbhip_upload_radii above).  One shard with "integrator" 2 only; excludes "nearest".
  *                    The active sweep then runs on 4 workgroups per CU instead of 5
+ *   "potential"      0 (default), 1: the Hermite sweeps also keep every body's potential phi_i (see murbhip_download_potential
+ *                    above).  One shard with "integrator" 2 only; excludes "nearest" and "contact".  Switching it drops the
+ *                    remembered evaluation.  The active sweep then runs on 4 workgroups per CU instead of 5
  *   "tri_first_pct"  "overlap" 1, pair-symmetric schedule: percentage (0..100, default 50) of the own-slice
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real
@@ -520,7 +558,7 @@ int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
 /* Numeric facts.  Keys: "cu_count", "clock_mhz", "n", "slots", "world", "rank", "jsplit", "variant", "cu_reserve", "sym_passes", "sym_waves", "sym_wide" (the form of the pair factor in use: 0 or 1; 0 on a one-sided plan), "taper",
  * "block_units", "block_grid" (work units and workgroups of murbhip_evolve_block's active sweep), "block_steps", "block_body_steps",
  * "block_clamped", "block_max_active" (the last murbhip_evolve_block call's counts), "nearest" (the option), "encounter_count" (hits of
- * the step that ended the last evolve call: murbhip_encounters' *count), "contact" (the option), "contact_count" (murbhip_contacts' *count),
+ * the step that ended the last evolve call: murbhip_encounters' *count), "contact" (the option), "contact_count" (murbhip_contacts' *count), "potential" (the option),
  * "workgroups", "interactions_per_launch", "device_bytes", "hermite_parts" (j chunks of the acceleration + jerk sweep of
  * "integrator" 2: "jsplit" clamped to the layout tiles and 32, or the automatic rule), and the timing spans of the steps since "profile" was set (HIP
  * events on the library's own streams, all shards of this process; the call drains the device):

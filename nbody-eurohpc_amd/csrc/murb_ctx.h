@@ -104,6 +104,10 @@ struct Shard {
     int* nn_idx = nullptr;                    // per slot: nearest other real body of the remembered evaluation, -1 = none
     float* nn_r2 = nullptr;                   // ... and the sweep's r2 of that pair
     MurbEncList* enc = nullptr;               // the encounter list of the last murbhip_evolve / murbhip_evolve_block
+    // "potential" (Hermite sweeps), allocated on first use (ensure_hermite)
+    float* herm_phi = nullptr;                // per slot: phi_i of the remembered evaluation (include/murbhip.h, "potential")
+    double* pot_sums = nullptr;               // block sums of murbhip_potential_energy
+    double* pot_sums_host = nullptr;          // ... and their pinned host copy
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -187,6 +191,7 @@ struct murbhip_ctx {
     double enc_time = 0.0;          // ... and the model time advanced in that call when they were seen
     // contact by radii (Hermite sweeps); shares the per-slot arrays, the hit list and the counters above with "nearest"
     int contact = 0;                // "contact": 1 the sweeps keep every body's (cp, gap2) beside (a, j), 2 also the contact stop
+    int potential = 0;              // "potential": the sweeps keep every body's phi_i beside (a, j); excludes "nearest" and "contact"
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

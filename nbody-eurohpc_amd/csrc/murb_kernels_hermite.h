@@ -38,13 +38,14 @@ struct MurbJerkArgs {
 
 // ---- one i body against two j bodies (packed): acceleration and jerk ----------------------------------------------
 // 6 pk_add + 6 pk_fma (|d|^2 + soft^2, d.w) + 2 rsq + 5 pk_mul + 9 pk_fma
-// (the _r2 form hands out the pair of |d|^2 + soft^2 the force arithmetic uses: the nearest-neighbour sweeps keep its minimum)
-__device__ __forceinline__ void murb_interact_jerk_pk_r2(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
+// (the _r2 form hands out the pair of |d|^2 + soft^2 the force arithmetic uses: the nearest-neighbour sweeps keep its minimum;
+// the _gi form also the pair of GM_j * inv it makes on the way to s: the potential sweeps keep its sum)
+__device__ __forceinline__ void murb_interact_jerk_pk_gi(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
                                                          const murb_f2 uj, const murb_f2 vj, const murb_f2 wj,
                                                          const float xi, const float yi, const float zi,
                                                          const float ui, const float vi, const float wi, const float soft2,
                                                          murb_f2& ax, murb_f2& ay, murb_f2& az,
-                                                         murb_f2& jx, murb_f2& jy, murb_f2& jz, murb_f2& r2)
+                                                         murb_f2& jx, murb_f2& jy, murb_f2& jz, murb_f2& r2, murb_f2& gi)
 {
     const murb_f2 dx = xj - xi, dy = yj - yi, dz = zj - zi;
     const murb_f2 wx = uj - ui, wy = vj - vi, wz = wj - wi;
@@ -58,7 +59,7 @@ __device__ __forceinline__ void murb_interact_jerk_pk_r2(const murb_f2 xj, const
     inv.x = __builtin_amdgcn_rsqf(r2.x);
     inv.y = __builtin_amdgcn_rsqf(r2.y);
     const murb_f2 inv2 = inv * inv;
-    const murb_f2 gi = gj * inv;
+    gi = gj * inv;
     const murb_f2 s = gi * inv2;            // GM_j * inv^3, never G*inv^3 alone (fp32 range)
     const murb_f2 c = (dw * inv2) * -3.0f;  // -3 (d.w) / (|d|^2 + soft^2)
     ax = __builtin_elementwise_fma(s, dx, ax);
@@ -67,6 +68,17 @@ __device__ __forceinline__ void murb_interact_jerk_pk_r2(const murb_f2 xj, const
     jx = __builtin_elementwise_fma(s, __builtin_elementwise_fma(c, dx, wx), jx);
     jy = __builtin_elementwise_fma(s, __builtin_elementwise_fma(c, dy, wy), jy);
     jz = __builtin_elementwise_fma(s, __builtin_elementwise_fma(c, dz, wz), jz);
+}
+
+__device__ __forceinline__ void murb_interact_jerk_pk_r2(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
+                                                         const murb_f2 uj, const murb_f2 vj, const murb_f2 wj,
+                                                         const float xi, const float yi, const float zi,
+                                                         const float ui, const float vi, const float wi, const float soft2,
+                                                         murb_f2& ax, murb_f2& ay, murb_f2& az,
+                                                         murb_f2& jx, murb_f2& jy, murb_f2& jz, murb_f2& r2)
+{
+    murb_f2 gi;
+    murb_interact_jerk_pk_gi(xj, yj, zj, gj, uj, vj, wj, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, r2, gi);
 }
 
 __device__ __forceinline__ void murb_interact_jerk_pk(const murb_f2 xj, const murb_f2 yj, const murb_f2 zj, const murb_f2 gj,
@@ -394,14 +406,92 @@ __device__ __forceinline__ void murb_ct_test(unsigned int* hits, MurbEncList* li
     if (at < MURB_ENC_CAP) { list->i[at] = i; list->j[at] = (int)idx; list->r2[at] = murb_ct_value(key); }
 }
 
+// ---- per-body potential beside the sweep (option "potential"; include/murbhip.h has the definition) --------------------------
+// phi_i = sum_{j != i} GM_j inv_ij: the sum of the gi the force arithmetic forms anyway, one more packed fma per pair of
+// interactions and R more packed accumulators.  The body's own term GM_i / soft is orders of magnitude above the pair terms
+// where the softening is small, so it never enters an fp32 sum: the accumulation is phi = fma(gi, pm, phi) with a wave-uniform
+// pm that is 0 in the layout tile(s) holding one of the wave's own i bodies and 1 elsewhere (murb_nn_tile's sign, in kind), and
+// such a tile's terms are added behind the loop from the records in memory with the own slot left out (murb_pot_own_tile).
+// Padding has GM = 0: its gi is +0 and needs no mask.  The loop nest keeps ONE copy of the arithmetic.
+template <int RT>
+__device__ __forceinline__ bool murb_pot_tile_own(const int tile, const int (&self_tile)[RT])   // wave-uniform
+{
+    bool m = false;
+#pragma unroll
+    for (int r = 0; r < RT; ++r) m |= self_tile[r] == tile;
+    return m;
+}
+
+template <int R>
+__device__ __forceinline__ void murb_pot_tile(const float4* tq, const float4* tv, const int lane, const bool own,
+                                              const float (&xi)[R], const float (&yi)[R], const float (&zi)[R],
+                                              const float (&ui)[R], const float (&vi)[R], const float (&wi)[R], const float soft2,
+                                              murb_f2 (&ax)[R], murb_f2 (&ay)[R], murb_f2 (&az)[R],
+                                              murb_f2 (&jx)[R], murb_f2 (&jy)[R], murb_f2 (&jz)[R], murb_f2 (&ph)[R])
+{
+    const float pm = own ? 0.f : 1.f;   // wave-uniform
+#pragma unroll
+    for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
+        const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
+        const float4 VA = tv[q + lane], VB = tv[q + lane + MURB_TILE_PAIRS];
+        const murb_f2 xj = {A.x, A.y}, yj = {A.z, A.w}, zj = {B.x, B.y}, gj = {B.z, B.w};
+        const murb_f2 uj = {VA.x, VA.y}, vj = {VA.z, VA.w}, wj = {VB.x, VB.y};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            murb_f2 r2, gi;
+            murb_interact_jerk_pk_gi(xj, yj, zj, gj, uj, vj, wj, xi[r], yi[r], zi[r], ui[r], vi[r], wi[r], soft2,
+                                     ax[r], ay[r], az[r], jx[r], jy[r], jz[r], r2, gi);
+            ph[r] = __builtin_elementwise_fma(gi, (murb_f2)(pm), ph[r]);
+        }
+    }
+}
+
+// GM_j * inv of one i body and one j body behind the loop, in single instructions that give the packed ones' bits
+__device__ __forceinline__ float murb_pot_gi_single(const float xj, const float yj, const float zj, const float gj,
+                                                    const float xi, const float yi, const float zi, const float soft2)
+{
+    const float inv = __builtin_amdgcn_rsqf(murb_nn_r2_single(xj, yj, zj, xi, yi, zi, soft2));
+#if defined(__HIP_DEVICE_COMPILE__)
+    float g;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(g) : "v"(gj), "v"(inv));
+    return g;
+#else
+    return gj * inv;
+#endif
+}
+
+// The terms of one tile that holds own bodies, from the records in memory, every body's own SLOT left out (another body at the
+// same place counts).  Runs after the loop; the order is fixed: lane steps rising, the two slots of a pair in their halves.
+template <int R>
+__device__ __forceinline__ void murb_pot_own_tile(const float4* rec, const int lane, const int tile,
+                                                  const float (&xi)[R], const float (&yi)[R], const float (&zi)[R], const float soft2,
+                                                  murb_f2 (&ph)[R], const int (&self)[R])
+{
+#pragma unroll 1
+    for (int qs = 0; qs < MURB_TILE_PAIRS / 64; ++qs) {
+        const unsigned long ra = (unsigned long)tile * MURB_TILE_F4 + qs * 64 + lane;
+        const float4 A = rec[ra], B = rec[ra + MURB_TILE_PAIRS];
+        const int j0 = tile * MURB_TILE_BODIES + 2 * (qs * 64 + lane);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float gx = murb_pot_gi_single(A.x, A.z, B.x, B.z, xi[r], yi[r], zi[r], soft2);
+            const float gy = murb_pot_gi_single(A.y, A.w, B.y, B.w, xi[r], yi[r], zi[r], soft2);
+            ph[r].x += j0 == self[r] ? 0.f : gx;
+            ph[r].y += j0 + 1 == self[r] ? 0.f : gy;
+        }
+    }
+}
+
 // ---- the sweep -------------------------------------------------------------------------------------------------------
 // grid.x = i groups of WAVES*R bodies, grid.y = j chunks.  LDS: STAGE position tiles + STAGE velocity tiles (16 KiB a stage).
 // The body is a device function so that the adaptive launch (murb_force_jerk_adaptive_kernel, below) runs the same code.
-// MODE 1: the nearest-neighbour form, 2: the contact form (Args = MurbNNJerkArgs); the plain form's code does not change with them.
+// MODE 1: the nearest-neighbour form, 2: the contact form, 3: the potential form (Args = MurbNNJerkArgs); the plain form's code
+// does not change with them.  NN names what the three share (the copy in whole rounds, the kernel arguments read again behind
+// the loop); the potential form (POT) keeps R packed sums in the place of the minima and steps.
 template <int R, int WAVES, int STAGE, int MODE = 0, typename Args = MurbJerkArgs>
 __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
 {
-    constexpr bool NN = MODE != 0, CT = MODE == 2;
+    constexpr bool NN = MODE != 0, CT = MODE == 2, POT = MODE == 3;
     static_assert(R % 2 == 0 && MURB_TILE_BODIES % (WAVES * R) == 0, "i groups must tile the layout");
     __shared__ float4 lds[2 * STAGE * MURB_TILE_F4];
 
@@ -447,11 +537,12 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
     }
     float mn[R];   // NN: the lane's smallest r2 per i body, and the lane step it fell at
     int st[R], self_tile[1] = {0}, count = 0;
+    murb_f2 ph[R];   // POT: the sums of GM_j * inv
     if constexpr (NN) {
-        count = a.count;
+        if constexpr (!POT) count = a.count;
         self_tile[0] = i_slot / MURB_TILE_BODIES;   // a wave's i bodies lie in one layout tile
 #pragma unroll
-        for (int r = 0; r < R; ++r) { mn[r] = __builtin_inff(); st[r] = 0; }
+        for (int r = 0; r < R; ++r) { mn[r] = __builtin_inff(); st[r] = 0; ph[r] = (murb_f2)(0.f); }
     }
 
     for (int vs = vt0; vs < vt1; vs += STAGE) {
@@ -480,6 +571,10 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
         for (int t = 0; t < nt; ++t) {
             const float4* tq = lds + (2 * t) * MURB_TILE_F4;
             const float4* tv = tq + MURB_TILE_F4;
+            if constexpr (POT) {
+                murb_pot_tile<R>(tq, tv, lane, murb_pot_tile_own<1>(vs + t, self_tile), xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
+                continue;
+            }
             if constexpr (NN) {
                 const bool masked = murb_nn_tile_masked<1>(vs + t, self_tile, count);   // wave-uniform
                 if constexpr (CT) murb_ct_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, ri, soft2, ax, ay, az, jx, jy, jz, mn, st);
@@ -501,7 +596,23 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
     }
 
     float nn_a = 0.f, nn_j = 0.f;   // the rows' fourth floats
-    if constexpr (NN) {
+    if constexpr (POT) {
+        const auto* again = murb_kernarg_again<Args>();   // `a` is the kernel's first argument
+        const float4* const rec = again->rec;
+        int self[R], first = i_slot;
+        asm volatile("" : "+s"(first));   // the bodies' slots are made here, not held through the loop
+#pragma unroll
+        for (int r = 0; r < R; ++r) self[r] = first + r;
+        const int tiles = again->tiles, nchunks = again->nchunks;
+        const int t0 = (int)(((long)tiles * chunk) / nchunks), t1 = (int)(((long)tiles * (chunk + 1)) / nchunks);   // vt0, vt1 again
+        const int own = first / MURB_TILE_BODIES;
+        if (own >= t0 && own < t1) murb_pot_own_tile<R>(rec, lane, own, xi, yi, zi, soft2, ph, self);   // wave-uniform
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float sp = murb_wave_sum(ph[r].x + ph[r].y);
+            if (lane == r) nn_a = sp;   // part_j.w stays 0
+        }
+    } else if constexpr (NN) {
         const auto* again = murb_kernarg_again<Args>();   // `a` is the nearest-neighbour kernel's first argument
         const float4* const rec = again->rec;
         const int cnt = again->count;
@@ -579,6 +690,7 @@ struct MurbHermiteArgs {
     float* nn_r2;
     MurbEncList* enc;       // ... and the encounter list of murbhip_evolve
     int contact;            // "contact": the rows' fourth floats are (key of gap2, slot), kept in nn_idx / nn_r2; 2 = with the contact stop
+    float* phi;             // "potential": part_a's fourth floats are partial potentials, added in chunk order beside a1; null = off
 };
 
 __device__ __forceinline__ float murb_hermite_predict_q(float q, float v, float a, float j, double dt, double c2, double c3)
@@ -667,6 +779,7 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
         for (int k = 0; k < 3; ++k) { f.a1[h][k] = 0.f; f.j1[h][k] = 0.f; }
     f.nn_r2[0] = f.nn_r2[1] = a.contact ? MURB_CT_NONE_KEY : MURB_F32_INF_BITS;
     f.nn_idx[0] = f.nn_idx[1] = MURB_NN_NONE;
+    float ph[2] = {0.f, 0.f};
     for (int p = 0; p < a.nparts; ++p) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -674,9 +787,11 @@ __device__ __forceinline__ void murb_hermite_sum_rows(const MurbHermiteArgs& a, 
             const float4 w = a.part_j[(unsigned long)p * n + s0 + h];
             f.a1[h][0] += u.x; f.a1[h][1] += u.y; f.a1[h][2] += u.z;
             f.j1[h][0] += w.x; f.j1[h][1] += w.y; f.j1[h][2] += w.z;
+            if (a.phi) ph[h] += u.w;
             murb_nn_fold_row(f.nn_r2[h], f.nn_idx[h], u, w);
         }
     }
+    if (a.phi) { a.phi[s0] = ph[0]; a.phi[s0 + 1] = ph[1]; }
     if (a.nn_idx) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -955,6 +1070,14 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     murb_force_jerk_sweep<R, WAVES, STAGE, 2, MurbNNJerkArgs>(a);
 }
 
+// The potential form of both launches (ctl null: the fixed-step one).  R more packed accumulators: 4 waves per SIMD.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_force_jerk_pot_kernel(const MurbNNJerkArgs a, const MurbEvolveCtl* ctl)
+{
+    if (ctl && ctl->done) return;   // wave-uniform
+    murb_force_jerk_sweep<R, WAVES, STAGE, 3, MurbNNJerkArgs>(a);
+}
+
 // The corrector of an adaptive step: murb_hermite_correct_kernel's work with dt from the control block, then the criterion.
 // The grid covers the slots exactly or overshoots (threads past `stride` only take part in the fold).
 __global__ __launch_bounds__(256) void murb_hermite_correct_adaptive_kernel(const MurbHermiteArgs a, MurbEvolveCtl* ctl)
@@ -1066,6 +1189,7 @@ struct MurbBlockArgs {
     unsigned int stride;   // slots
     float soft2;
     int contact;           // "contact": see MurbHermiteArgs
+    float* phi;            // "potential": every body's potential at its own time; null = off
 };
 
 // what the active sweep holds of it through its inner loop
@@ -1253,11 +1377,12 @@ __device__ __forceinline__ MurbBlockCtlK murb_block_ctl_now(const MurbBlockCtl* 
 // walks units u = blockIdx.x, += gridDim.x with (group, chunk) = (u % groups, u / groups).  The entries behind the list's
 // end in its last group are whatever the buffer held: their rows are never read.
 // The body is a device function with the nearest-neighbour form behind a compile-time switch (NN, Args =
-// MurbBlockNNSweepArgs; MODE 1) and the contact form (MODE 2), like murb_force_jerk_sweep: the plain form's code does not change.
+// MurbBlockNNSweepArgs; MODE 1), the contact form (MODE 2) and the potential form (MODE 3), like murb_force_jerk_sweep: the plain
+// form's code does not change.
 template <int R, int WAVES, int STAGE, int MODE = 0, typename Args = MurbBlockSweepArgs>
 __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const MurbBlockCtl* ctl)  // NN: a is the kernel's first argument
 {
-    constexpr bool NN = MODE != 0, CT = MODE == 2;
+    constexpr bool NN = MODE != 0, CT = MODE == 2, POT = MODE == 3;   // as in murb_force_jerk_sweep
     static_assert(R % 2 == 0 && WAVES * R == MURB_BLOCK_GROUP, "a workgroup takes one group of the list");
     static_assert(MURB_TILE_F4 % (WAVES * 64) == 0, "the workgroup copies a tile in whole rounds");
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass knows no constant address space to read through
@@ -1321,7 +1446,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
         const int vt0 = (int)(((long)tiles * chunk) / chunks);
         const int vt1 = (int)(((long)tiles * (chunk + 1)) / chunks);
 
-        murb_f2 ax[R], ay[R], az[R], jx[R], jy[R], jz[R];
+        murb_f2 ax[R], ay[R], az[R], jx[R], jy[R], jz[R], ph[R];   // ph: POT, the sums of GM_j * inv
         {
             float z = 0.f;   // made in every iteration, like the fold's below
             asm volatile("" : "+v"(z));
@@ -1329,6 +1454,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
             for (int r = 0; r < R; ++r) {
                 ax[r] = (murb_f2)(z); ay[r] = (murb_f2)(z); az[r] = (murb_f2)(z);
                 jx[r] = (murb_f2)(z); jy[r] = (murb_f2)(z); jz[r] = (murb_f2)(z);
+                if constexpr (POT) ph[r] = (murb_f2)(z);
             }
         }
 
@@ -1360,6 +1486,10 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
                     asm volatile("" : "+v"(w));   // read out here, in every tile
 #pragma unroll
                     for (int r = 0; r < R; ++r) self_tile[r] = __builtin_amdgcn_readlane(w, r) / MURB_TILE_BODIES;
+                    if constexpr (POT) {   // the wave's R bodies can lie in R different tiles
+                        murb_pot_tile<R>(tq, tv, lane, murb_pot_tile_own<R>(vs + t, self_tile), xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
+                        continue;
+                    }
                     const bool masked = murb_nn_tile_masked<R>(vs + t, self_tile, __builtin_amdgcn_readlane(w, R));   // wave-uniform
                     if constexpr (CT) murb_ct_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, ri, soft2, ax, ay, az, jx, jy, jz, mn, st);
                     else murb_nn_tile<R>(tq, tv, lane, vs + t, masked, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, mn, st);
@@ -1393,8 +1523,16 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
 #pragma unroll
             for (int r = 0; r < R; ++r) { self[r] = __builtin_amdgcn_readlane(w, r); self_tile[r] = self[r] / MURB_TILE_BODIES; }
             const int count = __builtin_amdgcn_readlane(w, R);
-            unsigned int nn_r2, nn_idx;
-            if constexpr (CT) {
+            unsigned int nn_r2 = 0u, nn_idx = 0u;
+            if constexpr (POT) {
+                for (int tile = vt0; tile < vt1; ++tile)
+                    if (murb_pot_tile_own<R>(tile, self_tile)) murb_pot_own_tile<R>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, ph, self);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float sp = murb_wave_sum(ph[r].x + ph[r].y);
+                    if (fold_lane == r) nn_r2 = __builtin_bit_cast(unsigned int, sp);   // part_j.w stays 0
+                }
+            } else if constexpr (CT) {
                 const float4* vel_pred = a.vel_pred;
                 asm volatile("" : "+s"(vel_pred));
                 for (int tile = vt0; tile < vt1; ++tile)
@@ -1449,6 +1587,13 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4)))
     murb_force_jerk_block_sweep<R, WAVES, STAGE, 2, MurbBlockNNSweepArgs>(a, ctl);
 }
 
+// The potential form: the i bodies' slots come from the list, like the nearest-neighbour form's.
+template <int R, int WAVES, int STAGE>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(4))) void murb_force_jerk_pot_block_kernel(const MurbBlockNNSweepArgs a, const MurbBlockCtl* ctl)
+{
+    murb_force_jerk_block_sweep<R, WAVES, STAGE, 3, MurbBlockNNSweepArgs>(a, ctl);
+}
+
 // launch 5: one thread per list entry.  The grid covers `count` entries; threads behind the list's end only take part in the
 // wave folds.
 __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlockArgs a, MurbBlockCtl* ctl)
@@ -1469,13 +1614,16 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
         const int k = a.levels[s];
         float a0[3], j0[3], a1[3] = {0.f, 0.f, 0.f}, j1[3] = {0.f, 0.f, 0.f};
         unsigned int nn_r2 = a.contact ? MURB_CT_NONE_KEY : MURB_F32_INF_BITS, nn_idx = MURB_NN_NONE;
+        float ph = 0.f;
         for (int p = 0; p < chunks; ++p) {
             const float4 u = a.part_a[(unsigned long)p * stride + at];
             const float4 w = a.part_j[(unsigned long)p * stride + at];
             a1[0] += u.x; a1[1] += u.y; a1[2] += u.z;
             j1[0] += w.x; j1[1] += w.y; j1[2] += w.z;
+            if (a.phi) ph += u.w;
             murb_nn_fold_row(nn_r2, nn_idx, u, w);
         }
+        if (a.phi) a.phi[s] = ph;
         if (a.contact) {
             murb_ct_store(a.nn_idx, a.nn_r2, s, nn_r2, nn_idx);
             if (a.contact == 2) murb_ct_test(&ctl->enc_hits, a.enc, s, nn_r2, nn_idx);
@@ -1512,6 +1660,22 @@ __global__ __launch_bounds__(256) void murb_block_correct_kernel(const MurbBlock
         atomicMax(&ctl->k_hi, (unsigned int)ctl->kmax - hi_inv);
         if (nclamped) atomicAdd(&ctl->clamped, nclamped);
     }
+}
+
+// murbhip_potential_energy: -1/2 m_i phi_i per real body in fp64, block sums in murb_metrics_kernel's fixed order (wave shuffle
+// tree, then the 4 waves through LDS); the host adds the block rows in index order.  One block = 256 consecutive slots.
+__global__ __launch_bounds__(256) void murb_potential_sum_kernel(const float* mass, const float* phi, double* out, const int count)
+{
+#pragma clang fp contract(off)
+    __shared__ double red[3];
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    double v = s < count ? -0.5 * (double)mass[s] * (double)phi[s] : 0.0;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0 && wave > 0) red[wave - 1] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = ((v + red[0]) + red[1]) + red[2];
 }
 
 // The radii in the velocity records ("contact"): lanes z, w of a pair's B record = {R0, R1}; radius null: 0 in both (option

@@ -794,6 +794,7 @@ int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
         RC_TRY(shard_alloc(sh, sh.nn_r2, c->in.slots * sizeof(float), sh.compute));
         RC_TRY(shard_alloc(sh, sh.enc, sizeof(MurbEncList), sh.compute));
     }
+    if (c->potential) RC_TRY(shard_alloc(sh, sh.herm_phi, c->in.slots * sizeof(float), sh.compute));
     return 0;
 }
 
@@ -820,6 +821,7 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
     a.update_state = update_state;
     if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
     a.contact = c->contact;
+    if (c->potential) a.phi = sh.herm_phi;
     return a;
 }
 
@@ -843,7 +845,10 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
         int rc = 0;
         const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
         RC_TRY(rc);
-        if (c->contact)
+        if (c->potential)
+            hipLaunchKernelGGL((murb_force_jerk_pot_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                               (const MurbEvolveCtl*)nullptr);
+        else if (c->contact)
             hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
                                (const MurbEvolveCtl*)nullptr);
         else if (c->nearest)
@@ -857,7 +862,10 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
         note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
         return 0;
     }
-    if (c->contact)
+    if (c->potential)
+        hipLaunchKernelGGL((murb_force_jerk_pot_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
+                           (const MurbEvolveCtl*)ctl);
+    else if (c->contact)
         hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
                            (const MurbEvolveCtl*)ctl);
     else if (c->nearest)
@@ -989,6 +997,7 @@ MurbBlockArgs block_args(const murbhip_ctx* c, const Shard& sh)
     a.list = sh.blk_list;
     if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
     a.contact = c->contact;
+    if (c->potential) a.phi = sh.herm_phi;
     a.count = (int)sh.count;
     a.stride = (unsigned int)c->in.slots;
     a.soft2 = c->soft2;
@@ -1002,12 +1011,15 @@ int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
     hipLaunchKernelGGL(murb_block_min_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_predict_kernel, dim3(per_pair), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_plan_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
-    if (c->nearest || c->contact) {   // 4 waves per SIMD: 4 resident workgroups per CU
+    if (c->nearest || c->contact || c->potential) {   // 4 waves per SIMD: 4 resident workgroups per CU
         MurbBlockNNSweepArgs na{};
         na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
         na.grid = block_grid(c) / 5 * 4;
         na.ctl = sh.blk_ctl;
-        if (c->contact)
+        if (c->potential)
+            hipLaunchKernelGGL((murb_force_jerk_pot_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
+        else if (c->contact)
             hipLaunchKernelGGL((murb_contact_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
                                dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
         else
@@ -1390,6 +1402,8 @@ int murbhip_destroy(murbhip_ctx* c)
         if (sh.herm_ctl_host) (void)hipHostFree(sh.herm_ctl_host);
         release(sh.blk_ctl, sh.blk_ticks, sh.blk_levels, sh.blk_list, sh.blk_rec, sh.blk_vel, sh.blk_part);
         release(sh.nn_idx, sh.nn_r2, sh.enc);
+        release(sh.herm_phi, sh.pot_sums);
+        if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
         free_sym_set(sh, sh.sym_main); free_sym_set(sh, sh.sym_tri);
@@ -1698,6 +1712,39 @@ int murbhip_download_contact(murbhip_ctx* c, int* idx, float* gap2)
     HIP_TRY(hipSetDevice(sh.device));
     if (idx) HIP_TRY(hipMemcpy(idx, sh.nn_idx, c->in.n * sizeof(int), hipMemcpyDeviceToHost));
     if (gap2) HIP_TRY(hipMemcpy(gap2, sh.nn_r2, c->in.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int murbhip_download_potential(murbhip_ctx* c, float* phi)
+{
+    if (!c || !phi) return MURBHIP_E_INVALID;
+    if (!c->uploaded || !c->potential || !c->herm_current) return MURBHIP_E_STATE;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    HIP_TRY(hipMemcpy(phi, sh.herm_phi, c->in.n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// w = -1/2 sum_i m_i phi_i of the remembered evaluation: fp64 block sums in fixed order on the device (murb_potential_sum_kernel),
+// the block rows added in index order here; the masses as uploaded, like murbhip_energy's metrics.
+int murbhip_potential_energy(murbhip_ctx* c, double* w)
+{
+    if (!c || !w) return MURBHIP_E_INVALID;
+    if (!c->uploaded || !c->potential || !c->herm_current) return MURBHIP_E_STATE;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const size_t blocks = (sh.count + 255) / 256, cap = (c->in.slots + 255) / 256;
+    RC_TRY(shard_alloc(sh, sh.pot_sums, cap * sizeof(double)));
+    if (!sh.pot_sums_host) HIP_TRY(hipHostMalloc((void**)&sh.pot_sums_host, cap * sizeof(double), hipHostMallocDefault));
+    hipLaunchKernelGGL(murb_potential_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float*)sh.mass,
+                       (const float*)sh.herm_phi, sh.pot_sums, (int)sh.count);
+    RC_TRY(hip_rc(hipGetLastError()));
+    HIP_TRY(hipMemcpyAsync(sh.pot_sums_host, sh.pot_sums, blocks * sizeof(double), hipMemcpyDeviceToHost, sh.compute));
+    RC_TRY(murbhip_sync(c));
+    double sum = 0.0;
+    for (size_t b = 0; b < blocks; ++b) sum += sh.pot_sums_host[b];
+    *w = sum;
     return 0;
 }
 
@@ -2180,7 +2227,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
         if (value == 2 && (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
-        if (value != 2 && (c->nearest || c->contact)) return MURBHIP_E_STATE;   // they belong to the Hermite sweeps: switch them off first
+        if (value != 2 && (c->nearest || c->contact || c->potential)) return MURBHIP_E_STATE;   // they belong to the Hermite sweeps: switch them off first
         c->integrator = (int)value;
     }
     else if (k == "evolve_batch") {
@@ -2190,7 +2237,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "nearest") {
         if (value != 0 && value != 1) return MURBHIP_E_INVALID;
         if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
-        if (value && c->contact) return MURBHIP_E_STATE;   // both use the rows' fourth floats and the per-slot arrays
+        if (value && (c->contact || c->potential)) return MURBHIP_E_STATE;   // they use the rows' fourth floats (and two of them the per-slot arrays)
         if (!value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
         if ((int)value != c->nearest) {
             c->nearest = (int)value;
@@ -2200,7 +2247,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     else if (k == "contact") {
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
-        if (value && c->nearest) return MURBHIP_E_STATE;   // both use the rows' fourth floats and the per-slot arrays
+        if (value && (c->nearest || c->potential)) return MURBHIP_E_STATE;   // they use the rows' fourth floats (and two of them the per-slot arrays)
         const bool was = c->contact != 0, now = value != 0;
         if (was != now) {
             if (c->blk_open) return MURBHIP_E_STATE;   // the open block's velocity records carry the radii or do not
@@ -2210,6 +2257,16 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
             RC_TRY(enqueue_radii_lanes(c));
         }
         c->contact = (int)value;   // 1 <-> 2: only the stop; the evaluation and an open block stay
+    }
+    else if (k == "potential") {
+        if (value != 0 && value != 1) return MURBHIP_E_INVALID;
+        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+        if (value && (c->nearest || c->contact)) return MURBHIP_E_STATE;   // all three use the rows' fourth floats
+        if ((int)value != c->potential) {
+            if (c->blk_open) return MURBHIP_E_STATE;   // the inactive bodies of the open block have their phi or do not
+            c->potential = (int)value;
+            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its potentials beside it
+        }
     }
     else if (k == "block_units") {
         if (value < 0 || value > kBlockMaxUnits) return MURBHIP_E_INVALID;
@@ -2274,6 +2331,7 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "nearest") *value = c->nearest;
     else if (k == "encounter_count") *value = c->contact ? 0.0 : (double)c->enc_count;
     else if (k == "contact") *value = c->contact;
+    else if (k == "potential") *value = c->potential;
     else if (k == "contact_count") *value = c->contact ? (double)c->enc_count : 0.0;
     else if (k == "block_steps") *value = c->blk_info[0];
     else if (k == "block_body_steps") *value = c->blk_info[1];

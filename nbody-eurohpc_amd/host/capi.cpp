@@ -2,6 +2,7 @@
 //   * the product's own initial conditions (so bench.py never needs the oracle for its inputs),
 //   * the mirrored plugin classes driven exactly like the reference's tests drive the originals
 //     (src/test/implem/test_SimulationNBody.cpp:28-71, test_CUDABodies.cpp:23-75).
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -170,6 +171,23 @@ int murbhost_sim_encounters(void *p, int *i, int *j, float *r2, unsigned long ca
         if (j) j[k] = e[k].j;
         if (r2) r2[k] = e[k].r2;
     }
+    return 0;
+}
+// hip+hermite / hip+hermite+adaptive / hip+hermite+block: SimulationNBodyHIPTracking::setPotential.  0, or -1 where it does not
+// apply (another simulation, an encounter radius or the contact stop set).
+int murbhost_sim_set_potential(void *p, int on)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    return t && t->setPotential(on != 0) ? 0 : -1;
+}
+// ... every body's potential of the last sweep, n entries.  0, -1 for a simulation without the option, -2 before the first sweep.
+int murbhost_sim_potential(void *p, float *phi)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t || !t->hasPotential() || !phi) return -1;
+    const std::vector<float> v = t->getPotential();
+    if (v.empty()) return -2;
+    std::copy(v.begin(), v.end(), phi);
     return 0;
 }
 // hip+hermite+adaptive / hip+hermite+block: SimulationNBodyHIPTracking::setContactStop.  0, or -1 where it does not apply

@@ -11,7 +11,7 @@ SimulationNBodyHIPTracking<T, Q>::SimulationNBodyHIPTracking(const BodiesAllocat
                                                              const int integrator, const std::vector<int> &devices,
                                                              int exchange)
     : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}, adaptive{integrator == 3 || integrator == 4},
-      blockSteps{integrator == 4}
+      blockSteps{integrator == 4}, hermite{integrator >= 2 && integrator <= 4}
 {
     if (!this->history) this->history = std::make_shared<SimulationHistory<Q>>();
     if (integrator)
@@ -34,7 +34,7 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
 
 template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setEncounterRadius(const T radius)
 {
-    if (!adaptive || (radius > 0 && contactStop)) return false;
+    if (!adaptive || (radius > 0 && (contactStop || potentialOn))) return false;
     murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
     if (radius > 0) murbhipCheck(murbhip_set_option(ctx, "nearest", 1), "murbhip_set_option(nearest)");
     murbhipCheck(murbhip_set_encounter(ctx, (float)radius), "murbhip_set_encounter");
@@ -44,7 +44,7 @@ template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setEnco
 
 template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setContactStop(const bool on, const T scale)
 {
-    if (!adaptive || encounterRadius > 0 || !(scale > 0) || !std::isfinite((double)scale)) return false;
+    if (!adaptive || encounterRadius > 0 || (on && potentialOn) || !(scale > 0) || !std::isfinite((double)scale)) return false;
     murbhip_ctx *ctx = this->hipBodiesPtr->getContext();
     if (on) {
         const auto &r = this->hipBodiesPtr->getDataSoA().r;
@@ -57,6 +57,23 @@ template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setCont
     contactStop = on;
     contactScale = scale;
     return true;
+}
+
+template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setPotential(const bool on)
+{
+    if (!hermite || (on && (encounterRadius > 0 || contactStop))) return false;
+    murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "potential", on ? 1 : 0), "murbhip_set_option(potential)");
+    potentialOn = on;
+    return true;
+}
+
+template <typename T, typename Q> std::vector<float> SimulationNBodyHIPTracking<T, Q>::getPotential() const
+{
+    std::vector<float> phi;
+    if (!potentialOn) return phi;
+    phi.resize(this->hipBodiesPtr->getN());
+    if (murbhip_download_potential(this->hipBodiesPtr->getContext(), phi.data()) != 0) phi.clear();   // no sweep yet
+    return phi;
 }
 
 template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::readContacts()

@@ -31,6 +31,8 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     int currentIteration = 0;
     bool adaptive = false;            // integrator 3: "integrator" 2 driven by murbhip_evolve; 4: by murbhip_evolve_block
     bool blockSteps = false;          // integrator 4
+    bool hermite = false;             // integrators 2, 3 and 4: the acceleration + jerk sweeps
+    bool potentialOn = false;         // ... keep every body's potential beside them (option "potential")
     int kmax = 12;                    // its deepest level (--kmax): steps down to dt 2^-kmax
     unsigned long bodySteps = 0, clampedSteps = 0;   // integrator 4: bodies advanced, and steps the cap was too coarse for
     double eta = 0.02;                // its accuracy parameter (--eta); the first step of all uses eta_start = 0.01
@@ -89,6 +91,14 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     unsigned long getContactCount() const { return contactCount; }
     double getContactTime() const { return contactTime; }
     const std::vector<Encounter> &getContacts() const { return contacts; }
+    // hip+hermite / hip+hermite+adaptive / hip+hermite+block (option "potential"): the sweeps keep every body's potential phi_i
+    // (include/murbhip.h has the definition).  Excludes an encounter radius and the contact stop.  false for the other
+    // integrators and beside either of the two.
+    bool setPotential(const bool on);
+    bool hasPotential() const { return potentialOn; }
+    // phi_i of the last sweep in the bodies' order (murbhip_download_potential; after an iteration: of its last substep's
+    // predicted end state); empty where the option is off or no sweep has run yet
+    std::vector<float> getPotential() const;
 };
 
 #endif

@@ -79,6 +79,8 @@ def lib():
         L.murbhip_download_contact.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp]
         L.murbhip_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong, C.POINTER(C.c_ulong),
                                        C.POINTER(C.c_double)]
+        L.murbhip_download_potential.argtypes = [C.c_void_p, _fp]
+        L.murbhip_potential_energy.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -100,6 +102,7 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_evolve_block murbhip_block_state murbhip_block_set_levels "
            "murbhip_download_nearest murbhip_set_encounter murbhip_encounters "
            "murbhip_upload_radii murbhip_download_contact murbhip_contacts "
+           "murbhip_download_potential murbhip_potential_energy "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
 
@@ -323,6 +326,20 @@ class Simulation:
         _check(lib().murbhip_download_contact(self._h, idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(gap2)), "murbhip_download_contact")
         return idx, gap2
 
+    def potential(self):
+        """float32 phi_i = sum_{j != i} G m_j / sqrt(r_ij^2 + soft^2) of every body in the remembered evaluation (option
+        "potential" 1; include/murbhip.h: murbhip_download_potential).  Positive; after a step: at its predicted end state."""
+        phi = np.zeros(self.n, np.float32)
+        _check(lib().murbhip_download_potential(self._h, _ptr(phi)), "murbhip_download_potential")
+        return phi
+
+    def potential_energy(self):
+        """-1/2 sum_i m_i phi_i of the remembered evaluation, summed in fp64 on the device (option "potential" 1); also while a
+        block is open, where energy() refuses."""
+        w = C.c_double()
+        _check(lib().murbhip_potential_energy(self._h, C.byref(w)), "murbhip_potential_energy")
+        return w.value
+
     def contacts(self):
         """dict of the step that ended the last evolve call by a contact ("contact" 2): i, j (int32), gap2 (float32) sorted by
         i, the count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
@@ -482,6 +499,8 @@ def host_lib():
         H.murbhost_sim_encounters.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                               C.POINTER(C.c_ulong), _dp]
         H.murbhost_sim_set_contact.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        H.murbhost_sim_set_potential.argtypes = [C.c_void_p, C.c_int]
+        H.murbhost_sim_potential.argtypes = [C.c_void_p, _fp]
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                             C.POINTER(C.c_ulong), _dp]
         _host = H
@@ -522,7 +541,7 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0):
+                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0, potential=False):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
         driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
@@ -530,7 +549,8 @@ class HostSim:
         its own size dt 2^-k, k <= kmax, with accuracy parameter eta).  encounter=R (integrator 3 or 4): an iteration ends
         behind the substep in which a body has its nearest neighbour within R; encounters() then has the pairs.  contact=True
         (integrator 3 or 4, not beside encounter=): it ends behind the substep in which two bodies touch, their radii being
-        the scheme's times rscale; contacts() then has the pairs."""
+        the scheme's times rscale; contacts() then has the pairs.  potential=True (integrator 2, 3 or 4, not beside encounter= or
+        contact=): the sweeps keep every body's potential; potential() then has it."""
         if integrator is None:
             integrator = int(bool(leapfrog))
         if contact and integrator not in (3, 4):
@@ -539,6 +559,10 @@ class HostSim:
             raise ValueError("contact= cannot be combined with encounter=")
         if contact and not (np.isfinite(rscale) and rscale > 0):
             raise ValueError("rscale= must be finite and positive")
+        if potential and integrator not in (2, 3, 4):
+            raise ValueError("potential= needs integrator 2, 3 or 4")
+        if potential and (contact or encounter):
+            raise ValueError("potential= cannot be combined with encounter= or contact=")
         arr = (C.c_int * len(devices))(*devices)
         self.H = host_lib()
         ex = {"copy": 0, "rccl": 1}[exchange]
@@ -555,6 +579,17 @@ class HostSim:
         if contact:
             if self.H.murbhost_sim_set_contact(self.h, 1, rscale) != 0:
                 raise ValueError("contact= needs integrator 3 or 4")
+        if potential:
+            if self.H.murbhost_sim_set_potential(self.h, 1) != 0:
+                raise ValueError("potential= needs integrator 2, 3 or 4")
+
+    def potential(self):
+        """potential=True: float32 phi_i of every body in the last sweep (Simulation.potential; after an iteration: of its last
+        substep's predicted end state); None where the feature does not apply or before the first sweep."""
+        phi = np.zeros(self.n, np.float32)
+        if self.H.murbhost_sim_potential(self.h, _ptr(phi)) != 0:
+            return None
+        return phi
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;

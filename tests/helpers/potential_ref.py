@@ -1,0 +1,120 @@
+"""Per-body potential of the Hermite sweeps (option "potential"), restated from include/murbhip.h in fp64, and the probes that
+tests/test_potential_host.py (CPU) and tests/test_potential_gpu.py (GPU) share.  numpy only; nothing here touches a device.
+
+    phi_i = sum over real bodies j != i of G m_j / sqrt(|q_j - q_i|^2 + soft^2)
+
+The body's own SLOT is left out, nothing else: another body at the same position counts with G m_j / soft, a massless body
+has a phi of its own and adds to nobody's.  The bound everywhere is the project's force bound TOL_F64_MAX, relative to the fp64
+phi_i: all terms are positive, so the sum of the term magnitudes is phi_i itself."""
+import numpy as np
+
+import hermite_ref as H
+
+TOL_F64_MAX = 2e-6       # tests/helpers/hermite_probe.py, forces
+POWER_FACTOR = 10.0      # a probe must show one term at 10 x the bound on 99 % of the bodies
+TILE = 512               # slots per layout tile (MURB_TILE_BODIES)
+Q, V = ("qx", "qy", "qz"), ("vx", "vy", "vz")
+
+
+def phi_f64(q, gm, soft, rows=None, want_min=False):
+    """fp64 phi of the bodies `rows` (all by default) at positions q (3, n) with G m = gm (n); with want_min also every
+    body's smallest term among the bodies of non-zero mass (+inf where there is none).  Blocked over i."""
+    q, gm = np.asarray(q, np.float64), np.asarray(gm, np.float64)
+    n = q.shape[1]
+    rows = np.arange(n) if rows is None else np.asarray(rows, np.int64)
+    soft2 = float(soft) * float(soft)
+    phi, mn = np.zeros(len(rows)), np.full(len(rows), np.inf)
+    for lo in range(0, len(rows), 256):
+        r = rows[lo:lo + 256]
+        d = q[:, None, :] - q[:, r, None]
+        with np.errstate(divide="ignore", invalid="ignore"):      # soft == 0: the own slot's term, dropped below
+            t = gm[None, :] / np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + soft2)
+        t[np.arange(len(r)), r] = 0.0      # the own slot, by index
+        phi[lo:lo + 256] = t.sum(1)
+        if want_min:
+            t[:, gm == 0.0] = np.inf
+            t[np.arange(len(r)), r] = np.inf
+            mn[lo:lo + 256] = t.min(1)
+    return (phi, mn) if want_min else phi
+
+
+def phi_of(s, soft, **kw):
+    return phi_f64(H._stack(s, Q), H._gm(s), soft, **kw)
+
+
+def energy_of(s, phi):
+    """w = -1/2 sum_i m_i phi_i in fp64."""
+    return -0.5 * float((np.asarray(s["m"], np.float64) * np.asarray(phi, np.float64)).sum())
+
+
+def rel_err(got, want):
+    """|got - want| / want per body; 0 where both are exactly 0 (a lone body)."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(want == 0.0, np.where(got == 0.0, 0.0, np.inf), np.abs(got - want) / want)
+
+
+def state(q, m, v=None):
+    q = np.asarray(q, np.float32)
+    v = np.zeros_like(q) if v is None else np.asarray(v, np.float32)
+    s = {k: np.ascontiguousarray(q[i]) for i, k in enumerate(Q)}
+    s.update({k: np.ascontiguousarray(v[i]) for i, k in enumerate(V)})
+    s["m"] = np.asarray(m, np.float32)
+    return s
+
+
+# ---- the own term ------------------------------------------------------------------------------------------------------------
+OWN_MASS, OWN_SEP, OWN_SOFT = 1e30, 1e10, np.float32(1e6)   # the own term G m / soft is 1e4 x the pair term G m / sep
+OWN_SLOTS = (5, 513)
+
+
+def own_term_pair(n):
+    """(state, soft, the two massive bodies): n = 2, or n = 514 with the two at slots 5 and 513 (two layout tiles) and every
+    other body massless and at least 1e13 m away from them and from each other."""
+    if n == 2:
+        return state([[0.0, OWN_SEP], [0.0, 0.0], [0.0, 0.0]], [OWN_MASS, OWN_MASS]), OWN_SOFT, (0, 1)
+    k = np.arange(n, dtype=np.float64)
+    q = np.stack([1e13 + 1e13 * k, -2e13 - 1e13 * (k % 7), 3e13 + 5e12 * (k % 11)])
+    m = np.zeros(n)
+    a, b = OWN_SLOTS
+    q[:, a], q[:, b] = (0.0, 0.0, 0.0), (OWN_SEP, 0.0, 0.0)
+    m[a] = m[b] = OWN_MASS
+    return state(q, m), OWN_SOFT, OWN_SLOTS
+
+
+# ---- coincident bodies -------------------------------------------------------------------------------------------------------
+COINCIDENT_SOFT = np.float32(0.5)
+COINCIDENT_PAIRS = ((4, 5), (4, 10), (4, 600))      # the same pair of slots, different lanes of a tile, different tiles
+
+
+def coincident(pair, n=1024, seed=3):
+    """n massive bodies on integer coordinates in [300, 1024]^3 (every difference exact in fp32), body pair[1] moved onto body
+    pair[0]: each of the two has the other's G m / soft in its phi."""
+    rng = np.random.default_rng(seed)
+    q = rng.integers(300, 1025, size=(3, n)).astype(np.float64)
+    q[:, pair[1]] = q[:, pair[0]]
+    m = rng.uniform(1e8, 2e8, n)
+    return state(q, m, rng.standard_normal((3, n))), COINCIDENT_SOFT
+
+
+# ---- sparse sources ----------------------------------------------------------------------------------------------------------
+SPARSE_N, SPARSE_SOFT = 2049, np.float32(0.01)
+SPARSE_SOURCES = (0, 5, 100, 511, 512, 700, 777, 1023, 1024, 1300, 1535, 1536, 1801, 2000, 2047, 2048)   # every tile's ends
+
+
+def sparse(n=SPARSE_N, seed=11, velocities=False):
+    """(state, soft, sources): n bodies in a unit cube, mass (1 ... 2) x 1e10 kg on the 16 sources alone — G m / r of order 1."""
+    rng = np.random.default_rng(seed)
+    q = rng.uniform(0.0, 1.0, (3, n))
+    m = np.zeros(n)
+    src = np.array([x for x in SPARSE_SOURCES if x < n], np.int64)
+    m[src] = 1e10 * rng.uniform(1.0, 2.0, len(src))
+    v = 1e-3 * rng.standard_normal((3, n)) if velocities else None
+    return state(q, m, v), SPARSE_SOFT, src
+
+
+def power(s, soft):
+    """Per body: the share of its smallest source term in its phi (inf where it has no source term)."""
+    phi, mn = phi_of(s, soft, want_min=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(np.isfinite(mn), mn / phi, np.inf)
