@@ -410,8 +410,11 @@ __device__ __forceinline__ void murb_ct_test(unsigned int* hits, MurbEncList* li
 // phi_i = sum_{j != i} GM_j inv_ij: the sum of the gi the force arithmetic forms anyway, one more packed fma per pair of
 // interactions and R more packed accumulators.  The body's own term GM_i / soft is orders of magnitude above the pair terms
 // where the softening is small, so it never enters an fp32 sum: the accumulation is phi = fma(gi, pm, phi) with a wave-uniform
-// pm that is 0 in the layout tile(s) holding one of the wave's own i bodies and 1 elsewhere (murb_nn_tile's sign, in kind), and
-// such a tile's terms are added behind the loop from the records in memory with the own slot left out (murb_pot_own_tile).
+// pm that is 0 in the layout tile holding the i body and 1 elsewhere (murb_nn_tile's sign, in kind), and that tile's terms are
+// added behind the loop from the records in memory with the own slot left out (murb_pot_own_tile).  The fixed sweep's wave has
+// its R bodies in one tile and one pm (RT = 1).  The active sweep's R bodies come from the list and can lie in R tiles: there
+// pm is per body (RT = R) and murb_pot_own_tile adds a tile to its own bodies alone, so that every body's sum receives "all
+// other tiles in layout order, then its own" whoever shares its wave, and phi does not depend on the list's order.
 // Padding has GM = 0: its gi is +0 and needs no mask.  The loop nest keeps ONE copy of the arithmetic.
 template <int RT>
 __device__ __forceinline__ bool murb_pot_tile_own(const int tile, const int (&self_tile)[RT])   // wave-uniform
@@ -422,14 +425,17 @@ __device__ __forceinline__ bool murb_pot_tile_own(const int tile, const int (&se
     return m;
 }
 
-template <int R>
-__device__ __forceinline__ void murb_pot_tile(const float4* tq, const float4* tv, const int lane, const bool own,
+template <int R, int RT>
+__device__ __forceinline__ void murb_pot_tile(const float4* tq, const float4* tv, const int lane, const int tile, const int (&self_tile)[RT],
                                               const float (&xi)[R], const float (&yi)[R], const float (&zi)[R],
                                               const float (&ui)[R], const float (&vi)[R], const float (&wi)[R], const float soft2,
                                               murb_f2 (&ax)[R], murb_f2 (&ay)[R], murb_f2 (&az)[R],
                                               murb_f2 (&jx)[R], murb_f2 (&jy)[R], murb_f2 (&jz)[R], murb_f2 (&ph)[R])
 {
-    const float pm = own ? 0.f : 1.f;   // wave-uniform
+    static_assert(RT == 1 || RT == R, "one tile for the wave, or one per body");
+    float pm[RT];   // wave-uniform, per body: 0 in the body's OWN tile alone, whatever tiles the wave's other bodies lie in
+#pragma unroll
+    for (int r = 0; r < RT; ++r) pm[r] = self_tile[r] == tile ? 0.f : 1.f;
 #pragma unroll
     for (int q = 0; q < MURB_TILE_PAIRS; q += 64) {
         const float4 A = tq[q + lane], B = tq[q + lane + MURB_TILE_PAIRS];
@@ -441,7 +447,7 @@ __device__ __forceinline__ void murb_pot_tile(const float4* tq, const float4* tv
             murb_f2 r2, gi;
             murb_interact_jerk_pk_gi(xj, yj, zj, gj, uj, vj, wj, xi[r], yi[r], zi[r], ui[r], vi[r], wi[r], soft2,
                                      ax[r], ay[r], az[r], jx[r], jy[r], jz[r], r2, gi);
-            ph[r] = __builtin_elementwise_fma(gi, (murb_f2)(pm), ph[r]);
+            ph[r] = __builtin_elementwise_fma(gi, (murb_f2)(pm[RT == 1 ? 0 : r]), ph[r]);
         }
     }
 }
@@ -462,7 +468,7 @@ __device__ __forceinline__ float murb_pot_gi_single(const float xj, const float 
 
 // The terms of one tile that holds own bodies, from the records in memory, every body's own SLOT left out (another body at the
 // same place counts).  Runs after the loop; the order is fixed: lane steps rising, the two slots of a pair in their halves.
-template <int R>
+template <int R, bool EACH = false>
 __device__ __forceinline__ void murb_pot_own_tile(const float4* rec, const int lane, const int tile,
                                                   const float (&xi)[R], const float (&yi)[R], const float (&zi)[R], const float soft2,
                                                   murb_f2 (&ph)[R], const int (&self)[R])
@@ -476,6 +482,12 @@ __device__ __forceinline__ void murb_pot_own_tile(const float4* rec, const int l
         for (int r = 0; r < R; ++r) {
             const float gx = murb_pot_gi_single(A.x, A.z, B.x, B.z, xi[r], yi[r], zi[r], soft2);
             const float gy = murb_pot_gi_single(A.y, A.w, B.y, B.w, xi[r], yi[r], zi[r], soft2);
+            if constexpr (EACH) {   // the wave's bodies lie in several tiles: a body takes the terms of its own tile alone
+                const bool other = self[r] / MURB_TILE_BODIES != tile;   // wave-uniform; + 0 changes no bit of a sum of positive terms
+                ph[r].x += other || j0 == self[r] ? 0.f : gx;
+                ph[r].y += other || j0 + 1 == self[r] ? 0.f : gy;
+                continue;
+            }
             ph[r].x += j0 == self[r] ? 0.f : gx;
             ph[r].y += j0 + 1 == self[r] ? 0.f : gy;
         }
@@ -572,7 +584,7 @@ __device__ __forceinline__ void murb_force_jerk_sweep(const Args a)
             const float4* tq = lds + (2 * t) * MURB_TILE_F4;
             const float4* tv = tq + MURB_TILE_F4;
             if constexpr (POT) {
-                murb_pot_tile<R>(tq, tv, lane, murb_pot_tile_own<1>(vs + t, self_tile), xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
+                murb_pot_tile<R, 1>(tq, tv, lane, vs + t, self_tile, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
                 continue;
             }
             if constexpr (NN) {
@@ -1487,7 +1499,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
 #pragma unroll
                     for (int r = 0; r < R; ++r) self_tile[r] = __builtin_amdgcn_readlane(w, r) / MURB_TILE_BODIES;
                     if constexpr (POT) {   // the wave's R bodies can lie in R different tiles
-                        murb_pot_tile<R>(tq, tv, lane, murb_pot_tile_own<R>(vs + t, self_tile), xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
+                        murb_pot_tile<R, R>(tq, tv, lane, vs + t, self_tile, xi, yi, zi, ui, vi, wi, soft2, ax, ay, az, jx, jy, jz, ph);
                         continue;
                     }
                     const bool masked = murb_nn_tile_masked<R>(vs + t, self_tile, __builtin_amdgcn_readlane(w, R));   // wave-uniform
@@ -1526,7 +1538,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
             unsigned int nn_r2 = 0u, nn_idx = 0u;
             if constexpr (POT) {
                 for (int tile = vt0; tile < vt1; ++tile)
-                    if (murb_pot_tile_own<R>(tile, self_tile)) murb_pot_own_tile<R>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, ph, self);
+                    if (murb_pot_tile_own<R>(tile, self_tile)) murb_pot_own_tile<R, true>(rec_pred, fold_lane, tile, xi, yi, zi, soft2, ph, self);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const float sp = murb_wave_sum(ph[r].x + ph[r].y);
@@ -1563,7 +1575,7 @@ __device__ __forceinline__ void murb_force_jerk_block_sweep(const Args a, const 
         if constexpr (CT) stride_u = murb_kernarg_again<Args>()->grid;
     }
 #else
-    (void)a; (void)ctl; (void)NN; (void)CT;
+    (void)a; (void)ctl; (void)NN; (void)CT; (void)POT;
 #endif
 }
 

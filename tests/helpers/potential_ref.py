@@ -118,3 +118,50 @@ def power(s, soft):
     phi, mn = phi_of(s, soft, want_min=True)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(np.isfinite(mn), mn / phi, np.inf)
+
+
+# ---- the dense system and the order of the tiles -------------------------------------------------------------------------------
+DENSE_N, DENSE_SOFT = 2049, np.float32(0.01)
+
+
+def dense(n=DENSE_N, seed=23):
+    """(state, soft): n bodies in a unit cube, every one with a mass of (1 ... 2) x 1e10 kg and a velocity of order 1e-3:
+    every tile adds to every body's phi, so the order in which an fp32 sum receives the tiles shows in its last bits."""
+    rng = np.random.default_rng(seed)
+    q = rng.uniform(0.0, 1.0, (3, n))
+    m = 1e10 * rng.uniform(1.0, 2.0, n)
+    return state(q, m, 1e-3 * rng.standard_normal((3, n))), DENSE_SOFT
+
+
+def dense_probes(count=64, tile=0):
+    """`count` bodies of one tile, spread over its lanes and lane steps."""
+    return tile * TILE + np.unique(np.linspace(0, TILE - 1, count).astype(np.int64))
+
+
+def lane_sums_f32(s, soft, body, order):
+    """numpy float32 emulation of one body's phi in one wave of the potential sweep: 64 lanes with two accumulators each (the
+    halves of a packed register); lane l takes the slot pairs l, l + 64, l + 128, l + 192 of a tile, one rounded addition per
+    term; the tiles come in `order`; the body's own slot adds nothing.  Returns (the 128 lane accumulators, the folded total:
+    the two halves added, then a butterfly over the lanes).  1 / sqrt in float32 stands for the device's reciprocal square
+    root: the question is the order of the additions alone."""
+    f = np.float32
+    q = np.stack([np.asarray(s[k], f) for k in Q])
+    n = q.shape[1]
+    gm = np.asarray(H._gm(s), f)
+    soft2 = f(soft) * f(soft)
+    acc = np.zeros((64, 2), f)
+    lanes = np.arange(64)
+    for tile in order:
+        for qs in range(TILE // 2 // 64):
+            for half in (0, 1):
+                j = tile * TILE + 2 * (qs * 64 + lanes) + half
+                ok = (j < n) & (j != body)
+                jj = np.minimum(j, n - 1)
+                d = q[:, jj] - q[:, body, None]
+                r2 = ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + soft2
+                gi = np.where(ok, gm[jj] * (f(1.0) / np.sqrt(r2)), f(0.0)).astype(f)
+                acc[:, half] = acc[:, half] + gi
+    fold = acc[:, 0] + acc[:, 1]
+    for sft in (32, 16, 8, 4, 2, 1):
+        fold = fold + fold[lanes ^ sft]
+    return acc, fold[0]

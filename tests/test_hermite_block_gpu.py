@@ -143,25 +143,49 @@ def replay_system(name):
     bodies over levels 0 ... 6 and the first 44 block steps have active sets of 1 ... 2 049 bodies (restatement, CPU).
     cluster: the specification's 256 bodies, blocks of half a binary period in 4 096 ticks — the binary starts at level 12 and
     the field bodies at levels 0 ... 2, so that the binary alone is active for the first 99 block steps; the field's levels
-    come up (44, 20, 110, 68 bodies) from there to the block's end at the 128th, where all 256 are (restatement, CPU)."""
+    come up (44, 20, 110, 68 bodies) from there to the block's end at the 128th, where all 256 are (restatement, CPU).
+    wrap: 5 120 bodies of the same generator, blocks of 8 ticks of 3 600 s, levels set by hand (replay_levels) and one chunk per
+    layout tile (replay_options): the system tests/test_block_wrap_gpu.py replays, whose steps walk more units than the grid."""
     import murbhip
     if name == "random":
         return murbhip.init_bodies(2049, "random"), float(SOFT), 2.0 ** 17, 6
+    if name == "wrap":      # tests/test_block_wrap_gpu.py: 10 layout tiles, blocks of 8 ticks of 3 600 s, levels by hand
+        return murbhip.init_bodies(5120, "random"), float(SOFT), 8.0 * float(DT), 3
     s, period = cluster(256)
     return s, B.SOFT, float(np.float32(period / 2.0)), 12
 
 
+def replay_levels(name):
+    """The levels a replay starts from where they are set by hand (set_block_levels), None where the starting rule gives them.
+    wrap: i mod 4 with kmax 3, so that the first active sets hold about 1 280, 2 560, 1 280, 3 840 ... 5 120 bodies."""
+    return (np.arange(5120) % 4).astype(np.int32) if name == "wrap" else None
+
+
+def replay_options(name):
+    return {"block_units": 65536} if name == "wrap" else {}      # wrap: one chunk per layout tile in every step
+
+
 @pytest.mark.parametrize("name,steps", [("random", 44), ("cluster", 136)])
 def test_single_step_replay(gpu, O, name, steps):
+    sizes, _ = replay(gpu, O, name, steps)
+    assert steps >= 40 and len(sizes) == steps and min(sizes) < 16 < max(sizes)
+
+
+def replay(gpu, O, name, steps):
+    """`steps` block steps of replay_system(name), one per call, or fewer where a synchronised boundary comes first and the
+    levels were set by hand.  Returns (the restatement's active-set sizes, the device's body-steps) per step."""
     s, soft, dt_max, kmax = replay_system(name)
+    hand = replay_levels(name)
     n, gm, c_jerk = len(s["m"]), H._gm(s), jerk_bound(name)
     T = 1 << kmax
     worst_a = worst_j = 0.0
-    sizes = []
-    with hermite_sim(gpu, s, soft) as sim:
+    sizes, body_steps = [], []
+    with hermite_sim(gpu, s, soft, **replay_options(name)) as sim:
         sim.compute_acc_jerk()
         a0, j0 = np.stack(sim.acc()), np.stack(sim.jerk())
-        want_start = B.start_levels(a0, j0, ETA_START, dt_max, kmax)
+        want_start = B.start_levels(a0, j0, ETA_START, dt_max, kmax) if hand is None else hand
+        if hand is not None:
+            sim.set_block_levels(hand, kmax)
         pre = None
         for k in range(steps):
             out = sim.evolve_block(dt_max, blocks=1000, eta=ETA, eta_start=ETA_START, kmax=kmax, max_steps=1)
@@ -173,6 +197,7 @@ def test_single_step_replay(gpu, O, name, steps):
             t_next, act = B.next_time(pre.ticks, pre.levels, kmax)
             idx = np.flatnonzero(act)
             sizes.append(len(idx))
+            body_steps.append(out["body_steps"])
             # the active set is exactly the argmin set: its size, and nobody else moved in any array, bit for bit
             assert out["steps"] == 1 and out["body_steps"] == len(idx) == out["max_active"], (k, out, len(idx))
             assert out["synchronised"] == (t_next == T)
@@ -201,10 +226,12 @@ def test_single_step_replay(gpu, O, name, steps):
             worst_a = max(worst_a, float(O.rel_err(post.a[:, rows], ta).max()))
             worst_j = max(worst_j, float(H.scaled_err(post.j[:, rows], tj, abs_j).max()) * 2.0 ** 24)
             pre = post
-    print(f"{name}: {steps} block steps, active sets {sizes}; acc max rel {worst_a:.3e} (bound {TOL_F64_MAX:.1e}); "
+            if hand is not None and out["synchronised"]:
+                break
+    print(f"{name}: {len(sizes)} block steps, active sets {sizes}; acc max rel {worst_a:.3e} (bound {TOL_F64_MAX:.1e}); "
           f"jerk max scaled {worst_j:.2f} x 2^-24 (bound C = {c_jerk:.2f})")
-    assert steps >= 40 and min(sizes) < 16 < max(sizes)
     assert worst_a <= TOL_F64_MAX and worst_j <= c_jerk
+    return sizes, body_steps
 
 
 # ------------------------------------------------------------------------------------------------------- 3. active-set shapes

@@ -144,7 +144,8 @@ def test_block_entry_points_are_exported(mh):
 def test_block_kernels_use_no_scratch():
     """Code-object metadata of a fresh gfx950 build: the eight kernels of a block step are there, with 0 bytes of scratch and
     0 spilled registers; the active sweep has the fixed-step sweep's LDS and arithmetic and fits 5 waves per SIMD (at most
-    96 vector registers: 512 / 5 rounded down to the allocation unit of 8)."""
+    96 vector registers: 512 / 5 rounded down to the allocation unit of 8).  The two potential kernels, likewise free of
+    scratch and spills, fit 4 waves per SIMD (128 vector registers)."""
     hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
@@ -154,9 +155,10 @@ def test_block_kernels_use_no_scratch():
         subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
                        check=True, stderr=subprocess.DEVNULL)
         text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_block_|murb_force_jerk_block_)\S*)\n(.*?)\.wavefront_size", text, re.S))
+    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_block_|murb_force_jerk_block_|murb_force_jerk_pot_)\S*)\n(.*?)\.wavefront_size", text, re.S))
     for want in ("murb_block_begin_kernel", "murb_block_start_kernel", "murb_block_min_kernel", "murb_block_predict_kernel",
-                 "murb_block_plan_kernel", "murb_force_jerk_block_kernel", "murb_block_correct_kernel", "murb_block_book_kernel"):
+                 "murb_block_plan_kernel", "murb_force_jerk_block_kernel", "murb_block_correct_kernel", "murb_block_book_kernel",
+                 "murb_force_jerk_pot_kernel", "murb_force_jerk_pot_block_kernel"):
         assert any(want in k for k in kernels), want + " missing from the code object"
     fields = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")
     for name, meta in kernels.items():
@@ -165,6 +167,8 @@ def test_block_kernels_use_no_scratch():
         assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
         if "murb_force_jerk_block_kernel" in name:
             assert num["vgpr_count"] <= 96, "the active sweep no longer fits 5 waves per SIMD"
+        if "murb_force_jerk_pot_" in name:      # the potential forms, fixed and active (per-body multipliers): 4 waves per SIMD
+            assert num["vgpr_count"] <= 128, name + " no longer fits 4 waves per SIMD"
 
     def packed(kernel):   # the packed fp32 instructions, reciprocal square roots and LDS reads of a kernel's body
         body = text[text.index(kernel + ":"):]
@@ -174,3 +178,74 @@ def test_block_kernels_use_no_scratch():
     fixed = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M))
     block = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_block_kernel\w*):", text, re.M))
     assert packed(fixed) == packed(block) and len(packed(fixed)) > 100
+
+
+# ------------------------------------------------------------------------------- the shapes tests/test_block_wrap_gpu.py relies on
+def test_wrap_case_shapes(mh):
+    """Every (n, active count, "block_units") of tests/test_block_wrap_gpu.py: the rows the sweep writes fit ensure_block's
+    buffer (slots + 16 U), and on 256 CUs the cases hold units equal to the plain grid exactly, two passes, and at least 3 passes
+    of the plain grid with 4 of the option forms' grid."""
+    import block_wrap as W
+    for n in W.CUTS:
+        assert W.slots_of(n) == mh.slice_slots(n, 1), n
+    assert (W.GRID_PLAIN, W.GRID_OPTION) == (1280, 1024)
+    seen = []
+    for n, active, units in W.cases():
+        slots = W.slots_of(n)
+        groups, chunks, walked = W.plan(active, units, slots // W.TILE)
+        assert 1 <= chunks <= slots // W.TILE and walked == groups * chunks
+        assert W.GROUP * walked <= slots + W.GROUP * units, (n, active, units, walked)
+        seen.append((n, active, units, walked, W.passes(walked, W.GRID_PLAIN), W.passes(walked, W.GRID_OPTION)))
+    for line in sorted(set(x for x in seen if x[1] >= x[0] // 2)):
+        print("n=%d active=%d U=%d: %d units, %d passes of 1280, %d of 1024" % line)
+    walked = [x[3] for x in seen]
+    assert W.GRID_PLAIN in walked, "no case fills the plain grid exactly"
+    assert any(x[4] == 2 for x in seen) and any(x[5] == 2 for x in seen)
+    assert any(x[4] >= 3 and x[5] >= 4 for x in seen if x[0] == W.MAIN)
+    deep = max(x[3] for x in seen if x[0] == W.DEEP)
+    assert deep == 577 * 20 == 11540 and W.passes(deep, W.GRID_PLAIN) == 10 and W.passes(deep, W.GRID_OPTION) == 12
+    # the cut of 10 tiles into 7 chunks, and the small sets stay inside one pass of either grid
+    assert W.cut(10, 7) == [1, 1, 2, 1, 2, 1, 2] and W.cut(10, 4) == [2, 3, 2, 3] and W.cut(10, 10) == [1] * 10
+    for n in W.CUTS:
+        d = W.depth_set(n)
+        assert 64 <= len(d) <= 72 and 4 <= -(-len(d) // W.GROUP) <= 5
+        assert -(-len(d) // W.GROUP) * (W.slots_of(n) // W.TILE) <= W.GRID_OPTION
+
+
+def test_tightest_row_sizing():
+    """n = 5 120 (10 tiles, no padding, 320 groups) with U = 320 x 9 + 1 = 2 881: 10 chunks, 51 200 row entries written of
+    51 216 allocated.  One unit less and the plan gives 9 chunks."""
+    import block_wrap as W
+    assert W.TIGHT_U == 2881 and W.slots_of(W.MAIN) == 5120
+    groups, chunks, walked = W.plan(W.MAIN, W.TIGHT_U, 10)
+    assert (groups, chunks, walked) == (320, 10, 3200)
+    assert W.GROUP * walked == 51200 and W.slots_of(W.MAIN) + W.GROUP * W.TIGHT_U == 51216
+    assert W.plan(W.MAIN, W.TIGHT_U - 1, 10)[1] == 9
+    # no (active, U) at all can pass the buffer: units <= max(U + groups - 1, groups) and 16 groups <= slots
+    for n in (W.MAIN, W.PADDED, W.DEEP, 17, 1024, 1025):
+        slots = W.slots_of(n)
+        for active in (1, 15, 16, 17, n // 2, n - 1, n):
+            for units in (1, 2, 15, 16, 17, 1279, 1280, 1281, W.TIGHT_U, 65536):
+                walked = W.plan(active, units, slots // W.TILE)[2]
+                assert W.GROUP * walked <= slots + W.GROUP * units, (n, active, units)
+
+
+def test_phi_lane_sums_depend_on_the_tile_order():
+    """numpy float32 emulation of a wave's phi sums on the dense system of tests/test_potential_gpu.py (n = 2 049, 5 tiles that
+    hold bodies): "tiles 1, 2, 3, 4, then the own tile 0" (a wave whose bodies all lie in tile 0) against "tile 4, then 0, 1, 2,
+    3" (a wave with one body each in tiles 0 ... 3: all four masked in the loop and added behind it).  The folded totals differ
+    for several probe bodies: a sweep whose mask is per wave gives a body's phi other bits in other company."""
+    import potential_ref as PR
+    s, soft = PR.dense()
+    probes = PR.dense_probes(64)
+    assert len(probes) == 64 and (probes < PR.TILE).all()
+    lanes = folded = 0
+    for b in probes:
+        acc_a, tot_a = PR.lane_sums_f32(s, soft, int(b), (1, 2, 3, 4, 0))
+        acc_b, tot_b = PR.lane_sums_f32(s, soft, int(b), (4, 0, 1, 2, 3))
+        lanes += int(not np.array_equal(acc_a.view(np.uint32), acc_b.view(np.uint32)))
+        folded += int(np.float32(tot_a).view(np.uint32) != np.float32(tot_b).view(np.uint32))
+        want = PR.phi_of(s, soft, rows=[int(b)])[0]
+        assert abs(float(tot_a) - want) <= PR.TOL_F64_MAX * want and abs(float(tot_b) - want) <= PR.TOL_F64_MAX * want
+    print(f"{lanes} of {len(probes)} probe bodies differ in a lane accumulator, {folded} in the folded total")
+    assert folded >= 4

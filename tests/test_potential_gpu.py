@@ -357,3 +357,62 @@ def test_plugin_end_to_end(gpu):
         assert plain.potential() is None
     with gpu.HostSim(n, "galaxy", soft=soft, dt=dt, integrator=1) as leap:
         assert leap.H.murbhost_sim_set_potential(leap.h, 1) == -1 and leap.potential() is None
+
+
+# ------------------------------------------------------------------------------- 8. phi and the company a body keeps in its wave
+@lru_cache(maxsize=None)
+def dense_system():
+    return PR.dense()
+
+
+@pytest.mark.parametrize("cut", ["one chunk", "one tile per chunk"])
+def test_phi_does_not_depend_on_the_wave_mates(gpu, cut):
+    """The active sweep's wave takes four bodies of the active list, whose order is unspecified: they can lie in four layout
+    tiles.  A body's phi, like its (a1, j1), must not change by a bit with the bodies that share its wave (include/murbhip.h).
+    Dense system, n = 2 049.  Reference bits: a block step of all 512 bodies of tile 0, where every wave has tile 0 as its only
+    own tile.  Against them, for 64 bodies b of tile 0: a step of {b, one body each of tiles 1, 2, 3} — exactly one wave, four
+    own tiles —, a step of b alone, and the step of all n bodies.  With one tile per chunk a partial sum holds one tile and no
+    order can matter: the control."""
+    s, soft = dense_system()
+    n, gm = len(s["m"]), H._gm(s)
+    probes = PR.dense_probes(64)
+    with hermite_sim(gpu, s, soft) as sim:
+        tiles = int(sim.info("slots")) // PR.TILE
+        chunks = 1 if cut == "one chunk" else tiles
+
+        def step(act):
+            act = np.asarray(act, np.int64)
+            sim.set_option("block_units", ((len(act) + 15) // 16) * chunks)
+            sim.upload(s)
+            sim.compute_acc_jerk()
+            levels = np.zeros(n, np.int32)
+            levels[act] = SHAPE_KMAX
+            sim.set_block_levels(levels, SHAPE_KMAX)
+            out = sim.evolve_block(float(SHAPE_DT_MAX), kmax=SHAPE_KMAX, max_steps=1)
+            assert out["body_steps"] == len(act)
+            return bits(sim.potential()), bits(np.stack(sim.acc() + sim.jerk()))
+
+        sim.compute_acc_jerk()
+        a0, j0 = np.stack(sim.acc()), np.stack(sim.jerk())
+        want_phi, want_aj = step(np.arange(PR.TILE))
+        qp, _ = B.predict_all(H._stack(s, Q), H._stack(s, V), a0, j0, np.zeros(n, np.int64), 1, SHAPE_DT_MAX, SHAPE_KMAX)
+        full = np.zeros(n)
+        full[probes] = PR.phi_f64(H._r32(qp), gm, soft, rows=probes)
+        assert_phi(want_phi.view(np.float32), full, f"{cut}: tile 0 active", rows=probes)
+        all_phi, all_aj = step(np.arange(n))
+        again_phi, again_aj = step(np.arange(n))
+        assert np.array_equal(all_aj, again_aj), f"{cut}: (a1, j1) of two all-n steps differ"
+        bad = {"four tiles": [], "alone": [], "all n": [int(b) for b in probes if all_phi[b] != want_phi[b]],
+               "all n, run to run": np.flatnonzero(all_phi != again_phi).tolist()}
+        assert np.array_equal(all_aj[:, probes], want_aj[:, probes]), f"{cut}: (a1, j1) differ between tile 0 and all n"
+        for k, b in enumerate(probes):
+            mates = [PR.TILE * t + (37 * k + 11 * t) % PR.TILE for t in (1, 2, 3)]
+            for what, act in (("four tiles", [int(b)] + mates), ("alone", [int(b)])):
+                phi, aj = step(act)
+                assert np.array_equal(aj[:, b], want_aj[:, b]), f"{cut}: (a1, j1) of body {b} differ, {what}"
+                if phi[b] != want_phi[b]:
+                    bad[what].append(int(b))
+        print(f"{cut} ({chunks} of {tiles} tiles): phi bits against the tile-0 step differ for "
+              + ", ".join(f"{len(v)} of {n if 'run' in k else len(probes)} bodies ({k})" for k, v in bad.items()))
+        assert not any(bad.values()), f"{cut}: phi depends on the bodies that share the wave: " + \
+            ", ".join(f"{k}: {len(v)} bodies, first {v[:8]}" for k, v in bad.items() if v)
