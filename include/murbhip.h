@@ -32,6 +32,35 @@
 extern "C" {
 #endif
 
+/* Call orders.  A context remembers results of earlier calls (forces, the pair potential, the Hermite integrator's (a0, j0), its
+ * step proposal, the metric sums, the bodies' levels) and every such shortcut is bit-identical to doing the work again.  Stated
+ * once, for every entry point and option:
+ *   Body-changing calls: murbhip_upload, murbhip_init_bodies, murbhip_upload_radii, murbhip_step(s), murbhip_evolve,
+ *     murbhip_evolve_block, murbhip_integrate_host_acc, murbhip_block_set_levels, murbhip_set_encounter, and a murbhip_set_option
+ *     that changes the value of any key not listed as result-neutral below.
+ *   Observers: murbhip_compute_acc, murbhip_compute_acc_jerk, murbhip_energy, murbhip_moments, murbhip_potential_energy, every
+ *     murbhip_download_*, murbhip_block_state, murbhip_evolve_dts, murbhip_encounters, murbhip_contacts, murbhip_sync,
+ *     murbhip_warmup, murbhip_get_info; a value-changing set of a result-neutral key: "energy_sweep" (every murbhip_energy is
+ *     the energy of the mode in force when it is called), "profile", "evolve_batch", "init_libm_fma"; and a change that is put
+ *     back before the next body-changing call: "contact" 1 <-> 2, or murbhip_set_encounter(r) then (0).
+ *   Refused calls: anything that returns MURBHIP_E_STATE or MURBHIP_E_INVALID.
+ *   C1  Deleting every observer and every refused call from a sequence of calls changes no bit of anything read afterwards:
+ *       state, accelerations and jerks, (nn, r2), (cp, gap2), phi, ticks and levels, out5 / out8, murbhip_evolve_dts and the hit
+ *       lists, energies and moments.
+ *   C2  An observer returns the bits it returns when it is the only observer at that point of the sequence.  murbhip_download_acc
+ *       is meant as the pair murbhip_compute_acc; download or murbhip_compute_acc_jerk; download: on its own it returns what the
+ *       evaluation that used the buffer last left there.
+ *   C3  A refused call returns its documented code and changes nothing.
+ *   C4  A value-changing murbhip_set_option of a key that enters the force plan or the layout of its partial rows — "variant",
+ *       "jsplit", "taper", "diag_tri", "sym_red", "sym_waves", "sym_wide", "sym_pass_mb", "pad_aware", "xcd_order",
+ *       "fuse_integrate", "overlap", "tri_first_pct", "tri_div" — drops the remembered forces and pair potential, and the metric
+ *       sums kept for murbhip_energy / murbhip_moments with them.  It does not drop the Hermite memory or the levels, and it is
+ *       no change of the bodies.  Results are thus a function of the state and of the options in force when the work is done,
+ *       never of those in force when something was remembered.
+ *   C5  While a block of murbhip_evolve_block is open, switching "nearest", "potential", or "contact" between 0 and non-zero is
+ *       refused with MURBHIP_E_STATE.
+ * tests/helpers/call_orders.py holds this classification as a table and tests/test_call_orders_gpu.py checks C1-C5 on sequences
+ * generated from it. */
 typedef struct murbhip_ctx murbhip_ctx;
 
 #define MURBHIP_UNIQUE_ID_BYTES 128
@@ -287,7 +316,8 @@ int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
  *   The values belong to the evaluation that produced them: after a step they are taken at that step's predicted end state,
  *   like (a1, j1).  Under block steps only the active bodies' entries are refreshed; an inactive body keeps its (nn, r2) bit
  *   for bit, exactly as it keeps its (a0, j0).  Switching the option drops the remembered evaluation, so a remembered
- *   (a0, j0) always has its neighbours beside it.  With 0 every result is what it was without the option, bit for bit.
+ *   (a0, j0) always has its neighbours beside it, and is refused (MURBHIP_E_STATE) while a block is open: the bodies sit at
+ *   their own times and only some of them would have neighbours.  With 0 every result is what it was without the option, bit for bit.
  *   The nearest-neighbour sweeps are kernels of their own (csrc/murb_kernels_hermite.h; DESIGN.md 4.9 has their cost).
  * murbhip_download_nearest: n entries each, either pointer may be NULL; waits for enqueued work.  MURBHIP_E_STATE when
  *   "nearest" is 0 or no such evaluation is current (murbhip_download_jerk's rule; while a block is open it returns every
@@ -448,39 +478,50 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    GPU from 4 097 bodies (5 blocks of 1024) up, except at 6 blocks, and in multi-GPU runs when a rank gets
  *                    >= 400 block pairs, the one-sided kernel otherwise (1; 2 = four i bodies per wave for a rank's slice of up
  *                    to 16 384 bodies; one GPU: with the state update in the tail of its launch, see "fuse_integrate").  1-6: one-sided variants, 7: persistent schedule
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "jsplit"         one-sided variants: number of j-chunks a body's sum is split into; variant 7:
  *                    scheduling rounds; variant 8: i-side sub-blocks per item (1, 2, 4, 8, 16).  0 = auto
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "taper"          variant 8: percentage (0..100) of each launch's work whose items are cut finer (the last
  *                    taper % in halves, the last taper/2 % in quarters): a shorter drain phase at the end of a launch.
  *                    -1 (default) = the plan's own choice
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "sym_pass_mb"    variant 8, one GPU: budget in MiB for the partial sums of one pass (0 = default: a quarter of the
  *                    device memory).  A problem whose partial sums exceed it (N > ~2.4 M bodies by default) is
  *                    evaluated in several passes over ranges of j columns that share one buffer, their row sums
  *                    accumulated in fp64 ("sym_passes" of murbhip_get_info says how many)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "diag_tri"       variant 8: 1 = a diagonal block (i block = j block) is cut into pieces of 128 i bodies that only
  *                    evaluate the j bodies from their own position on (36 instead of 64 units of work per diagonal
  *                    block); 0 = the full square with the i side kept.  -1 (default) = the plan's own choice
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "sym_red"        variant 8: how the i-side sums of a group are folded over the wave: 0 = in registers (permlane
  *                    swaps + DPP), 1 = through LDS (fewer VALU instructions).  -1 (default) = the plan's own choice
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "sym_waves"      variant 8: waves per workgroup, 4 or 8; 0 = auto (one GPU up to 27 blocks: 8 or 4 by a measured table per
  *                    block count together with the item length, profiles/r03_small_plan_table.txt; 4 otherwise)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "sym_wide"       variant 8: the pair factor as (G m / r) (1 / r^2), one packed multiply more per 4 pair terms (+6 %), instead
  *                    of G m (1 / r^3), whose cube leaves the normal fp32 range for r beyond 2^42 length units.  -1 (default) =
  *                    chosen by every murbhip_upload: 1 where the diagonal of the bodies' bounding box and the softening, added
  *                    in quadrature, exceed 2^34 length units (2^8 of headroom for the system to expand) or the softening is
  *                    below 2^-40, else 0; murbhip_init_bodies keeps 0.  0 / 1 force a form
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "pad_aware"      variant 8: 1 (default) = the zero-mass padding slots that fill a slice up to whole blocks of 1024 are
  *                    not walked: the emptier block of a pair goes on the walked (i) side and its items end at its last
  *                    real body; 0 = every block as if full (kept for the A/B: -3 % at N = 30 000, -4 % for a rank of 8
  *                    at N = 200 000)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "tri_div"        variant 8, several ranks: the items of the own-slice triangle's two launches (which run under the two
  *                    collectives and, with few blocks per slice, do not fill the chip) cut into 1, 2, 4 or 8 parts more
  *                    than the rectangles' items; 0 (default) = the plan's choice (~2 rounds of workgroups per launch)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "energy_sweep"   murbhip_energy on a pair-symmetric plan: 1 = the separate potential sweep of rounds 1-2 instead of the
  *                    pair potential summed inside a force evaluation (default 0); kept for the A/B and as a cross-check
  *   "xcd_order"      variant 8: 0 (default) = j-major item order (round-robin dispatch then gives XCD x the i
  *                    blocks x mod 8 of every j block); 1 = one contiguous run of items per XCD (measured:
  *                    more L2 misses, same time; kept for the comparison)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "profile"        1: bracket every force kernel with HIP events (read with murbhip_get_info); 2: also both collectives
  *                    on the exchange stream, the compute stream's waits for them (the EXPOSED part of the exchange) and
  *                    the compute stream's whole step - ~16 more event records per step, meant for a short diagnostic
@@ -488,6 +529,7 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *   "overlap"        sharded/rank mode: 0 = no overlap; 1 (default) = the own-slice work brackets the
  *                    exchanges on the compute stream; 2 = the own-slice triangle runs on a second,
  *                    lowest-priority compute stream next to the rectangle launch (pair-symmetric only)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "integrator"     0 (default) = the reference's update, Bodies.cpp:260-278; 1 = kick-drift-kick
  *                    leapfrog, the scheme the reference's gpu+leapfrog states (CUDABodies.cu:172-178) with
  *                    the force taken at the positions it belongs to: one force evaluation per step, the
@@ -509,6 +551,8 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    many as the remaining time takes at the step last seen, 64 at the most; 1..64 = exactly that many
  *                    (timing aid: a batch longer than the run needs ends in launches that find the done flag set and do
  *                    nothing, which tools/hermite_adaptive_rate.py times).  The results do not depend on it
+ *   "init_libm_fma"  murbhip_init_bodies: which build of glibc's sincosf the device reproduces (-1 default, 0, 1; see there).  Read
+ *                    by murbhip_init_bodies alone: result-neutral for everything else
  *   "block_units"    murbhip_evolve_block: U, the number of (group of 16 active bodies, j chunk) work units the active sweep
  *                    is cut into at least: chunks = ceil(U / groups) clamped to [1, layout tiles].  0 (default) = one per
  *                    workgroup the chip holds at once (5 per CU; info "block_units" / "block_grid"); up to 65 536.  The
@@ -516,7 +560,7 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *   "nearest"        0 (default), 1: the Hermite sweeps also keep every body's nearest neighbour and its r2 (see
  *                    murbhip_download_nearest above).  One shard with "integrator" 2 only (MURBHIP_E_STATE otherwise; while it is
  *                    1, "integrator" cannot leave 2, and it cannot return to 0 while an encounter radius is set).  Switching
- *                    it drops the remembered evaluation.  The active sweep then runs on 4 workgroups per CU instead of 5
+ *                    it drops the remembered evaluation and is refused (MURBHIP_E_STATE) while a block is open (C5).  The active sweep then runs on 4 workgroups per CU instead of 5
  *   "contact"        0 (default), 1, 2: the Hermite sweeps also keep every body's contact partner by radii and its gap2; 2 adds
  *                    the contact stop (see murbhip_upload_radii above).  One shard with "integrator" 2 only; excludes "nearest".
  *                    The active sweep then runs on 4 workgroups per CU instead of 5
@@ -527,6 +571,7 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    triangle that is launched before the rectangles, i.e. under the all-gather of positions;
  *                    the rest runs under the reduce-scatter of accelerations.  A tuning knob for real
  *                    interconnect latencies (bench.py picks it per run, untimed)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "exchange_p2p"   RCCL exchange only (MURBHIP_E_STATE otherwise): 1 = both exchanges of a step as grouped ncclSend / ncclRecv
  *                    instead of collectives.  Accelerations: under the half-ring schedule a rank only has contributions for
  *                    the floor(W/2) slices ahead of it, so it sends those chunks straight to their owners and adds up the
@@ -548,6 +593,7 @@ int murbhip_moments(murbhip_ctx* ctx, double* out10);
  *                    update runs in the tail of the force launch — one launch per step instead of two, bit-identical results
  *                    (N = 2 048: 7.2 instead of 13.4 us per step).  0 = two launches, and the round-2 rule for "variant" 0
  *                    (pair-symmetric from 3 blocks up)
+ *                    A plan key: a value-changing set drops the remembered forces and pair potential (C4)
  *   "solo_shard"     r >= 0: in a sharded context only shard r launches force work (timing aid: the
  *                    isolated per-step timeline of one rank of W; results are meaningless).  -1 = off
  *   "force_exchange" 1: run the position exchange even with a single rank/shard (self-test of the

@@ -2198,31 +2198,40 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
     if (!c || !key) return MURBHIP_E_INVALID;
     const std::string k(key);
     if (k == "solo_shard" || k == "force_exchange") c->acc_current = false;   // what acc_out covers changes
-    if (k == "variant") { if (value < 0 || value > kNumVariants) return MURBHIP_E_INVALID; c->in.variant = (int)value; }
-    else if (k == "jsplit") { if (value < 0 || value > kMaxParts / 2) return MURBHIP_E_INVALID; c->in.jsplit = (int)value; }
-    else if (k == "xcd_order") c->xcd_order = value ? 1 : 0;
-    else if (k == "pad_aware") c->pad_aware = value ? 1 : 0;
+    // A key that enters current_plan() or layout_key(): another value means another kernel, another cut of the sums or another
+    // layout of the partial rows (rebuilt zeroed, the pair potentials behind them gone).  What is remembered of the force plan
+    // belongs to the old value: drop it, so that results are a function of the state and of the options in force when the work
+    // is done.  The kept metric sums go with them: murbhip_energy's swept potential is the plan's sweep, and under leapfrog the
+    // kinetic energy takes its closing half kick from the plan's forces.  The Hermite memory, the levels and state_serial are
+    // not the force plan's and stay.
+    const auto plan_key = [c](auto& field, auto v) {
+        if (field != v) { c->acc_current = false; c->pe_current = false; c->metrics_serial = c->state_serial - 1; }
+        field = v;
+    };
+    if (k == "variant") { if (value < 0 || value > kNumVariants) return MURBHIP_E_INVALID; plan_key(c->in.variant, (int)value); }
+    else if (k == "jsplit") { if (value < 0 || value > kMaxParts / 2) return MURBHIP_E_INVALID; plan_key(c->in.jsplit, (int)value); }
+    else if (k == "xcd_order") plan_key(c->xcd_order, value ? 1 : 0);
+    else if (k == "pad_aware") plan_key(c->pad_aware, value ? 1 : 0);
     else if (k == "energy_sweep") c->energy_sweep = value ? 1 : 0;
     else if (k == "sym_wide") {
         if (value < -1 || value > 1) return MURBHIP_E_INVALID;
-        if ((int)value != c->sym_wide) { c->acc_current = false; c->pe_current = false; }   // the other form rounds differently
-        c->sym_wide = (int)value;
+        plan_key(c->sym_wide, (int)value);   // the other form rounds differently
     }
-    else if (k == "fuse_integrate") c->in.fuse_integrate = value ? 1 : 0;
+    else if (k == "fuse_integrate") plan_key(c->in.fuse_integrate, value ? 1 : 0);
     else if (k == "exchange_p2p") {
         if (value && (c->exchange != 1 || !rccl().Send || !rccl().Recv)) return MURBHIP_E_STATE;   // needs the RCCL exchange and ncclSend/ncclRecv
         RC_TRY(murbhip_sync(c));
         c->exchange_p2p = value ? 1 : 0;
     }
-    else if (k == "tri_div") { if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->in.tri_div = (int)value; }
+    else if (k == "tri_div") { if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MURBHIP_E_INVALID; plan_key(c->in.tri_div, (int)value); }
     else if (k == "init_libm_fma") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->init_libm_fma = (int)value; }
-    else if (k == "tri_first_pct") { if (value < 0 || value > 100) return MURBHIP_E_INVALID; c->tri_first_pct = (int)value; }
-    else if (k == "taper") { if (value < -1 || value > 100) return MURBHIP_E_INVALID; c->in.taper = (int)value; }
-    else if (k == "sym_pass_mb") { if (value < 0) return MURBHIP_E_INVALID; c->in.sym_pass_mb = value; }
-    else if (k == "diag_tri") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->in.diag_tri = (int)value; }
-    else if (k == "sym_red") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; c->in.sym_red = (int)value; }
-    else if (k == "sym_waves") { if (value != 0 && value != 4 && value != 8) return MURBHIP_E_INVALID; c->in.sym_waves = (int)value; }
-    else if (k == "overlap") { if (value < 0 || value > 2) return MURBHIP_E_INVALID; c->overlap = (int)value; }
+    else if (k == "tri_first_pct") { if (value < 0 || value > 100) return MURBHIP_E_INVALID; plan_key(c->tri_first_pct, (int)value); }
+    else if (k == "taper") { if (value < -1 || value > 100) return MURBHIP_E_INVALID; plan_key(c->in.taper, (int)value); }
+    else if (k == "sym_pass_mb") { if (value < 0) return MURBHIP_E_INVALID; plan_key(c->in.sym_pass_mb, value); }
+    else if (k == "diag_tri") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; plan_key(c->in.diag_tri, (int)value); }
+    else if (k == "sym_red") { if (value < -1 || value > 1) return MURBHIP_E_INVALID; plan_key(c->in.sym_red, (int)value); }
+    else if (k == "sym_waves") { if (value != 0 && value != 4 && value != 8) return MURBHIP_E_INVALID; plan_key(c->in.sym_waves, (int)value); }
+    else if (k == "overlap") { if (value < 0 || value > 2) return MURBHIP_E_INVALID; plan_key(c->overlap, (int)value); }
     else if (k == "integrator") {
         if (value < 0 || value > 2) return MURBHIP_E_INVALID;
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
@@ -2240,6 +2249,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (value && (c->contact || c->potential)) return MURBHIP_E_STATE;   // they use the rows' fourth floats (and two of them the per-slot arrays)
         if (!value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
         if ((int)value != c->nearest) {
+            if (c->blk_open) return MURBHIP_E_STATE;   // the inactive bodies of the open block have their neighbours or do not
             c->nearest = (int)value;
             invalidate_cached_forces(c);   // a remembered (a0, j0) always has its neighbours beside it
         }
