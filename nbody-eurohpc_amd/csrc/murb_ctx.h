@@ -108,6 +108,13 @@ struct Shard {
     float* herm_phi = nullptr;                // per slot: phi_i of the remembered evaluation (include/murbhip.h, "potential")
     double* pot_sums = nullptr;               // block sums of murbhip_potential_energy
     double* pot_sums_host = nullptr;          // ... and their pinned host copy
+    // field read-out (murbfield_at / murbfield_of): buffers of its own, allocated on first use and grown (ensure_field)
+    float* fld_in = nullptr;        // a launch's uploaded points: 6 planes of floats and one of ints (skip entries or bodies)
+    float4* fld_pts = nullptr;      // ... packed: two records per point
+    float* fld_out = nullptr;       // ... results: 7 planes
+    size_t fld_points = 0;          // points the three hold
+    float4* fld_part = nullptr;     // partial rows: fld_rows entries {ax, ay, az, phi}, then as many {jx, jy, jz, 0}
+    size_t fld_rows = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -148,6 +155,7 @@ enum ProfKind {
     kProfWaitGather,      // compute stream: idle in front of the rectangles, waiting for the gathered positions
     kProfWaitReduce,      // compute stream: idle in front of the state update, waiting for the reduced share
     kProfStep,            // compute stream: first launch of a step to the end of its state update
+    kProfField,           // compute stream: a sweep launch of the field read-out (murbfield.h); never part of the force figures
     kProfKinds
 };
 
@@ -192,6 +200,8 @@ struct murbhip_ctx {
     // contact by radii (Hermite sweeps); shares the per-slot arrays, the hit list and the counters above with "nearest"
     int contact = 0;                // "contact": 1 the sweeps keep every body's (cp, gap2) beside (a, j), 2 also the contact stop
     int potential = 0;              // "potential": the sweeps keep every body's phi_i beside (a, j); excludes "nearest" and "contact"
+    long field_chunks = 0;          // "field_chunks": j chunks of the field read-out; 0 = default (murb_field.h)
+    long field_batch = 0;           // "field_batch": its points per launch; 0 = default
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

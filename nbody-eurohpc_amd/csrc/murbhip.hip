@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/murbhip.h"
+#include "../../include/murbfield.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
 
@@ -1211,6 +1212,109 @@ int read_hit_list(murbhip_ctx* c, bool mine, int* i, int* j, float* v, unsigned 
     return 0;
 }
 
+// ---- field read-out (murbfield_at / murbfield_of; kernels: murb_kernels_hermite.h, planning: murb_field.h) ----------
+// Synchronous, on the compute stream, in launches of at most "field_batch" points.  Everything it writes is its own: the
+// uploaded points, their packed records, the partial rows and the results.  Of the context it reads rec[cur], vel and soft2.
+int ensure_field(Shard& sh, size_t points, size_t rows)
+{
+    if (points > sh.fld_points) {
+        shard_free(sh, sh.fld_in, 7 * sh.fld_points * sizeof(float));
+        shard_free(sh, sh.fld_pts, 2 * sh.fld_points * sizeof(float4));
+        shard_free(sh, sh.fld_out, 7 * sh.fld_points * sizeof(float));
+        sh.fld_points = 0;
+        RC_TRY(shard_alloc(sh, sh.fld_in, 7 * points * sizeof(float)));
+        RC_TRY(shard_alloc(sh, sh.fld_pts, 2 * points * sizeof(float4)));
+        RC_TRY(shard_alloc(sh, sh.fld_out, 7 * points * sizeof(float)));
+        sh.fld_points = points;
+    }
+    if (rows > sh.fld_rows) {
+        shard_free(sh, sh.fld_part, 2 * sh.fld_rows * sizeof(float4));
+        sh.fld_rows = 0;
+        RC_TRY(shard_alloc(sh, sh.fld_part, 2 * rows * sizeof(float4)));
+        sh.fld_rows = rows;
+    }
+    return 0;
+}
+
+// What both entry points share once their arguments are checked.  p: the six input planes (murbfield_at; p[3..5] null:
+// at rest) or all null (murbfield_of: idx are the bodies); out: ax ay az jx jy jz phi, null where not asked for.
+int field_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], const int* idx, bool of_bodies, float* const (&out)[7])
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, cap * (size_t)l.chunks));
+    const bool has_vel = p[3] != nullptr;
+    std::vector<float> host(7 * cap, 0.f);
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            const int planes = has_vel ? 6 : 3;
+            for (int k = 0; k < planes; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), planes * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (idx) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, idx + first, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.idx = idx ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = has_vel ? 1 : 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbFieldArgs fa{};
+        fa.rec = sh.rec[c->cur];
+        fa.vel = sh.vel;
+        fa.pts = sh.fld_pts;
+        fa.part_a = sh.fld_part;
+        fa.part_j = sh.fld_part + sh.fld_rows;
+        fa.groups = (int)(padded / MURB_FIELD_GROUP);
+        fa.chunks = l.chunks;
+        fa.tiles = l.tiles;
+        fa.stride = (unsigned int)padded;   // chunks * padded <= fld_rows
+        fa.soft2 = c->soft2;
+        const long units = (long)fa.groups * fa.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // 4 waves per SIMD: 4 workgroups per CU
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfField, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_force_field_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                           sh.compute, fa);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        hipLaunchKernelGGL(murb_field_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)fa.part_a, (const float4*)fa.part_j, sh.fld_out, (int)bn, fa.chunks, fa.stride, (unsigned int)cap);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        int lo = 7, hi = 0;   // the planes the caller asked for: one copy from the first to the last of them
+        for (int k = 0; k < 7; ++k)
+            if (out[k]) { lo = std::min(lo, k); hi = k + 1; }
+        if (lo < hi) HIP_TRY(hipMemcpy(host.data() + lo * cap, sh.fld_out + lo * cap, (size_t)(hi - lo) * cap * sizeof(float), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 7; ++k)
+            if (out[k]) std::memcpy(out[k] + first, host.data() + k * cap, bn * sizeof(float));
+    }
+    return 0;
+}
+
+// all of a group's pointers, or none of them
+inline bool all_or_none(std::initializer_list<const void*> group)
+{
+    size_t set = 0;
+    for (const void* q : group) set += q != nullptr;
+    return set == 0 || set == group.size();
+}
+
+inline int field_state(const murbhip_ctx* c)
+{
+    // the bodies of an open block sit at different times; several shards or ranks: not covered
+    return !c->uploaded || c->in.world != 1 || c->shards.size() != 1 || c->blk_open ? MURBHIP_E_STATE : 0;
+}
+
 }  // namespace
 
 // ===================================================================================== C ABI
@@ -1403,6 +1507,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.blk_ctl, sh.blk_ticks, sh.blk_levels, sh.blk_list, sh.blk_rec, sh.blk_vel, sh.blk_part);
         release(sh.nn_idx, sh.nn_r2, sh.enc);
         release(sh.herm_phi, sh.pot_sums);
+        release(sh.fld_in, sh.fld_pts, sh.fld_out, sh.fld_part);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -1745,6 +1850,72 @@ int murbhip_potential_energy(murbhip_ctx* c, double* w)
     double sum = 0.0;
     for (size_t b = 0; b < blocks; ++b) sum += sh.pot_sums_host[b];
     *w = sum;
+    return 0;
+}
+
+int murbfield_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const float* pvx,
+                 const float* pvy, const float* pvz, const int* skip, float* ax, float* ay, float* az, float* jx, float* jy,
+                 float* jz, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz}) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz, pvx, pvy, pvz})
+        for (unsigned long i = 0; q && i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[6] = {px, py, pz, pvx, pvy, pvz};
+    float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
+    return field_run(c, count, p, skip, false, out);
+}
+
+int murbfield_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* ax, float* ay, float* az, float* jx, float* jy,
+                 float* jz, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!bodies || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
+    return field_run(c, count, p, bodies, true, out);
+}
+
+int murbfield_layout(unsigned long n, long chunks_option, long batch_option, unsigned long* out4)
+{
+    if (n == 0 || !out4 || !murb_field_options_valid(chunks_option, batch_option)) return MURBHIP_E_INVALID;
+    const MurbFieldLayout l = murb_field_layout(n, chunks_option, batch_option);
+    const unsigned long count = out4[3];
+    out4[0] = (unsigned long)l.chunks;
+    out4[1] = l.groups;
+    out4[2] = murb_field_batches(l, count);
+    out4[3] = l.rows;
+    return 0;
+}
+
+int murbfield_set_option(murbhip_ctx* c, const char* key, long value)
+{
+    if (!c || !key) return MURBHIP_E_INVALID;
+    const std::string k(key);
+    if (k != "field_chunks" && k != "field_batch") return MURBHIP_E_INVALID;
+    const bool chunks = k == "field_chunks";
+    if (!murb_field_options_valid(chunks ? value : 0, chunks ? 0 : value)) return MURBHIP_E_INVALID;
+    (chunks ? c->field_chunks : c->field_batch) = value;   // read by the field read-out alone
+    return 0;
+}
+
+int murbfield_get_option(murbhip_ctx* c, const char* key, long* value)
+{
+    if (!c || !key || !value) return MURBHIP_E_INVALID;
+    const std::string k(key);
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);   // as resolved
+    if (k == "field_chunks") *value = l.chunks;
+    else if (k == "field_batch") *value = (long)l.batch;
+    else return MURBHIP_E_INVALID;
     return 0;
 }
 
@@ -2362,10 +2533,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "force_launches" || k == "force_ms_avg" || k == "force_ms_total" || k.rfind("span_", 0) == 0 || k == "compute_wait_ms_per_step") {
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
-        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step
+        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step"};
+                                                      "wait_reduce", "step", "field"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -215,6 +215,13 @@ int murbhost_sim_contacts(void *p, int *i, int *j, float *gap2, unsigned long ca
     }
     return 0;
 }
+// SimulationNBodyHIP::fieldAt (murbfield_at's arguments); murbhip's code
+int murbhost_sim_field_at(void *p, unsigned long count, const float *px, const float *py, const float *pz, const float *pvx,
+                          const float *pvy, const float *pvz, const int *skip, float *ax, float *ay, float *az, float *jx, float *jy,
+                          float *jz, float *phi)
+{
+    return static_cast<Sim *>(p)->sim->fieldAt(count, px, py, pz, pvx, pvy, pvz, skip, ax, ay, az, jx, jy, jz, phi);
+}
 int murbhost_sim_history_csv(void *p, const char *path)
 {
     try {

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "murbfield.h"
 #include "murbhip.h"
 
 template <typename T>
@@ -46,6 +47,13 @@ template <typename T> const accSoA_t<T> &SimulationNBodyHIP<T>::getAccSoA()
     murbhipCheck(murbhip_download_acc(hipBodiesPtr->getContext(), accSoA.ax.data(), accSoA.ay.data(),
                                       accSoA.az.data()), "murbhip_download_acc");
     return accSoA;
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::fieldAt(unsigned long count, const T *px, const T *py, const T *pz, const T *pvx, const T *pvy, const T *pvz,
+                                   const int *skip, T *ax, T *ay, T *az, T *jx, T *jy, T *jz, T *phi)
+{
+    return murbfield_at(hipBodiesPtr->getContext(), count, px, py, pz, pvx, pvy, pvz, skip, ax, ay, az, jx, jy, jz, phi);
 }
 
 template class SimulationNBodyHIP<float>;

@@ -27,6 +27,13 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     void synchronize();                    // that sync, for callers without HIP headers
     void warmUp(double milliseconds);      // force evaluations on the current state for about that long (state unchanged)
     const accSoA_t<T> &getAccSoA();        // accelerations of the last iteration (test hook)
+
+    // What the bodies, as they are on the device, make at `count` points of the caller's: acceleration, jerk and potential
+    // (murbfield_at's arguments and rules: velocities all three null = points at rest; skip null, or per point a body left
+    // out, -1 = none; every output group may be null).  A read-out: synchronous, nothing of the simulation changes.  Returns
+    // murbhip's code (0 = done) instead of ending the program: a refused call is the caller's to handle.
+    int fieldAt(unsigned long count, const T *px, const T *py, const T *pz, const T *pvx, const T *pvy, const T *pvz, const int *skip,
+                T *ax, T *ay, T *az, T *jx, T *jy, T *jz, T *phi);
 };
 
 #endif

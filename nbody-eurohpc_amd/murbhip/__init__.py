@@ -81,6 +81,12 @@ def lib():
                                        C.POINTER(C.c_double)]
         L.murbhip_download_potential.argtypes = [C.c_void_p, _fp]
         L.murbhip_potential_energy.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        # include/murbfield.h
+        L.murbfield_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [C.POINTER(C.c_int)] + [_fp] * 7
+        L.murbfield_of.argtypes = [C.c_void_p, C.c_ulong, C.POINTER(C.c_int)] + [_fp] * 7
+        L.murbfield_layout.argtypes = [C.c_ulong, C.c_long, C.c_long, C.POINTER(C.c_ulong)]
+        L.murbfield_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
+        L.murbfield_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -105,6 +111,10 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
            "murbhip_download_potential murbhip_potential_energy "
            "murbhip_warmup murbhip_step murbhip_steps murbhip_integrate_host_acc murbhip_sync murbhip_energy murbhip_moments murbhip_set_option "
            "murbhip_get_info").split()
+
+
+FIELD_EXPORTS = "murbfield_at murbfield_of murbfield_layout murbfield_set_option murbfield_get_option".split()   # include/murbfield.h
+FIELD_OPTIONS = ("field_chunks", "field_batch")
 
 
 def error_string(code):
@@ -165,6 +175,18 @@ def schedule_layout(n, world, rank, split=1, waves=4, taper=0, tri_first_pct=50,
     _check(lib().murbhip_schedule_layout(*args, items.ctypes.data_as(lp), ni.value, C.byref(ni), rows.ctypes.data_as(lp), nr.value,
                                          C.byref(nr), C.byref(fm), C.byref(ft)), "murbhip_schedule_layout")
     return items, rows, fm.value, ft.value
+
+
+def field_layout(n, chunks=0, batch=0, count=0):
+    """dict of the field read-out's planning for n bodies under "field_chunks" = chunks and "field_batch" = batch (host only;
+    include/murbfield.h: murbfield_layout): chunks, groups of 16 points per full launch, launches for `count` points, entries
+    of a partial-row buffer, and the chunks' tile ranges [(first, end), ...]."""
+    out = (C.c_ulong * 4)(0, 0, 0, count)
+    _check(lib().murbfield_layout(n, chunks, batch, out), "murbfield_layout")
+    tiles = (n + 511) // 512
+    k = int(out[0])
+    return {"chunks": k, "groups": int(out[1]), "batches": int(out[2]), "rows": int(out[3]), "tiles": tiles,
+            "ranges": [(tiles * c // k, tiles * (c + 1) // k) for c in range(k)]}
 
 
 def device_count():
@@ -340,6 +362,37 @@ class Simulation:
         _check(lib().murbhip_potential_energy(self._h, C.byref(w)), "murbhip_potential_energy")
         return w.value
 
+    _FIELD_KEYS = ("ax", "ay", "az", "jx", "jy", "jz", "phi")
+
+    def field_at(self, points, velocities=None, skip=None):
+        """Acceleration, jerk and potential the bodies make at `points` (3, count), moving with `velocities` (3, count; None = at
+        rest), with body skip[k] (or none: -1, or skip=None) left out for point k (include/murbfield.h: murbfield_at).  A dict of
+        float32 arrays ax ay az jx jy jz phi.  A read-out: synchronous, changes nothing of the simulation."""
+        p = [_f32(x) for x in points]
+        v = [_f32(x) for x in velocities] if velocities is not None else None
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p + (v or [])) or (v is not None and len(v) != 3):
+            raise ValueError("points and velocities are three arrays of one length each")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        out = {k: np.zeros(count, np.float32) for k in self._FIELD_KEYS}
+        _check(lib().murbfield_at(self._h, count, *[_ptr(x) for x in p], *([_ptr(x) for x in v] if v else [None] * 3),
+                                      sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                      *[_ptr(out[k]) for k in self._FIELD_KEYS]), "murbfield_at")
+        return out
+
+    def field_of(self, bodies):
+        """field_at at the listed bodies' own current positions and velocities, each with itself left out (include/murbfield.h:
+        murbfield_of); the gather happens on the device."""
+        b = np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        out = {k: np.zeros(b.shape[0], np.float32) for k in self._FIELD_KEYS}
+        _check(lib().murbfield_of(self._h, b.shape[0], b.ctypes.data_as(C.POINTER(C.c_int)), *[_ptr(out[k]) for k in self._FIELD_KEYS]),
+               "murbfield_of")
+        return out
+
     def contacts(self):
         """dict of the step that ended the last evolve call by a contact ("contact" 2): i, j (int32), gap2 (float32) sorted by
         i, the count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
@@ -377,6 +430,16 @@ class Simulation:
     # -- tuning / facts
     def set_option(self, key, value):
         _check(lib().murbhip_set_option(self._h, key.encode(), int(value)), f"murbhip_set_option({key})")
+
+    def set_field_option(self, key, value):
+        """"field_chunks" / "field_batch" of field_at() and field_of() (include/murbfield.h: murbfield_set_option)."""
+        _check(lib().murbfield_set_option(self._h, key.encode(), int(value)), f"murbfield_set_option({key})")
+
+    def field_option(self, key):
+        """The value of a field option in force, defaults resolved (include/murbfield.h: murbfield_get_option)."""
+        f = C.c_long()
+        _check(lib().murbfield_get_option(self._h, key.encode(), C.byref(f)), f"murbfield_get_option({key})")
+        return f.value
 
     def info(self, key):
         v = C.c_double()
@@ -501,6 +564,7 @@ def host_lib():
         H.murbhost_sim_set_contact.argtypes = [C.c_void_p, C.c_int, C.c_float]
         H.murbhost_sim_set_potential.argtypes = [C.c_void_p, C.c_int]
         H.murbhost_sim_potential.argtypes = [C.c_void_p, _fp]
+        H.murbhost_sim_field_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [C.POINTER(C.c_int)] + [_fp] * 7
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                             C.POINTER(C.c_ulong), _dp]
         _host = H
@@ -590,6 +654,19 @@ class HostSim:
         if self.H.murbhost_sim_potential(self.h, _ptr(phi)) != 0:
             return None
         return phi
+
+    def field_at(self, points, velocities=None, skip=None):
+        """SimulationNBodyHIP::fieldAt: Simulation.field_at on the plugin's bodies as they are on the device."""
+        p = [_f32(x) for x in points]
+        v = [_f32(x) for x in velocities] if velocities is not None else None
+        count = p[0].shape[0]
+        sk = np.ascontiguousarray(skip, np.int32) if skip is not None else None
+        out = {k: np.zeros(count, np.float32) for k in Simulation._FIELD_KEYS}
+        rc = self.H.murbhost_sim_field_at(self.h, count, *[_ptr(x) for x in p], *([_ptr(x) for x in v] if v else [None] * 3),
+                                          sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                          *[_ptr(out[k]) for k in Simulation._FIELD_KEYS])
+        _check(rc, "murbhost_sim_field_at")
+        return out
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
