@@ -234,7 +234,7 @@ int murbhip_download_jerk(murbhip_ctx* ctx, float* jx, float* jy, float* jz);
  * body) counts as +inf.  The first step of a call that finds no proposal — the remembered (a0, j0) were not left by an
  * adaptive step — is eta_start * min_i |a0| / |j0|, clamped likewise.  A candidate >= duration - t becomes
  * (float)(duration - t): that step is the last, and the clock is set to `duration` exactly.  No growth limiter.  The
- * criterion is evaluated in fp64 without contraction in the order fixed in csrc/murb_kernels_hermite.h
+ * criterion is evaluated in fp64 without contraction in the order fixed in csrc/murb_kernels_adaptive.h
  * (murb_evolve_body_step), and the chosen step is rounded once to fp32; the steps themselves are murbhip_step's,
  * bit for bit.  Step size, clock and the end of the run live on the device: the host enqueues batches of steps and looks
  * at the control block once per batch (one stream sync), so the call returns after a sync.
@@ -318,7 +318,7 @@ int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
  *   for bit, exactly as it keeps its (a0, j0).  Switching the option drops the remembered evaluation, so a remembered
  *   (a0, j0) always has its neighbours beside it, and is refused (MURBHIP_E_STATE) while a block is open: the bodies sit at
  *   their own times and only some of them would have neighbours.  With 0 every result is what it was without the option, bit for bit.
- *   The nearest-neighbour sweeps are kernels of their own (csrc/murb_kernels_hermite.h; DESIGN.md 4.9 has their cost).
+ *   The nearest-neighbour sweeps are kernels of their own (csrc/murb_kernels_side.h; DESIGN.md 4.9 has their cost).
  * murbhip_download_nearest: n entries each, either pointer may be NULL; waits for enqueued work.  MURBHIP_E_STATE when
  *   "nearest" is 0 or no such evaluation is current (murbhip_download_jerk's rule; while a block is open it returns every
  *   body's values at its own time, like the other download hooks).

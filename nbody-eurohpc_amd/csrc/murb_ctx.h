@@ -9,7 +9,8 @@
 
 #include "murb_choose.h"
 #include "murb_crew.h"
-#include "murb_kernels_hermite.h"
+#include "murb_kernels_block.h"     // murb_kernels_pair.h, _side.h, _hermite.h, _adaptive.h on the way
+#include "murb_kernels_field.h"
 #include "murb_kernels_sym.h"
 #include "murb_rccl.h"
 

@@ -805,6 +805,46 @@ inline float encounter_threshold(const murbhip_ctx* c)
     return c->enc_radius > 0.f ? (float)((double)c->enc_radius * (double)c->enc_radius + (double)c->soft2) : -1.f;
 }
 
+// The side product the Hermite sweeps keep: murbhip_set_option lets at most one of the three options be on.
+inline MurbSide sweep_side(const murbhip_ctx* c)
+{
+    return c->potential ? MurbSide::Potential : c->contact ? MurbSide::Contact : c->nearest ? MurbSide::Nearest : MurbSide::None;
+}
+
+// side -> the kernel of the fixed sweep and of the active sweep.  The forms with a side product take the control block of an
+// adaptive step or null; the plain fixed sweep is two kernels, one that takes none and one that takes it.
+#define MURB_SWEEP(name) ((const void*)name<kHermiteR, kHermiteWaves, kHermiteStage>)
+const void* fixed_sweep_kernel(const MurbSide side, const bool with_ctl)
+{
+    switch (side) {
+    case MurbSide::Potential: return MURB_SWEEP(murb_force_jerk_pot_kernel);
+    case MurbSide::Contact: return MURB_SWEEP(murb_contact_sweep_kernel);
+    case MurbSide::Nearest: return MURB_SWEEP(murb_nn_sweep_kernel);
+    case MurbSide::None: break;
+    }
+    return !with_ctl ? MURB_SWEEP(murb_force_jerk_kernel) : MURB_SWEEP(murb_force_jerk_adaptive_kernel);
+}
+const void* active_sweep_kernel(const MurbSide side)
+{
+    switch (side) {
+    case MurbSide::Potential: return MURB_SWEEP(murb_force_jerk_pot_block_kernel);
+    case MurbSide::Contact: return MURB_SWEEP(murb_contact_active_sweep_kernel);
+    case MurbSide::Nearest: return MURB_SWEEP(murb_nn_active_sweep_kernel);
+    case MurbSide::None: break;
+    }
+    return MURB_SWEEP(murb_force_jerk_block_kernel);
+}
+#undef MURB_SWEEP
+
+// the per-slot arrays of the side product as the correctors take them (MurbHermiteArgs, MurbBlockArgs)
+template <typename Args>
+void side_slots(const murbhip_ctx* c, const Shard& sh, Args& a)
+{
+    if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
+    a.contact = c->contact;
+    if (c->potential) a.phi = sh.herm_phi;
+}
+
 MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, float dt, int update_state)
 {
     MurbHermiteArgs a{};
@@ -820,15 +860,13 @@ MurbHermiteArgs hermite_args(const murbhip_ctx* c, const Shard& sh, int parts, f
     a.stride = (unsigned int)c->in.slots;
     a.dt = dt;
     a.update_state = update_state;
-    if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
-    a.contact = c->contact;
-    if (c->potential) a.phi = sh.herm_phi;
+    side_slots(c, sh, a);
     return a;
 }
 
 // accelerations and jerks of the state (rec, vel) into the partial rows.  `ctl`: the control-block form of an adaptive step
 // (enqueue_hermite_adaptive), which records no timing span.
-int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts, MurbEvolveCtl* ctl = nullptr)
+int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, int parts, const MurbEvolveCtl* ctl = nullptr)
 {
     MurbNNJerkArgs a{};   // the plain sweeps take its base
     a.count = (int)sh.count;
@@ -842,40 +880,16 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
     a.soft2 = c->soft2;
     constexpr int group = kHermiteWaves * kHermiteR;
     const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);   // whole i groups: the extra slots hold mass 0
-    if (!ctl) {
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfForce, sh.compute, &rc);
-        RC_TRY(rc);
-        if (c->potential)
-            hipLaunchKernelGGL((murb_force_jerk_pot_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                               (const MurbEvolveCtl*)nullptr);
-        else if (c->contact)
-            hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                               (const MurbEvolveCtl*)nullptr);
-        else if (c->nearest)
-            hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                               (const MurbEvolveCtl*)nullptr);
-        else
-            hipLaunchKernelGGL((murb_force_jerk_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute,
-                               (const MurbJerkArgs&)a);
-        RC_TRY(hip_rc(hipGetLastError()));
-        RC_TRY(span_end(sh, sp, sh.compute));
-        note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
-        return 0;
-    }
-    if (c->potential)
-        hipLaunchKernelGGL((murb_force_jerk_pot_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                           (const MurbEvolveCtl*)ctl);
-    else if (c->contact)
-        hipLaunchKernelGGL((murb_contact_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                           (const MurbEvolveCtl*)ctl);
-    else if (c->nearest)
-        hipLaunchKernelGGL((murb_nn_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0, sh.compute, a,
-                           (const MurbEvolveCtl*)ctl);
-    else
-        hipLaunchKernelGGL((murb_force_jerk_adaptive_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), grid, dim3(kHermiteWaves * 64), 0,
-                           sh.compute, (const MurbJerkArgs&)a, (const MurbEvolveCtl*)ctl);
-    return hip_rc(hipGetLastError());
+    void* args[] = {&a, &ctl};   // a kernel takes as many as it has, and of `a` what its parameter's type holds
+    int rc = 0;
+    const int sp = ctl ? -1 : span_begin(c, sh, kProfForce, sh.compute, &rc);
+    RC_TRY(rc);
+    (void)hipLaunchKernel(fixed_sweep_kernel(sweep_side(c), ctl != nullptr), grid, dim3(kHermiteWaves * 64), args, 0, sh.compute);
+    RC_TRY(hip_rc(hipGetLastError()));
+    if (ctl) return 0;
+    RC_TRY(span_end(sh, sp, sh.compute));
+    note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
+    return 0;
 }
 
 // update_state 0: make sure (a0, j0) of the current state are remembered; 1: one step.
@@ -924,7 +938,7 @@ int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
     return 0;
 }
 
-// ---- shared adaptive steps (murbhip_evolve; control block and kernels: murb_kernels_hermite.h) --------------------------
+// ---- shared adaptive steps (murbhip_evolve; control block and kernels: murb_kernels_adaptive.h) -------------------------
 constexpr int kEvolveBatch = 64;                              // steps enqueued between two looks at the control block
 constexpr size_t kEvolveHead = offsetof(MurbEvolveCtl, ring);   // what the host reads back after a batch
 
@@ -949,7 +963,7 @@ int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
     return 0;
 }
 
-// ---- individual block time steps (murbhip_evolve_block; control block and kernels: murb_kernels_hermite.h, third part) -------
+// ---- individual block time steps (murbhip_evolve_block; control block and kernels: murb_kernels_block.h) ----------------------
 constexpr int kBlockBatch = 64;        // block steps enqueued between two looks at the control block
 constexpr int kBlockMaxUnits = 65536;  // "block_units"
 
@@ -996,9 +1010,7 @@ MurbBlockArgs block_args(const murbhip_ctx* c, const Shard& sh)
     a.ticks = sh.blk_ticks;
     a.levels = sh.blk_levels;
     a.list = sh.blk_list;
-    if (c->nearest || c->contact) { a.nn_idx = sh.nn_idx; a.nn_r2 = sh.nn_r2; a.enc = sh.enc; }
-    a.contact = c->contact;
-    if (c->potential) a.phi = sh.herm_phi;
+    side_slots(c, sh, a);
     a.count = (int)sh.count;
     a.stride = (unsigned int)c->in.slots;
     a.soft2 = c->soft2;
@@ -1012,25 +1024,14 @@ int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
     hipLaunchKernelGGL(murb_block_min_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_predict_kernel, dim3(per_pair), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_plan_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
-    if (c->nearest || c->contact || c->potential) {   // 4 waves per SIMD: 4 resident workgroups per CU
-        MurbBlockNNSweepArgs na{};
-        na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
-        na.grid = block_grid(c) / 5 * 4;
-        na.ctl = sh.blk_ctl;
-        if (c->potential)
-            hipLaunchKernelGGL((murb_force_jerk_pot_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
-                               dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
-        else if (c->contact)
-            hipLaunchKernelGGL((murb_contact_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
-                               dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
-        else
-        hipLaunchKernelGGL((murb_nn_active_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)na.grid),
-                           dim3(kHermiteWaves * 64), 0, sh.compute, na, (const MurbBlockCtl*)sh.blk_ctl);
-    } else {
-        const MurbBlockSweepArgs sa{a.rec_pred, a.vel_pred, a.soft2};
-        hipLaunchKernelGGL((murb_force_jerk_block_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)block_grid(c)),
-                           dim3(kHermiteWaves * 64), 0, sh.compute, sa, sh.blk_ctl);
-    }
+    const MurbSide side = sweep_side(c);
+    MurbBlockNNSweepArgs na{};   // the plain sweep takes its base
+    na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
+    na.grid = side == MurbSide::None ? block_grid(c) : block_grid(c) / 5 * 4;   // with a side product 4 waves per SIMD: 4 resident workgroups per CU
+    na.ctl = sh.blk_ctl;
+    const MurbBlockCtl* ctl = sh.blk_ctl;
+    void* args[] = {&na, &ctl};   // an error of this launch shows in hipGetLastError below, like the others'
+    (void)hipLaunchKernel(active_sweep_kernel(side), dim3((unsigned)na.grid), dim3(kHermiteWaves * 64), args, 0, sh.compute);
     hipLaunchKernelGGL(murb_block_correct_kernel, dim3(per_body), dim3(256), 0, sh.compute, a, sh.blk_ctl);
     hipLaunchKernelGGL(murb_block_book_kernel, dim3(1), dim3(1), 0, sh.compute, sh.blk_ctl);
     return hip_rc(hipGetLastError());
@@ -1183,6 +1184,30 @@ int enqueue_radii_lanes(murbhip_ctx* c)
     return hip_rc(hipGetLastError());
 }
 
+// "nearest", "contact", "potential": the side products of the Hermite sweeps.  One shard under "integrator" 2; at most one of
+// them at a time, because all three use the rows' fourth floats (and two of them the per-slot arrays); no change of form
+// while a block is open, whose inactive bodies have their side product or do not (with "contact": whose velocity records
+// carry the radii or do not); and a change drops the remembered forces: a remembered (a0, j0) always has its side product
+// beside it.  The order of the checks decides which error a refused call reports.
+int set_side_option(murbhip_ctx* c, const std::string& k, long value)
+{
+    const bool nearest = k == "nearest", contact = k == "contact";
+    int& field = nearest ? c->nearest : contact ? c->contact : c->potential;
+    if (value < 0 || value > (contact ? 2 : 1)) return MURBHIP_E_INVALID;   // "contact" 2: with the contact stop
+    if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+    if (value && c->nearest + c->contact + c->potential != field) return MURBHIP_E_STATE;   // another one is on
+    if (nearest && !value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
+    if ((field != 0) != (value != 0)) {
+        if (c->blk_open) return MURBHIP_E_STATE;
+        field = (int)value;
+        if (contact) c->enc_count = 0;
+        invalidate_cached_forces(c);
+        if (contact) RC_TRY(enqueue_radii_lanes(c));
+    }
+    field = (int)value;   // "contact" 1 <-> 2: only the stop; the evaluation and an open block stay
+    return 0;
+}
+
 // The hit list of the last evolve call (encounters or contacts: the options exclude each other), sorted by i.
 int read_hit_list(murbhip_ctx* c, bool mine, int* i, int* j, float* v, unsigned long capacity, unsigned long* count, double* time)
 {
@@ -1212,7 +1237,7 @@ int read_hit_list(murbhip_ctx* c, bool mine, int* i, int* j, float* v, unsigned 
     return 0;
 }
 
-// ---- field read-out (murbfield_at / murbfield_of; kernels: murb_kernels_hermite.h, planning: murb_field.h) ----------
+// ---- field read-out (murbfield_at / murbfield_of; kernels: murb_kernels_field.h, planning: murb_field.h) ----------
 // Synchronous, on the compute stream, in launches of at most "field_batch" points.  Everything it writes is its own: the
 // uploaded points, their packed records, the partial rows and the results.  Of the context it reads rec[cur], vel and soft2.
 int ensure_field(Shard& sh, size_t points, size_t rows)
@@ -2414,41 +2439,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (value < 0 || value > kEvolveBatch) return MURBHIP_E_INVALID;
         c->evolve_batch = (int)value;
     }
-    else if (k == "nearest") {
-        if (value != 0 && value != 1) return MURBHIP_E_INVALID;
-        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
-        if (value && (c->contact || c->potential)) return MURBHIP_E_STATE;   // they use the rows' fourth floats (and two of them the per-slot arrays)
-        if (!value && c->enc_radius > 0.f) return MURBHIP_E_STATE;   // the encounter stop reads the neighbours: murbhip_set_encounter(0) first
-        if ((int)value != c->nearest) {
-            if (c->blk_open) return MURBHIP_E_STATE;   // the inactive bodies of the open block have their neighbours or do not
-            c->nearest = (int)value;
-            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its neighbours beside it
-        }
-    }
-    else if (k == "contact") {
-        if (value < 0 || value > 2) return MURBHIP_E_INVALID;
-        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
-        if (value && (c->nearest || c->potential)) return MURBHIP_E_STATE;   // they use the rows' fourth floats (and two of them the per-slot arrays)
-        const bool was = c->contact != 0, now = value != 0;
-        if (was != now) {
-            if (c->blk_open) return MURBHIP_E_STATE;   // the open block's velocity records carry the radii or do not
-            c->contact = (int)value;
-            c->enc_count = 0;
-            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its contact partners beside it
-            RC_TRY(enqueue_radii_lanes(c));
-        }
-        c->contact = (int)value;   // 1 <-> 2: only the stop; the evaluation and an open block stay
-    }
-    else if (k == "potential") {
-        if (value != 0 && value != 1) return MURBHIP_E_INVALID;
-        if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
-        if (value && (c->nearest || c->contact)) return MURBHIP_E_STATE;   // all three use the rows' fourth floats
-        if ((int)value != c->potential) {
-            if (c->blk_open) return MURBHIP_E_STATE;   // the inactive bodies of the open block have their phi or do not
-            c->potential = (int)value;
-            invalidate_cached_forces(c);   // a remembered (a0, j0) always has its potentials beside it
-        }
-    }
+    else if (k == "nearest" || k == "contact" || k == "potential") RC_TRY(set_side_option(c, k, value));
     else if (k == "block_units") {
         if (value < 0 || value > kBlockMaxUnits) return MURBHIP_E_INVALID;
         c->block_units = (int)value;

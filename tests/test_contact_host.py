@@ -6,10 +6,8 @@ import collections
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 from functools import lru_cache
 
 import numpy as np
@@ -18,6 +16,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import code_object as CO   # noqa: E402
 import contact_ref as CR   # noqa: E402
 import nearest_ref as N    # noqa: E402
 
@@ -145,20 +144,11 @@ def test_contact_kernels_use_no_scratch():
     instruction per record, 16, none of them beside the 16-byte reads, and no 16-byte read of the plain sweep missing.  (The
     plain sweep's own ds_read_b128 count, 12, is therefore NOT the contact sweeps': 4 reads are wider, none is added to the 16
     records.)"""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*murb_contact_\S*)\n(.*?)\.wavefront_size", text, re.S))
-    fields = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")
     seen = {}
-    for name, meta in kernels.items():
-        num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1)) for f in fields}
+    for name, num in CO.metadata(r"murb_contact_").items():
         print(name, num)
         assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
         seen[re.search(r"(murb_[a-z_]+_kernel)", name).group(1)] = num["vgpr_count"]
@@ -169,12 +159,9 @@ def test_contact_kernels_use_no_scratch():
         assert seen[want] <= 128 or (seen[want] <= 168 and "3 waves per SIMD" in section), f"{want}: {seen[want]} vector registers"
 
     def counted(kernel, pattern):
-        body = text[text.index(kernel + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        return collections.Counter(re.findall(pattern, body, re.M))
+        return collections.Counter(CO.ops(kernel, pattern))
 
-    def symbol(short):
-        return next(k for k in re.findall(r"^(_Z\w*" + short + r"\w*):", text, re.M))
+    symbol = CO.symbol
 
     arith, lds = r"^\s*(v_pk_\w+|v_rsq_f32\w*)\b", r"^\s*(ds_read\w+)\b"
     plain, plain_lds = counted(symbol("murb_force_jerk_kernel"), arith), counted(symbol("murb_force_jerk_kernel"), lds)

@@ -4,10 +4,8 @@ object, and why a skipped body must never enter an fp32 sum."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,6 +13,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import code_object as CO      # noqa: E402
 import field_ref as F         # noqa: E402
 import hermite_ref as H       # noqa: E402
 import potential_ref as PR    # noqa: E402
@@ -189,30 +188,20 @@ def test_field_kernel_uses_no_scratch():
     """Code-object metadata of a fresh gfx950 build (the method of test_nearest_host.py): murb_force_field_kernel is there with 0
     bytes of scratch and 0 spilled registers and fits 4 waves per SIMD (at most 128 vector registers); its inner loop is the
     plain sweep's packed arithmetic plus one packed multiply (the mask) and one packed add (phi) per pair of interactions."""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     assert hipcc, "hipcc is needed: the library itself is built with it"
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*murb_force_field_kernel\S*)\n(.*?)\.wavefront_size", text, re.S))
+    kernels = CO.metadata(r"murb_force_field_kernel")
     assert len(kernels) == 1, "murb_force_field_kernel missing from the code object"
-    (name, meta), = kernels.items()
-    num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1))
-           for f in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")}
+    (name, num), = kernels.items()
     print(name, num)
     assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0
     assert num["vgpr_count"] <= 128, "no longer fits 4 waves per SIMD"
 
     def counts(kernel):
-        body = text[text.index(kernel + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        ops = [re.sub(r"_e(32|64)$", "", op) for op in re.findall(r"^\s*(v_pk_\w+|v_rsq_f32\w*)\b", body, re.M)]
-        return {k: ops.count(k) for k in set(ops)}, body
+        ops = [re.sub(r"_e(32|64)$", "", op) for op in CO.ops(kernel, r"^\s*(v_pk_\w+|v_rsq_f32\w*)\b")]
+        return {k: ops.count(k) for k in set(ops)}, CO.body(kernel)
 
-    plain, _ = counts(next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M)))
+    plain, _ = counts("murb_force_jerk_kernel")
     mine, body = counts(name)
     print("plain sweep", plain, "field sweep", mine)
     pairs = plain["v_rsq_f32"] // 2          # pairs of interactions of the unrolled tile: 4 lane steps x 4 points

@@ -3,7 +3,6 @@ step rule (tests/helpers/hermite_adaptive_ref.py) does on an eccentric binary an
 is for; the control-block kernels of a fresh gfx950 build use no scratch."""
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -13,6 +12,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import code_object as CO           # noqa: E402
 import hermite_adaptive_ref as A   # noqa: E402
 
 SOFT_BINARY = 1e6
@@ -110,31 +110,19 @@ def test_step_rule_edges():
 def test_adaptive_kernels_use_no_scratch():
     """Code-object metadata of a fresh gfx950 build: the six control-block kernels are there, with 0 bytes of scratch and 0
     spilled registers; the adaptive sweep has the fixed-step sweep's LDS and arithmetic."""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
-    import tempfile
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_evolve_|_adaptive_kernel)\S*)\n(.*?)\.wavefront_size", text, re.S))
+    kernels = CO.metadata(r"murb_evolve_|_adaptive_kernel")
     for want in ("murb_evolve_begin_kernel", "murb_evolve_first_kernel", "murb_evolve_start_kernel", "murb_evolve_book_kernel",
                  "murb_hermite_predict_adaptive_kernel", "murb_force_jerk_adaptive_kernel", "murb_hermite_correct_adaptive_kernel"):
         assert any(want in k for k in kernels), want + " missing from the code object"
-    for name, meta in kernels.items():
-        num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1))
-               for f in ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")}
+    for name, num in kernels.items():
         print(name, num)
         assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
 
     def packed(kernel):   # the packed fp32 instructions and reciprocal square roots of a kernel's body
-        body = text[text.index(kernel + ":"):]
-        body = body[:body.index(".Lfunc_end")]   # not the first s_endpgm: the adaptive kernel's early exit comes first
-        return sorted(re.findall(r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b", body, re.M))
+        return sorted(CO.ops(kernel, r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b"))
 
-    fixed = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M))
-    adaptive = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_adaptive_kernel\w*):", text, re.M))
+    fixed, adaptive = "murb_force_jerk_kernel", "murb_force_jerk_adaptive_kernel"
     assert packed(fixed) == packed(adaptive) and len(packed(fixed)) > 100

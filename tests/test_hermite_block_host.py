@@ -5,10 +5,8 @@ header carry the entry points, and the new kernels of a fresh gfx950 build use n
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 from functools import lru_cache
 
 import numpy as np
@@ -17,6 +15,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import code_object as CO           # noqa: E402
 import hermite_adaptive_ref as A   # noqa: E402
 import hermite_block_ref as B      # noqa: E402
 
@@ -146,23 +145,15 @@ def test_block_kernels_use_no_scratch():
     0 spilled registers; the active sweep has the fixed-step sweep's LDS and arithmetic and fits 5 waves per SIMD (at most
     96 vector registers: 512 / 5 rounded down to the allocation unit of 8).  The two potential kernels, likewise free of
     scratch and spills, fit 4 waves per SIMD (128 vector registers)."""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_block_|murb_force_jerk_block_|murb_force_jerk_pot_)\S*)\n(.*?)\.wavefront_size", text, re.S))
+    kernels = CO.metadata(r"murb_block_|murb_force_jerk_block_|murb_force_jerk_pot_")
     for want in ("murb_block_begin_kernel", "murb_block_start_kernel", "murb_block_min_kernel", "murb_block_predict_kernel",
                  "murb_block_plan_kernel", "murb_force_jerk_block_kernel", "murb_block_correct_kernel", "murb_block_book_kernel",
                  "murb_force_jerk_pot_kernel", "murb_force_jerk_pot_block_kernel"):
         assert any(want in k for k in kernels), want + " missing from the code object"
-    fields = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")
-    for name, meta in kernels.items():
-        num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1)) for f in fields}
+    for name, num in kernels.items():
         print(name, num)
         assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
         if "murb_force_jerk_block_kernel" in name:
@@ -171,12 +162,9 @@ def test_block_kernels_use_no_scratch():
             assert num["vgpr_count"] <= 128, name + " no longer fits 4 waves per SIMD"
 
     def packed(kernel):   # the packed fp32 instructions, reciprocal square roots and LDS reads of a kernel's body
-        body = text[text.index(kernel + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        return sorted(re.findall(r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b", body, re.M))
+        return sorted(CO.ops(kernel, r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b"))
 
-    fixed = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M))
-    block = next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_block_kernel\w*):", text, re.M))
+    fixed, block = "murb_force_jerk_kernel", "murb_force_jerk_block_kernel"
     assert packed(fixed) == packed(block) and len(packed(fixed)) > 100
 
 

@@ -3,7 +3,6 @@ the GPU tests (tests/helpers/hermite_ref.py) is pinned against itself — its je
 acceleration, its scheme is 4th order; the sweep, predictor and corrector kernels of a fresh gfx950 build use no scratch."""
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -13,7 +12,8 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
-import hermite_ref as H   # noqa: E402
+import code_object as CO   # noqa: E402
+import hermite_ref as H    # noqa: E402
 
 SOFT, DT = np.float32(2e8), np.float32(3600.0)
 
@@ -118,22 +118,15 @@ def test_restatement_pieces_agree(O):
 def test_new_kernels_use_no_scratch():
     """Code-object metadata of a fresh gfx950 build: the acceleration + jerk sweep, the predictor and the corrector
     are there, with 0 bytes of scratch and 0 spilled registers (as __graft_entry__.check_kernel_resources reads it)."""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
-    import tempfile
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_force_jerk|murb_hermite_)\S*)\n(.*?)\.wavefront_size", text, re.S))
+    kernels = CO.metadata(r"murb_force_jerk|murb_hermite_")
     for want in ("murb_force_jerk_kernel", "murb_hermite_predict_kernel", "murb_hermite_correct_kernel"):
         assert any(want in k for k in kernels), want + " missing from the code object"
     for name, meta in kernels.items():
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0, name
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) == 0, name
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", meta).group(1)) == 0, name
-    body = text[text.index("murb_force_jerk_kernel"):]
+        assert meta["private_segment_fixed_size"] == 0, name
+        assert meta["vgpr_spill_count"] == 0, name
+        assert meta["sgpr_spill_count"] == 0, name
+    body = CO.text()[CO.text().index("murb_force_jerk_kernel"):]
     assert "v_pk_fma_f32" in body and "ds_read_b128" in body

@@ -5,10 +5,8 @@ nothing, keep the plain sweep's packed arithmetic, and leave the plain kernels' 
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 from functools import lru_cache
 
 import numpy as np
@@ -17,6 +15,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import code_object as CO   # noqa: E402
 import nearest_ref as N   # noqa: E402
 
 E_INVALID = -2000
@@ -91,20 +90,11 @@ def test_nearest_kernels_use_no_scratch():
     there with 0 bytes of scratch and 0 spilled registers, their packed fp32 instructions, reciprocal square roots and LDS
     reads are exactly the plain sweep's, and they fit 4 waves per SIMD (at most 128 vector registers; DESIGN.md 4.9 records
     that decision and what it costs).  The plain kernels keep the register counts they had before the option existed."""
-    hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
+    hipcc = CO.hipcc()
     if not hipcc:
         pytest.skip("hipcc is not installed: no code object to inspect")
-    src = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc", "murbhip.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "murbhip.s")
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", src, "-o", asm],
-                       check=True, stderr=subprocess.DEVNULL)
-        text = open(asm).read()
-    kernels = dict(re.findall(r"\.name:\s+(\S*(?:murb_nn_|murb_force_jerk_)\S*)\n(.*?)\.wavefront_size", text, re.S))
-    fields = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "sgpr_count")
     seen = {}
-    for name, meta in kernels.items():
-        num = {f: int(re.search(r"\." + f + r":\s+(\d+)", meta).group(1)) for f in fields}
+    for name, num in CO.metadata(r"murb_nn_|murb_force_jerk_").items():
         print(name, num)
         assert num["private_segment_fixed_size"] == 0 and num["vgpr_spill_count"] == 0 and num["sgpr_spill_count"] == 0, name
         short = re.search(r"(murb_[a-z_]+_kernel)", name).group(1)
@@ -117,14 +107,12 @@ def test_nearest_kernels_use_no_scratch():
     assert sum("DESIGN" in f for f in os.listdir(ROOT)) and "4 waves per SIMD" in open(os.path.join(ROOT, "DESIGN.md")).read()
 
     def packed(kernel):
-        body = text[text.index(kernel + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        return sorted(re.findall(r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b", body, re.M))
+        return sorted(CO.ops(kernel, r"^\s*(v_pk_\w+|v_rsq_f32\w*|ds_read_b128)\b"))
 
-    plain = packed(next(k for k in re.findall(r"^(_Z\w*murb_force_jerk_kernel\w*):", text, re.M)))
+    plain = packed("murb_force_jerk_kernel")
     assert len(plain) > 100
     for want in ("murb_nn_sweep_kernel", "murb_nn_active_sweep_kernel"):
-        assert packed(next(k for k in re.findall(r"^(_Z\w*" + want + r"\w*):", text, re.M))) == plain, want
+        assert packed(want) == plain, want
 
 
 # ------------------------------------------------------------------------------------------------------ the dense tie lattice
