@@ -72,17 +72,17 @@ def _eval(points, pvel, skip, q, v, gm, soft, dtype, nsplit, want_abs, block=256
     return a, j, phi, ab
 
 
-def field_f64(points, pvel, skip, state, soft, want_abs=True):
+def field_f64(points, pvel, skip, state, soft, want_abs=True, block=256):
     """fp64 (a (3, P), j (3, P), phi (P), abs): the field of `state`'s bodies at `points` (3, P) moving with `pvel` (3, P or None:
     at rest), body skip[k] (or -1 / None: nobody) left out for point k.  abs: dict a, j, phi of the per-point sums of the terms'
-    magnitudes (with want_abs)."""
-    return _eval(points, pvel, skip, H._stack(state, Q), H._stack(state, V), H._gm(state), soft, np.float64, 1, want_abs)
+    magnitudes (with want_abs).  block: points evaluated at a time (memory alone; no value depends on it)."""
+    return _eval(points, pvel, skip, H._stack(state, Q), H._stack(state, V), H._gm(state), soft, np.float64, 1, want_abs, block)
 
 
-def field_f32(points, pvel, skip, state, soft, nsplit=128):
+def field_f32(points, pvel, skip, state, soft, nsplit=128, block=256):
     """The same formula in plain numpy float32, `nsplit` partial sums per point, then added (hermite_ref.acc_jerk_f32's shape)."""
     a, j, phi, _ = _eval(points, pvel, skip, H._stack(state, Q, np.float32), H._stack(state, V, np.float32), H._gm(state, np.float32),
-                         soft, np.float32, nsplit, False)
+                         soft, np.float32, nsplit, False, block)
     return a, j, phi
 
 
@@ -100,10 +100,10 @@ def scaled_errors(got, ref):
     return out
 
 
-def bound_of(points, pvel, skip, state, soft, ref=None):
+def bound_of(points, pvel, skip, state, soft, ref=None, block=256):
     """(ref, C): field_f64's result and, per quantity, C of the bound in units of 2^-24 (the module's docstring)."""
-    ref = field_f64(points, pvel, skip, state, soft) if ref is None else ref
-    e = scaled_errors(field_f32(points, pvel, skip, state, soft), ref)
+    ref = field_f64(points, pvel, skip, state, soft, block=block) if ref is None else ref
+    e = scaled_errors(field_f32(points, pvel, skip, state, soft, block=block), ref)
     return ref, {k: 4.0 * float(np.max(v, initial=0.0)) / U24 for k, v in e.items()}
 
 

@@ -449,3 +449,110 @@ def test_plugin_field_at(gpu):
     F.check(got, ref, c, "plugin")
     with make_sim(gpu, s, soft) as sim:
         assert F.same_bits(sim.field_at(p, v, skip), got) and F.same_bits(sim.field_at(p), at_rest)
+
+
+# ------------------------------------------------------------------------------------------------- 9. after the state has moved
+MOVE_N = 1025
+MOVE_DT = 2.0 ** -10      # one step of it moves a body by about 1e-3 of the box and its velocity by about 2 (CPU estimate: |a| is
+#                           about 2e3): the field of the state before that step misses the bound by 100 x or more nearly everywhere
+MOVES = [(0, "steps", 1), (0, "steps", 2), (1, "steps", 1), (1, "steps", 2), (2, "steps", 1), (2, "steps", 2), (2, "evolve", 3),
+         (2, "evolve_block", 0)]
+
+
+def _advance(sim, how, k, whole=None):
+    """Take the context through the run (k steps of its integrator, evolve() in k steps, or one block of evolve_block()) and
+    return its number of steps; with `whole`, that number, stop one step before the run's end."""
+    if how == "steps":
+        if whole is None or k > 1:
+            sim.steps(MOVE_DT, k if whole is None else k - 1)
+        return k
+    if how == "evolve":      # dt_min = dt_max: k steps of MOVE_DT
+        steps = k if whole is None else k - 1
+        out = sim.evolve(k * MOVE_DT, dt_min=MOVE_DT, dt_max=MOVE_DT, max_steps=steps)
+        assert out["steps"] == steps and out["dt_min"] == out["dt_max"] == MOVE_DT, out
+        return k
+    sim.compute_acc_jerk()
+    sim.set_block_levels(np.arange(sim.n) % 3, 2)      # by hand: the starting rule puts every body of this system at level 0, one step a block
+    out = sim.evolve_block(4 * MOVE_DT, blocks=1, kmax=2, **({} if whole is None else {"max_steps": whole - 1}))
+    assert out["synchronised"] == (whole is None) and out["steps"] == (whole - 1 if whole else out["steps"]) and out["steps"] >= 1, out
+    return out["steps"]
+
+
+def _check_some(got, ref, c, what, quantities):
+    if len(quantities) == 3:
+        return F.check(got, ref, c, what)
+    e = F.scaled_errors(got, ref)
+    fig = {k: float(np.max(e[k], initial=0.0)) / F.U24 for k in quantities}
+    print(f"{what}: scaled error in 2^-24: " + ", ".join(f"{k} {fig[k]:.2f} (bound {c[k]:.2f})" for k in quantities))
+    for k in quantities:
+        assert fig[k] <= c[k], f"{what}: {k} of point {int(np.argmax(e[k]))} off by {fig[k]:.2f} x 2^-24, bound {c[k]:.2f}"
+
+
+@pytest.mark.parametrize("integrator,how,k", MOVES)
+def test_field_of_the_moved_state(gpu, integrator, how, k):
+    """After steps of every integrator (k = 1 and 2: both record buffers have been the current one), after an evolve() to its end
+    and after an evolve_block() to its synchronised end: field_of(every body) and field_at(midpoints) meet the bound against fp64
+    evaluated at the state the context returns.  The probe has power (CPU): the fp64 field of the bodies as they were one step
+    earlier, and as they were uploaded, at the same points misses 100 x the bound on at least half the points, in every compared
+    quantity — a read-out that swept the other record buffer, or velocities a step old, fails.
+    "integrator" 1: the device's velocities are half a step behind the ones murbhip_download_state returns (include/murbfield.h),
+    so there a and phi alone are compared; they read positions only."""
+    s = F.system(MOVE_N)
+    n = MOVE_N
+    quantities = ("a", "phi") if integrator == 1 else ("a", "j", "phi")
+
+    def moved(sim):
+        return dict(sim.state(), m=s["m"])
+
+    with make_sim(gpu, s, integrator=integrator) as sim:
+        steps = _advance(sim, how, k)
+        assert steps >= 2 or how == "steps", "the run has a step before its last"
+        now = moved(sim)
+        of = sim.field_of(np.arange(n))
+        mp, mv, _ = F.midpoints(now, 64)
+        at = sim.field_at(mp, mv)
+        assert F.same_bits(of, sim.field_of(np.arange(n))) and all(np.array_equal(now[q], moved(sim)[q]) for q in now), "the read-out moved something"
+    with make_sim(gpu, s, integrator=integrator) as sim:
+        _advance(sim, how, k, whole=steps)
+        earlier = moved(sim)
+    bp, bv, bskip = F.body_points(now, np.arange(n))
+    what = f"integrator {integrator}, {how}" + (f" {k}" if k else "")
+    for name, got, (p, v, skip) in (("field_of", of, (bp, bv, bskip)), ("midpoints", at, (mp, mv, None))):
+        ref, c = F.bound_of(p, v, skip, now, F.SOFT)
+        for old_name, old in (("a step earlier", earlier), ("as uploaded", s)):
+            e = F.scaled_errors(F.field_f64(p, v, skip, old, F.SOFT, want_abs=False)[:3], ref)
+            share = {q: float((e[q] >= 100.0 * c[q] * F.U24).mean()) for q in quantities}
+            print(f"{what}, {name}: the bodies {old_name} miss 100 x the bound on " + ", ".join(f"{100 * share[q]:.0f} % ({q})" for q in quantities))
+            assert min(share.values()) >= 0.5, (what, name, old_name, share)
+        _check_some(got, ref, c, f"{what}: {name}", quantities)
+
+
+# --------------------------------------------------------------------------------------------------- 10. the sweeps' side options
+def test_side_options_change_nothing(gpu):
+    """The field bits of one set of points and of every body are the same with all side options off, with "nearest" 1, with
+    "contact" 1 and large radii uploaded (they ride in the velocity records' spare lanes, which the field never reads) and with
+    "potential" 1: on the uploaded state, and again behind a compute_acc_jerk() and one Hermite step."""
+    n = 2049
+    s, _ = case(n)
+    rng = np.random.default_rng(19)
+    p = rng.uniform(0.0, 1.0, (3, 64)).astype(np.float32)
+    v = (1e-3 * rng.standard_normal((3, 64))).astype(np.float32)
+    skip = rng.integers(-1, n, 64).astype(np.int32)
+    skip[:4] = (-1, 0, 511, n - 1)
+    want = None
+    for option in (None, "nearest", "contact", "potential"):
+        with make_sim(gpu, s, integrator=2, **({option: 1} if option else {})) as sim:
+            if option == "contact":
+                sim.upload_radii(np.full(n, 8.0, np.float32))
+            rec = [sim.field_at(p, v, skip), sim.field_of(np.arange(n))]
+            sim.compute_acc_jerk()
+            sim.step(MOVE_DT)
+            rec += [sim.field_at(p, v, skip), sim.field_of(np.arange(n))]
+            st = sim.state()
+        assert not F.same_bits(rec[0], rec[2]) and not F.same_bits(rec[1], rec[3]), "the step moved the bodies"
+        if want is None:
+            want, want_state = rec, st
+            continue
+        assert all(np.array_equal(F.bits(st[k]), F.bits(want_state[k])) for k in st), f'"{option}" 1 changed the step'
+        for k, (x, y) in enumerate(zip(rec, want)):
+            assert F.same_bits(x, y), f'"{option}" 1: field call {k} differs from the call with all side options off'

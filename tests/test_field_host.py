@@ -215,3 +215,130 @@ def test_field_kernel_uses_no_scratch():
     total = mine["v_pk_fma_f32"] + mine["v_pk_mul_f32"] + mine["v_pk_add_f32"]
     assert total <= (per_pair + 2) * (pairs + 4) + 4 * 10, "more than one packed instruction each for the mask and phi beside the sweep's"
     assert not re.search(r"\bscratch_|\bbuffer_", body)
+
+
+# ------------------------------------------------------------------------------------------- the walk beyond one grid pass
+import field_wrap as FW      # noqa: E402
+
+CASE_NAMES = ("A", "B", "C", "D", "E")
+
+
+def test_wrap_helper_plans_like_the_library(mh):
+    """field_wrap's chunk count, chunk cut and launches are murbfield_layout's, for every case and both grids."""
+    for grid in (FW.GRID, FW.SMALL_GRID):
+        for name, case in FW.cases(grid).items():
+            lay = mh.field_layout(case.n, chunks=case.chunks_option, batch=case.batch, count=case.count)
+            assert lay["chunks"] == case.chunks and lay["ranges"] == FW.cut(case.n, case.chunks), name
+            assert lay["batches"] == len(FW.launches(case.count, case.batch)) and lay["groups"] * 16 == (case.batch or FW.BATCH_DEFAULT), name
+            assert lay["rows"] >= max(g for _, _, g in FW.launches(case.count, case.batch)) * 16 * case.chunks, name
+
+
+def test_wrap_walk_visits_every_unit_once():
+    """unit_of over every workgroup and every k is each (group, chunk) once; a workgroup has no unit behind its first missing one."""
+    for groups, chunks, grid in ((3, 3, 1024), (7, 5, 8), (622, 5, 1024), (2, 2, 4), (5, 1, 2)):
+        units, blocks, passes = FW.walk(groups, chunks, grid)
+        seen = [FW.unit_of(b, k, groups, chunks, grid) for b in range(grid) for k in range(passes + 1)]
+        got = sorted(x for x in seen if x is not None)
+        assert got == sorted((g, c) for c in range(chunks) for g in range(groups)), (groups, chunks, grid)
+        assert blocks == min(units, grid) and passes == -(-units // grid) and FW.unit_of(0, passes, groups, chunks, grid) is None
+        late = FW.late_units(groups, chunks, grid)
+        assert late.sum() == units - blocks and all(late[c, g] == (k > 0) for b in range(blocks) for k in range(passes)
+                                                    for g, c in [FW.unit_of(b, k, groups, chunks, grid) or (None, None)] if g is not None)
+
+
+@pytest.mark.parametrize("grid", [FW.GRID, FW.SMALL_GRID])
+def test_wrap_cases_make_their_passes(grid):
+    """On 256 CUs (1 024 workgroups) and on a chip of 64, every case of tests/test_field_wrap_gpu.py makes the passes it claims,
+    a workgroup's second unit is what the case says it is, and the points claimed to have a row written in a later pass have one."""
+    table = FW.cases(grid)
+    for name, case in table.items():
+        walks = case.walks(grid)
+        print(name, case.n, case.chunks, FW.cut(case.n, case.chunks), walks)
+        assert case.passes(grid) >= case.passes_min, name
+        late, claimed = case.late_points(grid), case.claimed_late(grid)
+        assert (late >= claimed).all(), name
+        assert claimed.any() == (name != "E")
+        for sl in FW.one_pass_slices(case.count, case.chunks, grid):
+            assert FW.walk(-(-(sl.stop - sl.start) // 16), case.chunks, grid)[2] == 1, name
+        assert sum(sl.stop - sl.start for sl in FW.one_pass_slices(case.count, case.chunks, grid)) == case.count
+    a, b, c, d, e = (table[k] for k in CASE_NAMES)
+    # A: 3 passes or more, all points late, the last group padded, the next unit in another group AND another chunk
+    _, bn, groups, units, blocks, passes = a.walks(grid)[0]
+    assert len(a.walks(grid)) == 1 and passes >= 3 and blocks == grid and grid % groups != 0 and bn % 16 == 13 and a.claimed_late(grid).all()
+    assert a.chunks == 5 and FW.cut(a.n, 5) == [(k, k + 1) for k in range(5)] and a.n % 512 == 1
+    for blk in range(grid):
+        (g0, c0), (g1, c1) = FW.unit_of(blk, 0, groups, 5, grid), FW.unit_of(blk, 1, groups, 5, grid)
+        assert g0 != g1 and c0 != c1
+    # B: one launch under its own batch, one chunk: the next unit is another group of the same chunk
+    _, bn, groups, units, blocks, passes = b.walks(grid)[0]
+    assert len(b.walks(grid)) == 1 and b.chunks == 1 and passes == 3 and units == groups and bn % 16 == 7
+    assert FW.unit_of(3, 1, groups, 1, grid) == (3 + grid, 0) and FW.unit_of(3, 2, groups, 1, grid) == (3 + 2 * grid, 0) and units == 2 * grid + 5
+    assert not b.claimed_late(grid)[:16 * grid].any() and b.claimed_late(grid)[16 * grid:].all() and (b.late_points(grid) == b.claimed_late(grid)).all()
+    # C: the rule's two chunks, three launches, the last of 17 points and one pass; at 1 024 workgroups the next unit is the same group's next chunk
+    assert c.chunks == 2 and FW.cut(c.n, 2) == [(0, 8), (8, 17)] and c.chunks_option == 0 and c.batch == 0
+    assert [(first, bn, groups) for first, bn, groups, *_ in c.walks(grid)] == [(0, 16384, 1024), (16384, 16384, 1024), (32768, 17, 2)]
+    assert [w[5] for w in c.walks(grid)] == [2048 // grid, 2048 // grid, 1] and c.walks(grid)[2][3:5] == (4, 4)
+    assert c.claimed_late(grid)[:32768].all() and not c.late_points(grid)[32768:].any()
+    if grid == FW.GRID:
+        assert all(FW.unit_of(blk, 1, 1024, 2, grid) == (blk, 1) and FW.unit_of(blk, 0, 1024, 2, grid) == (blk, 0) for blk in range(grid))
+    # D: the cap of 16 chunks, 8 or 9 tiles each; the call of 64 makes one pass, the call of 3 200 points 3 200 units
+    assert d.chunks == 16 and FW.chunks_of(d.n + 512 * 40) == 16 and {hi - lo for lo, hi in FW.cut(d.n, 16)} == {8, 9}
+    assert d.walks(grid, 64)[0][3:] == (64, 64, 1) and d.walks(grid)[0][3] == 3200 and d.passes(grid) == -(-3200 // grid) and d.claimed_late(grid).all()
+    # E: three chunks of 8, 8 and 9 tiles (with two tiles a stage: an odd tail stage), one pass at every count
+    assert e.chunks == 3 and [hi - lo for lo, hi in FW.cut(e.n, 3)] == [8, 8, 9] and e.counts == (1, 16, 17, 33)
+    assert all(w[5] == 1 for count in e.counts for w in e.walks(grid, count))
+
+
+@pytest.mark.parametrize("grid", [FW.GRID, FW.SMALL_GRID])
+def test_wrap_subsets_and_points(grid):
+    """The rows compared with fp64 hold points of the first group, of a group in the middle and of the last, padded group, both
+    sides of every launch boundary and rows written in a later pass; the points hold all four kinds and the skip entries the
+    cases need: slot 0, a tile's last slot, the last real slot, a slot in the second and in the last tile of every chunk, and -1."""
+    for name, case in FW.cases(grid).items():
+        for count in (case.counts if name != "E" else case.counts[-1:]):
+            rows = FW.subset(case, grid, count)
+            groups = -(-count // 16)
+            assert len(rows) == len(set(rows.tolist())) and rows.min() == 0 and rows.max() == count - 1 and len(rows) * case.n <= 1.05 * FW.PAIRS_LIMIT
+            assert len(rows) >= min(count, 100)
+            for first, bn, launch_groups in FW.launches(count, case.batch):
+                for g in (0, launch_groups // 2, launch_groups - 1):
+                    assert (((rows - first) // 16 == g) & (rows >= first) & (rows < first + bn)).any(), (name, first, g)
+            assert ((rows // 16) == groups - 1).sum() == count - 16 * (groups - 1), "the last group: all its real points"
+            for first, bn, _ in FW.launches(count, case.batch)[1:]:
+                assert {first - 1, first}.issubset(rows.tolist())
+            if count == case.count and name != "E":
+                late = case.late_points(grid)
+                assert late[rows].sum() >= len(rows) // 2, name
+            s = F.system(min(case.n, 2049)) if case.n > 20000 else F.system(case.n)      # the largest case: the slots alone matter here
+            slots = FW.special_slots(case.n, case.chunks)
+            assert {0, 511, case.n - 1} <= set(slots.tolist()) and len(slots) <= min(case.counts[-1], 64)
+            for lo, hi in FW.cut(case.n, case.chunks):
+                tiles = set((slots // 512).tolist())
+                assert min(lo + 1, hi - 1) in tiles and hi - 1 in tiles
+            if case.n <= 20000:
+                p, v, skip = FW.mixed_points(s, count, case.chunks, 100)
+                assert p.shape == v.shape == (3, count) and skip.shape == (count,) and p.dtype == v.dtype == np.float32 and skip.dtype == np.int32
+                assert set(slots.tolist()) <= set(skip.tolist()) and (skip == -1).any() and skip.min() == -1 and skip.max() == case.n - 1
+                assert set(FW.special_rows(count, len(slots)).tolist()) <= set(rows.tolist())
+                own = skip >= 0
+                on_body = own & (p[0] == s["qx"][np.maximum(skip, 0)])
+                far = np.abs(p).max(0) > 100
+                assert on_body.sum() > count // 8 and far.sum() > count // 8 and (own & ~on_body).sum() > count // 16
+                assert not v[:, far].any() and np.isfinite(FW.doubled(p)).all()
+
+
+@pytest.mark.parametrize("name", CASE_NAMES)
+def test_wrap_stale_rows_have_power(name):
+    """What a unit left out leaves in its rows is the call before: the same count at the doubled points.  The fp64 field there,
+    in the place of the measured call's, misses field_ref's bound on EVERY row of the subset by three orders of magnitude: the
+    largest of a row's three scaled errors, each over its own bound C * 2^-24, is 1 000 or more."""
+    grid = FW.GRID
+    case = FW.cases(grid)[name]
+    s = F.system(case.n)
+    p, v, skip = FW.mixed_points(s, case.count, case.chunks, 100)
+    rows = FW.subset(case, grid)
+    ref, c = FW.reference(case, s, p, v, skip, rows)
+    power = FW.stale_power(case, s, p, v, skip, rows, ref, c)
+    print(f"case {name}: {len(rows)} rows, C = " + ", ".join(f"{k} {c[k]:.1f}" for k in c) + f"; stale rows miss by {power.min():.3g} x the bound or more")
+    assert all(0.0 < c[k] < 200.0 for k in c)
+    assert (power >= 1000.0).all()
