@@ -31,16 +31,17 @@ def lattice(n, seed=1):
     return s, soft, r
 
 
-def _exact_gap2(qi, radii, soft2, lo, hi):
-    """gap2 (n, hi - lo) fp32 of every body against bodies [lo, hi) of a lattice; asserts that every fp32 step is exact."""
-    d = qi[:, None, lo:hi] - qi[:, :, None]
+def _exact_gap2(qi, radii, soft2, lo, hi, rows=slice(None)):
+    """gap2 (n, hi - lo) fp32 of every body (of the bodies `rows`) against bodies [lo, hi) of a lattice; asserts that every
+    fp32 step is exact."""
+    d = qi[:, None, lo:hi] - qi[:, rows, None]
     d2 = (d * d).sum(0).astype(np.float64)
     r2 = (d2 + float(soft2)).astype(np.float32)
     assert np.array_equal(r2.astype(np.float64), d2 + float(soft2)), "r2 is not exact in fp32"
     e = r2 - np.float32(soft2)
     assert np.array_equal(e.astype(np.float64), d2), "e is not exact in fp32"
-    s = radii[:, None] + radii[None, lo:hi]                       # fp32 add
-    s64 = radii.astype(np.float64)[:, None] + radii.astype(np.float64)[None, lo:hi]
+    s = radii[rows, None] + radii[None, lo:hi]                    # fp32 add
+    s64 = radii.astype(np.float64)[rows, None] + radii.astype(np.float64)[None, lo:hi]
     assert np.array_equal(s.astype(np.float64), s64), "s is not exact in fp32"
     g64 = d2 - s64 * s64                                          # the fused multiply-add rounds this once
     g = g64.astype(np.float32)
@@ -60,6 +61,29 @@ def contact(q, radii, soft2, n=None):
     g[np.arange(n), np.arange(n)] = np.inf
     idx = g.argmin(1).astype(np.int32)      # argmin returns the first (lowest) index of the minimum
     return idx, g[np.arange(n), idx]
+
+
+def gap2_rows(q_int, radii, soft2, lo, hi):
+    """Rows [lo, hi) of gap2_matrix: fp32 gap2 (hi - lo, n), +inf at every body's own index."""
+    qi = np.asarray(q_int, np.int64)
+    n = qi.shape[1]
+    g = _exact_gap2(qi, np.asarray(radii, np.float32)[:n], soft2, 0, n, rows=slice(lo, hi))
+    g[np.arange(hi - lo), np.arange(lo, hi)] = np.inf
+    return g
+
+
+def contact_blocked(q_int, radii, soft2, block=N.ROW_BLOCK):
+    """contact() without the (3, n, n) tensor: the same arithmetic in blocks of `block` rows.  Returns (index int32, gap2
+    float32), the lowest index among equal gap2; a lone body has -1 and +inf."""
+    n = np.asarray(q_int).shape[1]
+    if n == 1:
+        return np.array([-1], np.int32), np.array([np.inf], np.float32)
+    idx, best = np.empty(n, np.int32), np.empty(n, np.float32)
+    for lo in range(0, n, block):
+        g = gap2_rows(q_int, radii, soft2, lo, min(lo + block, n))
+        k = g.argmin(1)      # argmin returns the first (lowest) index of the minimum
+        idx[lo:lo + block], best[lo:lo + block] = k, g[np.arange(len(k)), k]
+    return idx, best
 
 
 def chunked(q, radii, soft2, n, tiles, chunks):

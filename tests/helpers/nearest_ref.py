@@ -177,6 +177,63 @@ def r2_matrix(q_int, soft2):
     return r2
 
 
+ROW_BLOCK = 512      # rows of one block of the row-blocked forms: a block's int64 arrays stay at some 50 MB at n = 12 289
+
+
+def r2_rows(q_int, soft2, lo, hi):
+    """Rows [lo, hi) of r2_matrix: fp32 r2 (hi - lo, n), +inf at every body's own index; the same arithmetic, the same assert."""
+    qi = np.asarray(q_int, np.int64)
+    d2 = np.zeros((hi - lo, qi.shape[1]), np.int64)
+    for c in qi:
+        d = c[None, :] - c[lo:hi, None]
+        d2 += d * d
+    want = d2.astype(np.float64) + float(soft2)
+    r2 = want.astype(np.float32)
+    assert np.array_equal(r2.astype(np.float64), want), "r2 is not exact in fp32"
+    r2[np.arange(hi - lo), np.arange(lo, hi)] = np.inf
+    return r2
+
+
+def nearest_blocked(q_int, soft2, block=ROW_BLOCK):
+    """nearest(exact=True) without the (3, n, n) tensor: r2_matrix's arithmetic in blocks of `block` rows.  Returns
+    (index int32, r2 float32), the lowest index among equal r2; a lone body has -1 and +inf."""
+    n = np.asarray(q_int).shape[1]
+    if n == 1:
+        return np.array([-1], np.int32), np.array([np.inf], np.float32)
+    idx, best = np.empty(n, np.int32), np.empty(n, np.float32)
+    for lo in range(0, n, block):
+        r2 = r2_rows(q_int, soft2, lo, min(lo + block, n))
+        k = r2.argmin(1)      # argmin returns the first (lowest) index of the minimum
+        idx[lo:lo + block], best[lo:lo + block] = k, r2[np.arange(len(k)), k]
+    return idx, best
+
+
+def tie_stats_blocked(q_int, soft2, rows_of, block=ROW_BLOCK):
+    """tie_stats, highest_index_wins and later_tile_wins of a lattice without its (n, n) matrix.  rows_of(lo, hi) gives the rows
+    [lo, hi) of the candidate values (r2_rows, contact_ref.gap2_rows).  Returns a dict of per-row arrays: idx (the rule's
+    winner), val, cnt, span, own, high, later."""
+    n = np.asarray(q_int).shape[1]
+    tiles = -(-n // TILE)
+    out = {k: [] for k in ("idx", "val", "cnt", "span", "own", "high", "later")}
+    for lo in range(0, n, block):
+        hi = min(lo + block, n)
+        values = rows_of(lo, hi)
+        rows = np.arange(hi - lo)
+        best = values.min(1)
+        tie = np.zeros((hi - lo, tiles * TILE), bool)
+        tie[:, :n] = values == best[:, None]
+        by_tile = tie.reshape(hi - lo, tiles, TILE)
+        per_tile = by_tile.any(2)
+        span = per_tile.sum(1)
+        last_tile = tiles - 1 - per_tile[:, ::-1].argmax(1)      # the last tile that holds a candidate at the minimum ...
+        later = last_tile * TILE + by_tile[rows, last_tile].argmax(1)      # ... and its first one: later_tile_wins
+        for k, x in (("idx", tie.argmax(1)), ("val", best), ("cnt", tie.sum(1)), ("span", span),
+                     ("own", per_tile[rows, np.arange(lo, hi) // TILE] & (span >= 2)),
+                     ("high", tiles * TILE - 1 - tie[:, ::-1].argmax(1)), ("later", later)):
+            out[k].append(x)
+    return {k: np.concatenate(v) for k, v in out.items()}
+
+
 def tie_stats(values):
     """Of an (n, n) matrix of candidate values (+inf on the diagonal), per row: the number of candidates at the row's minimum,
     the number of layout tiles they lie in, and whether one lies in the row's own tile and another outside it."""

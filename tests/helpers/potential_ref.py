@@ -68,18 +68,18 @@ OWN_MASS, OWN_SEP, OWN_SOFT = 1e30, 1e10, np.float32(1e6)   # the own term G m /
 OWN_SLOTS = (5, 513)
 
 
-def own_term_pair(n):
-    """(state, soft, the two massive bodies): n = 2, or n = 514 with the two at slots 5 and 513 (two layout tiles) and every
-    other body massless and at least 1e13 m away from them and from each other."""
+def own_term_pair(n, slots=OWN_SLOTS):
+    """(state, soft, the two massive bodies): n = 2, or n >= 514 with the two at `slots` (5 and 513 by default: two layout
+    tiles) and every other body massless and at least 1e13 m away from them and from each other."""
     if n == 2:
         return state([[0.0, OWN_SEP], [0.0, 0.0], [0.0, 0.0]], [OWN_MASS, OWN_MASS]), OWN_SOFT, (0, 1)
     k = np.arange(n, dtype=np.float64)
     q = np.stack([1e13 + 1e13 * k, -2e13 - 1e13 * (k % 7), 3e13 + 5e12 * (k % 11)])
     m = np.zeros(n)
-    a, b = OWN_SLOTS
+    a, b = slots
     q[:, a], q[:, b] = (0.0, 0.0, 0.0), (OWN_SEP, 0.0, 0.0)
     m[a] = m[b] = OWN_MASS
-    return state(q, m), OWN_SOFT, OWN_SLOTS
+    return state(q, m), OWN_SOFT, (a, b)
 
 
 # ---- coincident bodies -------------------------------------------------------------------------------------------------------
@@ -102,12 +102,23 @@ SPARSE_N, SPARSE_SOFT = 2049, np.float32(0.01)
 SPARSE_SOURCES = (0, 5, 100, 511, 512, 700, 777, 1023, 1024, 1300, 1535, 1536, 1801, 2000, 2047, 2048)   # every tile's ends
 
 
-def sparse(n=SPARSE_N, seed=11, velocities=False):
-    """(state, soft, sources): n bodies in a unit cube, mass (1 ... 2) x 1e10 kg on the 16 sources alone — G m / r of order 1."""
+def tile_sources(n, count):
+    """About `count` source slots over ALL layout tiles that hold bodies: every such tile's first and last real slot, the rest
+    an even spread over the bodies."""
+    tiles = -(-n // TILE)
+    ends = {t * TILE for t in range(tiles)} | {min(t * TILE + TILE - 1, n - 1) for t in range(tiles)}
+    assert count >= len(ends), "fewer sources than tile ends"
+    spread = {int(x) for x in np.linspace(3, n - 3, count - len(ends)).astype(np.int64)}
+    return tuple(sorted(ends | spread))
+
+
+def sparse(n=SPARSE_N, seed=11, velocities=False, sources=0):
+    """(state, soft, sources): n bodies in a unit cube, mass (1 ... 2) x 1e10 kg on the sources alone — G m / r of order 1.
+    sources = 0: the 16 SPARSE_SOURCES below n; a count: tile_sources(n, count)."""
     rng = np.random.default_rng(seed)
     q = rng.uniform(0.0, 1.0, (3, n))
     m = np.zeros(n)
-    src = np.array([x for x in SPARSE_SOURCES if x < n], np.int64)
+    src = np.array([x for x in (tile_sources(n, sources) if sources else SPARSE_SOURCES) if x < n], np.int64)
     m[src] = 1e10 * rng.uniform(1.0, 2.0, len(src))
     v = 1e-3 * rng.standard_normal((3, n)) if velocities else None
     return state(q, m, v), SPARSE_SOFT, src
@@ -136,6 +147,60 @@ def dense(n=DENSE_N, seed=23):
 def dense_probes(count=64, tile=0):
     """`count` bodies of one tile, spread over its lanes and lane steps."""
     return tile * TILE + np.unique(np.linspace(0, TILE - 1, count).astype(np.int64))
+
+
+def sweep_terms_f32(s, soft, rows, tiles):
+    """float32 terms G m_j * inv_ij of the bodies `rows` against all slots of `tiles` layout tiles, shaped (rows, tiles, 4 lane
+    steps, 64 lanes, 2 halves): slot = 512 tile + 128 step + 2 lane + half.  Every operation rounds once to float32 (the
+    differences, r2 as one fused chain, 1 / sqrt, the product); the own slot and the padding hold +0."""
+    f = np.float32
+    n = len(s["m"])
+    rows = np.asarray(rows, np.int64)
+    q = np.zeros((3, tiles * TILE), f)
+    q[:, :n] = np.stack([np.asarray(s[k], f) for k in Q])
+    gm = np.zeros(tiles * TILE, f)
+    gm[:n] = np.asarray(H._gm(s), f)
+    soft2 = float(f(soft) * f(soft))
+    out = np.empty((len(rows), tiles * TILE), f)
+    for lo in range(0, len(rows), 64):
+        r = rows[lo:lo + 64]
+        d = (q[:, None, :] - q[:, r, None]).astype(np.float64)      # fp32 differences, held in fp64: their squares are exact
+        r2 = (d[0] * d[0] + soft2).astype(f).astype(np.float64)      # one rounding per fused multiply-add
+        r2 = (d[1] * d[1] + r2).astype(f).astype(np.float64)
+        r2 = (d[2] * d[2] + r2).astype(f).astype(np.float64)
+        out[lo:lo + 64] = gm[None, :] * (1.0 / np.sqrt(r2)).astype(f)
+        out[np.arange(lo, lo + len(r)), r] = 0.0
+    return out.reshape(len(rows), tiles, TILE // 128, 64, 2)
+
+
+def sweep_phi_f32(terms, rows, chunks):
+    """numpy float32 emulation of the FULL potential sweep's summation order on sweep_terms_f32's terms: per chunk
+    [tiles c / chunks, tiles (c + 1) / chunks) 128 lane-half accumulators receive the chunk's tiles in layout order, lane steps
+    rising, the body's own tile after the others (it is added behind the loop), then the two halves and the lanes are folded;
+    the chunks' totals are added in index order.  The fold's pairing is a butterfly; the device's differs in order, not in
+    depth."""
+    f = np.float32
+    rows = np.asarray(rows, np.int64)
+    count, tiles = terms.shape[:2]
+    own, lanes = rows // TILE, np.arange(64)
+    phi = np.zeros(count, f)
+    for c in range(chunks):
+        t0, t1 = tiles * c // chunks, tiles * (c + 1) // chunks
+        acc = np.zeros((count, 64, 2), f)
+        for t in range(t0, t1):
+            other = (own != t)[:, None, None]
+            for step in range(terms.shape[2]):
+                acc = acc + np.where(other, terms[:, t, step], f(0.0))      # + 0 changes no bit of a sum of positive terms
+        inside = ((own >= t0) & (own < t1))[:, None, None]
+        mine = terms[np.arange(count), own]
+        for step in range(terms.shape[2]):
+            acc = acc + np.where(inside, mine[:, step], f(0.0))
+        fold = acc[:, :, 0] + acc[:, :, 1]
+        for sft in (1, 2, 4, 8, 16, 32):
+            fold = fold + fold[:, lanes ^ sft]
+        phi = phi + fold[:, 0]
+    assert phi.dtype == f
+    return phi
 
 
 def lane_sums_f32(s, soft, body, order):
