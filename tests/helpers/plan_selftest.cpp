@@ -5,12 +5,17 @@
 // The plan choice (csrc/murb_choose.h: make_plan and its rules) runs in the same binary: the fused one-launch step, the small-plan
 // table, the multi-rank thresholds and the forced options give the plans the comments there promise, and every pair-symmetric
 // choice is chained through sym_layout_key into the same layout checks.
+// The sweep has two parts: seven sizes from 1 to 60 001 bodies on 1-8 ranks, and 26 residues of a ragged last block (1 ... 1023
+// real bodies, both sides of every length it can be cut to) at 1 + rem and 3 + rem blocks on one rank and two blocks a slice on
+// 2-4 ranks (check_ragged_residues: 87 048 layouts).  About 93 000 layouts in all; under the sanitizers the run takes about
+// 30 s on one core, 14 s before the residues came (all 1024 residues would take a quarter of an hour and more: do not).
 //   plan_selftest        prints "ok <plans checked>" and exits 0
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <set>
 #include <vector>
 
@@ -127,12 +132,14 @@ static int chain_to_layout(const PlanInputs& in, const Plan& p)
 #define EXPECT(cond, ...) do { if (!(cond)) { std::fprintf(stderr, "choice, n=%lu W=%d cu=%d variant=%d jsplit=%d sym_waves=%d -> variant %d parts %d+%d split %d waves %d taper %d tri %d: ", \
     in.n, in.world, in.cu_count, in.variant, in.jsplit, in.sym_waves, p.variant, p.parts_local, p.parts_remote, p.split, p.waves, p.taper, (int)p.diag_tri); FAIL(__VA_ARGS__); } } while (0)
 
-// (a), (b): one rank, T = 1 ... 30 blocks, full and 37 bodies short of full
+// (a), (b): one rank, T = 1 ... 30 blocks: full, 37 bodies short of full, 65 bodies and one body in the last block
 static int check_block_sweep(int cu_count)
 {
     std::set<int> variants, waves, splits, tapers;
-    for (int T = 1; T <= 30; ++T)
-        for (unsigned long n : {1024ul * T, 1024ul * T - 37}) {
+    for (int T = 1; T <= 30; ++T) {
+        std::vector<unsigned long> sizes = {1024ul * T, 1024ul * T - 37};
+        if (T >= 2) { sizes.push_back(1024ul * (T - 1) + 65); sizes.push_back(1024ul * (T - 1) + 1); }   // a truly cut item; a one-body block
+        for (unsigned long n : sizes) {
             const PlanInputs in = inputs(n, 1, cu_count);
             const Plan p = make_plan(in);
             variants.insert(p.variant);
@@ -147,6 +154,7 @@ static int check_block_sweep(int cu_count)
                 EXPECT(p.waves == 8 && p.split == (T < 10 ? 8 : 4) && p.taper == 30 && p.diag_tri, "expected the 8-wave plan");
             if (chain_to_layout(in, p)) return 1;
         }
+    }
     if (cu_count != 256) return 0;
     // what tests/test_pair_coverage.py::test_block_count_sweep_reached_every_plan asserts on the GPU
     const bool reached = variants.count(1) && variants.count(8) && waves.count(4) && waves.count(8) && splits.count(4) && splits.count(8) &&
@@ -258,32 +266,55 @@ static int check_sym_wide()
     return 0;
 }
 
+// The layouts of n bodies on W ranks under every key of the sweep: splits x waves x tapers x (plain | triangular diagonals | XCD
+// order | several passes | the exchange pipeline | its triangle launches cut in 4)
+static int sweep_keys(unsigned long n, int W, std::initializer_list<int> tapers)
+{
+    for (int split : {1, 4, 8, 16})
+        for (int waves : {4, 8}) {
+            if (MURB_SYM_BLOCK / split < 16 * waves || (split == 8 && waves == 4)) continue;   // 8 x 4 lies between 4 x 4 and 16 x 4
+            for (int taper : tapers)
+                for (int variant = 0; variant < 6; ++variant) {
+                    SymLayoutKey key;
+                    key.split = split; key.waves = waves; key.taper = taper;
+                    key.diag_tri = variant & 1;
+                    key.exchange_mode = W > 1 || variant >= 4;
+                    key.overlap = 1; key.tri_first_pct = 50;
+                    key.xcd_order = variant == 2;
+                    key.tri_div = (key.exchange_mode && variant == 5) ? 4 : 1;
+                    key.budget_floats = (!key.exchange_mode && variant == 3) ? (size_t)40 * MURB_SYM_BLOCK : 0;
+                    for (int r = 0; r < W; r += (W > 4 ? 3 : 1)) {
+                        if (check_layout(n, W, r, key)) return 1;
+                        ++g_plans;
+                    }
+                }
+        }
+    return 0;
+}
+
+// `rem` real bodies in a slice's last block, on both sides of every length the work list can cut that block to (the list of
+// tests/helpers/ragged.py): one rank with 1 and 3 full blocks before it; 2, 3 and 4 ranks of two blocks a slice whose last
+// blocks hold rem and rem - 1 bodies in every mix (rem = 1: a wholly empty block, which counts as holding one body)
+static int check_ragged_residues()
+{
+    const int rems[] = {1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 193, 255, 257, 383, 385, 511, 513, 767, 769, 895, 897, 959, 961, 1023};
+    for (int rem : rems) {
+        for (int B : {1, 3})
+            if (sweep_keys(1024ul * B + rem, 1, {0, 30, 100})) return 1;
+        for (int W : {2, 3, 4})
+            for (int k = 0; k < W; ++k)
+                if (sweep_keys((unsigned long)W * (1024 + rem) - k, W, {0, 30, 100})) return 1;
+    }
+    return 0;
+}
+
 int main()
 {
     const unsigned long sizes[] = {1, 250, 1025, 2049, 9001, 30000, 60001};
     for (unsigned long n : sizes)
-        for (int W : {1, 2, 3, 4, 8}) {
-            if ((unsigned long)W > n) continue;
-            for (int split : {1, 4, 16})
-                for (int waves : {4, 8}) {
-                    if (MURB_SYM_BLOCK / split < 16 * waves) continue;
-                    for (int taper : {0, 40})
-                        for (int variant = 0; variant < 6; ++variant) {
-                            SymLayoutKey key;
-                            key.split = split; key.waves = waves; key.taper = taper;
-                            key.diag_tri = variant & 1;
-                            key.exchange_mode = W > 1 || variant >= 4;
-                            key.overlap = 1; key.tri_first_pct = 50;
-                            key.xcd_order = variant == 2;
-                            key.tri_div = (key.exchange_mode && variant == 5) ? 4 : 1;
-                            key.budget_floats = (!key.exchange_mode && variant == 3) ? (size_t)40 * MURB_SYM_BLOCK : 0;
-                            for (int r = 0; r < W; r += (W > 4 ? 3 : 1)) {
-                                if (check_layout(n, W, r, key)) return 1;
-                                ++g_plans;
-                            }
-                        }
-                }
-        }
+        for (int W : {1, 2, 3, 4, 8})
+            if ((unsigned long)W <= n && sweep_keys(n, W, {0, 40})) return 1;
+    if (check_ragged_residues()) return 1;
     for (int cu_count : {256, 304, 128})
         if (check_block_sweep(cu_count)) return 1;
     if (check_forced_options()) return 1;

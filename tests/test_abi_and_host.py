@@ -5,11 +5,15 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+from ragged import REMS   # noqa: E402
 
 
 def bits(a):
@@ -189,46 +193,82 @@ def test_half_ring_schedule_covers_every_pair_once(mh, n, world, split):
         assert max(counts) - min(counts) <= 1024 * tb, counts      # balanced up to one block row (walked bodies)
 
 
-@pytest.mark.parametrize("diag_tri", [False, True])
-@pytest.mark.parametrize("n,world,split,waves,taper,exchange,tri_div", [p_ if len(p_) == 7 else p_ + (1,) for p_ in [
-    (5000, 1, 1, 4, 0, False), (5000, 1, 4, 4, 0, False), (9000, 1, 8, 8, 0, False), (9000, 1, 2, 4, 50, False),
-    (9000, 1, 8, 8, 40, False), (9000, 1, 16, 4, 100, False), (3000, 1, 1, 4, 0, True),      # one rank with the exchange pipeline (RCCL self-test)
-    (9000, 2, 1, 4, 0, True), (9001, 3, 2, 4, 30, True), (20000, 4, 4, 4, 0, True), (20000, 4, 2, 8, 60, True),
-    (30000, 5, 1, 4, 0, True), (60000, 8, 4, 4, 25, True), (30000, 1, 4, 8, 30, False), (2049, 2, 2, 4, 0, True),
-    (60000, 8, 4, 4, 0, True, 2), (100000, 8, 4, 4, 0, True, 4), (40000, 4, 2, 8, 20, True, 2),     # the triangle's launches cut finer ("tri_div")
-]])
-def test_pair_symmetric_layout_is_complete_and_collision_free(mh, n, world, split, waves, taper, exchange, diag_tri, tri_div):
-    """What the pair-symmetric kernel is handed (murbhip_schedule_layout, host only), for every rank of a run:
-      * every ordered (i, j) interaction between REAL bodies is applied exactly once over all items of all ranks (at the
-        granularity of 16 slots), with any item size mix the taper produces; nothing is applied twice;
-      * every cell of every partial row has at most one writer, and exactly one where the slot holds a real body;
-      * pushing "how many REAL bodies did this cell's writer sum over" through the row tables, the reduce-scatter chunk
-        layout and the own-triangle addend gives every real slot exactly n interactions — i.e. the data flow of a step,
-        launch by launch, loses and duplicates nothing;
-      * padding is walked only up to the next multiple of 16 x waves bodies behind a block's last real body."""
-    slice_ = mh.slice_slots(n, world)
-    slots, tb = slice_ * world, slice_ // 1024
-    G = 16
+LAYOUT_G = 16   # slots per cell of the interaction matrix that the layout checker counts in
+
+
+def real_slots(mh, n, world):
+    """(fill, real): the real bodies of every global block, and which slots hold one."""
     fill = real_bodies_per_block(mh, n, world)
-    real = np.zeros(slots, bool)
+    real = np.zeros(mh.slice_slots(n, world) * world, bool)
     for b, f in enumerate(fill):
         real[b * 1024:b * 1024 + f] = True
     assert real.sum() == n
-    nreal = lambda lo, hi: int(real[lo:hi].sum())   # noqa: E731
-    count = np.zeros((slots // G, slots // G), np.int32)
+    return fill, real
+
+
+def layout_cell_counts(real, layouts):
+    """(count, real_cells) of the work lists `layouts` (one (items, rows, floats_main, floats_tri) per rank): how often every
+    ordered (i cell, j cell) interaction is applied over all items of all ranks, in cells of LAYOUT_G slots, and which cells
+    hold a real body (`real`: per slot).  An item counts for the slots it walks, [i0, i0 + len): a piece cut short of a block's last real body
+    leaves that body's cell at 0."""
+    G = LAYOUT_G
+    count = np.zeros((len(real) // G, len(real) // G), np.int32)
+    for items, _, _, _ in layouts:
+        for i0, ln, J, flags, _, _, _, _ in items.tolist():
+            diag, tri = i0 // 1024 == J, bool(flags & 2)
+            p_first, p_sym = ((flags >> 8) & 15, (flags >> 12) & 15) if tri else (0, 8 if diag else 0)
+            j0 = J * 1024
+            count[i0 // G:(i0 + ln) // G, (j0 + 128 * p_first) // G:(j0 + 1024) // G] += 1
+            if not (flags & 1):
+                count[(j0 + 128 * p_sym) // G:(j0 + 1024) // G, i0 // G:(i0 + ln) // G] += 1
+    return count, real.reshape(-1, G).any(1)
+
+
+def uncovered_cells(count, real_cells):
+    """The ordered (i cell, j cell) pairs of real bodies that no item applies, as an array of rows."""
+    ids = np.flatnonzero(real_cells)
+    a, b = np.nonzero(count[np.ix_(ids, ids)] == 0)
+    return np.stack([ids[a], ids[b]], 1)
+
+
+def check_pair_symmetric_layout(mh, n, world, split, waves, taper, exchange, diag_tri, tri_div, layouts=None):
+    """The checker of test_pair_symmetric_layout_is_complete_and_collision_free (its docstring says what is checked), on the
+    product's work lists or on `layouts` (one per rank) in their place."""
+    if layouts is None:
+        layouts = [mh.schedule_layout(n, world, r, split, waves, taper, 50, exchange, diag_tri, tri_div) for r in range(world)]
+    # the interaction matrix first: what it misses is reported cell by cell
+    fill, real = real_slots(mh, n, world)
+    count, real_cells = layout_cell_counts(real, layouts)
+    assert (count <= 1).all(), ("an interaction is applied twice", np.unique(count))
+    missing = uncovered_cells(count, real_cells)
+    assert len(missing) == 0, (f"{len(missing)} (i cell, j cell) interactions of {LAYOUT_G} x {LAYOUT_G} slots between real bodies are "
+                               f"never applied: i cells {np.unique(missing[:, 0]).tolist()[:40]}, the first ones {missing[:8].tolist()}")
+    slice_ = mh.slice_slots(n, world)
+    tb = slice_ // 1024
+    upto = np.concatenate([[0], np.cumsum(real)])
+    nreal = lambda lo, hi: int(upto[hi] - upto[lo])   # noqa: E731
     recv = np.zeros((world, slice_), np.int64)     # what the reduce-scatter delivers: sum over ranks of their chunk for a slice
     own = np.zeros((world, slice_), np.int64)      # own-triangle row sums (exchange pipeline) / everything (one GPU)
     for r in range(world):
-        items, rows, fm, ft = mh.schedule_layout(n, world, r, split, waves, taper, 50, exchange, diag_tri, tri_div)
+        items, rows, fm, ft = layouts[r]
         assert len(items) > 0
         if tri_div > 1:   # the own-slice triangle's items (row set 1) are finer than the rectangles' whole sub-blocks
-            assert items[items[:, 4] == 1][:, 1].max() <= max(1024 // split // tri_div, 16 * waves) and items[items[:, 4] == 0][:, 1].max() == 1024 // split
+            assert items[items[:, 4] == 1][:, 1].max() <= max(1024 // split // tri_div, 16 * waves)
+            # a rectangle's whole sub-block: 1024 / split bodies, or its real ones up to the next multiple of 16 x waves (a rank's
+            # rectangles may all walk ragged blocks).  Without a taper every rectangle is whole; with one the launch's first is
+            rect, sub = items[items[:, 4] == 0], 1024 // split
+            whole = np.array([min(sub, -(-(max(fill[i0 // 1024], 1) - i0 % 1024 // sub * sub) // (16 * waves)) * 16 * waves) for i0 in rect[:, 0]])
+            assert (rect[:, 1] <= whole).all() and (taper > 0 or (rect[:, 1] == whole).all())
+            if taper < 100:
+                assert rect[0, 1] == whole[0]
+                if fill[rect[0, 0] // 1024] == 1024:    # the first rectangle walks a full block: a whole sub-block of it
+                    assert rect[:, 1].max() == sub
         sets = {0: np.zeros(fm, np.int32), 1: np.zeros(ft, np.int32)}      # writers per cell
         vals = {0: np.zeros(fm, np.int64), 1: np.zeros(ft, np.int64)}      # real bodies summed into the cell
         needs = {0: np.zeros(fm, bool), 1: np.zeros(ft, bool)}             # cells that belong to a real slot
         launches = items[:, 7]
         assert (np.diff(launches) >= 0).all()                              # launch order
-        for i0, ln, J, flags, st, ioff, joff, launch in items:
+        for i0, ln, J, flags, st, ioff, joff, launch in items.tolist():
             assert ln % (4 * waves) == 0 and ln >= 16 * waves and i0 % (4 * waves) == 0 and i0 // 1024 == (i0 + ln - 1) // 1024
             bi = i0 // 1024
             assert i0 % 1024 < max(fill[bi], 1), "an item that walks nothing but padding"
@@ -243,26 +283,24 @@ def test_pair_symmetric_layout_is_complete_and_collision_free(mh, n, world, spli
                     assert bi // tb == r and J // tb == r                    # the triangle needs no remote data
                 else:
                     assert (bi // tb == r) != (J // tb == r)                 # a rectangle: one own block, one of another slice
-            assert fill[bi] <= fill[J]                                       # the emptier block is the walked one
+            assert max(fill[bi], 1) <= max(fill[J], 1)                       # the emptier block is the walked one (an empty one counts as 1)
             # which j steps (of 128 bodies) the item evaluates, and from which one on it applies both sides
             p_first, p_sym = ((flags >> 8) & 15, (flags >> 12) & 15) if tri else (0, 8 if diag else 0)
             if tri:
                 assert ln <= 128 and p_first == (i0 % 1024) // 128 and p_sym == p_first + 1
             assert j_side == (p_sym < 8) or (tri and not j_side)             # the last REAL triangular piece may have later (padding) steps
             j0 = J * 1024
-            count[i0 // G:(i0 + ln) // G, (j0 + 128 * p_first) // G:(j0 + 1024) // G] += 1
             sets[st][ioff:ioff + ln] += 1
             needs[st][ioff:ioff + ln] |= real[i0:i0 + ln]
             vals[st][ioff:ioff + ln] += nreal(j0 + 128 * p_first, j0 + 1024)
             if j_side:
-                count[(j0 + 128 * p_sym) // G:(j0 + 1024) // G, i0 // G:(i0 + ln) // G] += 1
                 sets[st][joff:joff + 1024] += 1
                 needs[st][joff:joff + 1024] |= real[j0:j0 + 1024]
                 vals[st][joff + 128 * p_sym:joff + 1024] += nreal(i0, i0 + ln)
         for st in (0, 1):
             assert (sets[st] <= 1).all(), (r, st, np.unique(sets[st]))       # never two writers
         seen = {0: np.zeros(fm, bool), 1: np.zeros(ft, bool)}
-        for st, out_slice, out_block, base_i, ni, base_j, nj in rows:
+        for st, out_slice, out_block, base_i, ni, base_j, nj in rows.tolist():
             assert not seen[st][base_j:base_j + nj * 1024].any() and not seen[st][base_i:base_i + ni * 1024].any()
             seen[st][base_j:base_j + nj * 1024] = True
             seen[st][base_i:base_i + ni * 1024] = True
@@ -283,10 +321,90 @@ def test_pair_symmetric_layout_is_complete_and_collision_free(mh, n, world, spli
                 own[0, out_block * 1024:(out_block + 1) * 1024] += tot
         for st in (0, 1):
             assert seen[st].all()                                          # the tables account for every row
-    assert (count <= 1).all(), np.unique(count)
-    real_cells = real.reshape(-1, G).any(1)
-    assert (count[np.ix_(real_cells, real_cells)] == 1).all()
     assert ((own + recv).reshape(-1)[real] == n).all()
+
+
+@pytest.mark.parametrize("diag_tri", [False, True])
+@pytest.mark.parametrize("n,world,split,waves,taper,exchange,tri_div", [p_ if len(p_) == 7 else p_ + (1,) for p_ in [
+    (5000, 1, 1, 4, 0, False), (5000, 1, 4, 4, 0, False), (9000, 1, 8, 8, 0, False), (9000, 1, 2, 4, 50, False),
+    (9000, 1, 8, 8, 40, False), (9000, 1, 16, 4, 100, False), (3000, 1, 1, 4, 0, True),      # one rank with the exchange pipeline (RCCL self-test)
+    (9000, 2, 1, 4, 0, True), (9001, 3, 2, 4, 30, True), (20000, 4, 4, 4, 0, True), (20000, 4, 2, 8, 60, True),
+    (30000, 5, 1, 4, 0, True), (60000, 8, 4, 4, 25, True), (30000, 1, 4, 8, 30, False), (2049, 2, 2, 4, 0, True),
+    (60000, 8, 4, 4, 0, True, 2), (100000, 8, 4, 4, 0, True, 4), (40000, 4, 2, 8, 20, True, 2),     # the triangle's launches cut finer ("tri_div")
+]])
+def test_pair_symmetric_layout_is_complete_and_collision_free(mh, n, world, split, waves, taper, exchange, diag_tri, tri_div):
+    """What the pair-symmetric kernel is handed (murbhip_schedule_layout, host only), for every rank of a run:
+      * every ordered (i, j) interaction between REAL bodies is applied exactly once over all items of all ranks (at the
+        granularity of 16 slots), with any item size mix the taper produces; nothing is applied twice;
+      * every cell of every partial row has at most one writer, and exactly one where the slot holds a real body;
+      * pushing "how many REAL bodies did this cell's writer sum over" through the row tables, the reduce-scatter chunk
+        layout and the own-triangle addend gives every real slot exactly n interactions — i.e. the data flow of a step,
+        launch by launch, loses and duplicates nothing;
+      * padding is walked only up to the next multiple of 16 x waves bodies behind a block's last real body."""
+    check_pair_symmetric_layout(mh, n, world, split, waves, taper, exchange, diag_tri, tri_div)
+
+
+RAGGED_KEYS = [(split, waves, taper, diag_tri) for split, waves in ((1, 4), (4, 4), (16, 4), (1, 8), (8, 8)) for taper in (0, 30, 100)
+               for diag_tri in (False, True)]
+
+
+def ragged_sizes(rem):
+    """(n, world) of the residue sweep: one rank with 1 and 3 full blocks before the ragged one; 2, 3 and 4 ranks of two
+    blocks a slice whose last blocks hold rem and rem - 1 bodies in every mix (rem = 1: a wholly empty block, counted as 1)."""
+    return [(1024 * B + rem, 1) for B in (1, 3)] + [(W * (1024 + rem) - k, W) for W in (2, 3, 4) for k in range(W)]
+
+
+@pytest.mark.parametrize("rem", REMS)
+def test_pair_symmetric_layout_over_ragged_residues(mh, rem):
+    """The same checker with `rem` real bodies in a slice's last block, on both sides of every length the work list can cut
+    that block to (helpers/ragged.py: REMS), for each size of ragged_sizes() under every key of RAGGED_KEYS; several ranks
+    (the exchange pipeline) also with the triangle's launches cut in 4."""
+    for n, world in ragged_sizes(rem):
+        fills = real_bodies_per_block(mh, n, world)[1::2] if world > 1 else [rem]
+        assert set(fills) <= {rem, rem - 1} and rem in fills, fills
+        for split, waves, taper, diag_tri in RAGGED_KEYS:
+            for tri_div in ((1, 4) if world > 1 else (1,)):
+                try:
+                    check_pair_symmetric_layout(mh, n, world, split, waves, taper, world > 1, diag_tri, tri_div)
+                except AssertionError as e:
+                    raise AssertionError(f"n={n} world={world} split={split} waves={waves} taper={taper} diag_tri={diag_tri} "
+                                         f"tri_div={tri_div}: {e}") from e
+
+
+@pytest.mark.parametrize("rem,B,split,waves,diag_tri", [(100, 1, 1, 4, False), (100, 1, 4, 4, True), (200, 3, 1, 8, False),
+                                                        (700, 1, 8, 8, True), (65, 1, 16, 4, False), (33, 1, 1, 4, True)])
+def test_layout_checker_reports_a_cut_rounded_down(mh, rem, B, split, waves, diag_tri):
+    """The checker's teeth at the last partial group.  The product cuts the piece that straddles a block's last real body to
+    the NEXT multiple of min_len = 16 x waves; restated here with the cut rounded DOWN (a piece left with nothing is dropped),
+    the bodies between the cut and the last real one are never walked, and the checker must name their cells:
+    every interaction of such a cell with the full block 0, both ways, and with itself."""
+    n, min_len = 1024 * B + rem, 16 * waves
+    assert rem % min_len != 0
+    items, rows, fm, ft = mh.schedule_layout(n, 1, 0, split, waves, 0, 50, False, diag_tri, 1)
+    real_end = 1024 * B + rem
+    cut, touched = [], 0
+    for it in items.tolist():
+        i0, ln = it[0], it[1]
+        if i0 < real_end < i0 + ln:                          # the straddling piece
+            touched += 1
+            it[1] = (real_end - i0) // min_len * min_len
+            if it[1] == 0:
+                continue
+        cut.append(it)
+    assert touched == B + 1                                  # the ragged block against every block, itself included
+    bad = [(np.array(cut, np.int64).reshape(-1, 8), rows, fm, ft)]
+    with pytest.raises(AssertionError, match="never applied"):
+        check_pair_symmetric_layout(mh, n, 1, split, waves, 0, False, diag_tri, 1, layouts=bad)
+    count, real_cells = layout_cell_counts(real_slots(mh, n, 1)[1], bad)
+    assert (count <= 1).all()
+    missing = {tuple(c) for c in uncovered_cells(count, real_cells).tolist()}
+    lost = set(range((1024 * B + rem // min_len * min_len) // LAYOUT_G, -(-real_end // LAYOUT_G)))   # cells behind the cut
+    assert lost and missing and all(a in lost or b in lost for a, b in missing)
+    block0 = range(1024 // LAYOUT_G)
+    assert all((g, h) in missing and (h, g) in missing for g in lost for h in block0)
+    assert all((g, g) in missing for g in lost)
+    # and the product's own list for the same size passes
+    check_pair_symmetric_layout(mh, n, 1, split, waves, 0, False, diag_tri, 1)
 
 
 @pytest.mark.parametrize("binary,members,rounds", [("crew_selftest", 8, 2000), ("crew_selftest", 1, 50), ("crew_selftest", 3, 2000),
@@ -395,15 +513,16 @@ def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
 
 def test_planner_selftest_under_sanitizers():
     """The host-side planner (csrc/murb_plan.h, murb_schedule.h: item tables and partial-row layouts, no HIP in them)
-    compiled with g++ under AddressSanitizer + UBSan and swept over a few thousand plans (sizes 1 … 60 001, 1-8 ranks, splits,
-    waves, tapers, triangular diagonals, the exchange pipeline, several passes, finer triangle launches): every index the
+    compiled with g++ under AddressSanitizer + UBSan and swept over some 90 000 plans (sizes 1 … 60 001, 1-8 ranks, splits,
+    waves, tapers, triangular diagonals, the exchange pipeline, several passes, finer triangle launches; the residues of a
+    ragged last block, helpers/ragged.py, on 1-4 ranks): every index the
     planner computes is in bounds, no partial-row cell has two writers, tables and passes account for every item.
     The same binary checks the plan choice (csrc/murb_choose.h) and chains its pair-symmetric choices into those layout checks."""
     exe = os.path.join(ROOT, "tests", "helpers", "_build", "plan_selftest")
     if not os.path.exists(exe):
         subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "helpers"), "_build/plan_selftest"], check=True, timeout=600)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stdout.startswith("ok ") and int(r.stdout.split()[1]) > 2000, (r.stdout, r.stderr[-3000:])
+    assert r.returncode == 0 and r.stdout.startswith("ok ") and int(r.stdout.split()[1]) > 90000, (r.stdout, r.stderr[-3000:])
 
 
 def test_layout_query_rejects_bad_arguments(mh):

@@ -113,11 +113,17 @@ def probe_potential(P, sim, what, tol):
 SWEEP_PLANS = {}   # n -> (variant, sym_waves, jsplit, taper) of the default plan
 
 
+def sweep_sizes(T):
+    """T blocks: full; 37 bodies short (no item is cut: 987 rounds up to 1024); and, from two blocks on, 65 bodies in the
+    last block (its items cut to 128 of 1024 slots) and one body (cut to one granule)."""
+    return (BLOCK * T, BLOCK * T - 37) + ((BLOCK * (T - 1) + 65, BLOCK * (T - 1) + 1) if T >= 2 else ())
+
+
 @pytest.mark.parametrize("T", range(1, 31))
 def test_block_count_sweep(gpu, O, T):
     """One GPU, the default plan at every block count T = 1 ... 30 (the small-plan table, the fused one-launch rule), full
     and with a ragged last block: compute_acc and the step route (the fused one-launch kernel for T <= 4 and T = 6)."""
-    for n in (BLOCK * T, BLOCK * T - 37):
+    for n in sweep_sizes(T):
         P = Problem(gpu, O, n)
         with gpu.Simulation(n, soft=SOFT) as sim:
             SWEEP_PLANS[n] = tuple(int(sim.info(k)) for k in ("variant", "sym_waves", "jsplit", "taper"))
@@ -130,7 +136,7 @@ def test_block_count_sweep_reached_every_plan(gpu, O):
     """The sweep above must keep reaching every plan of the table: if an edit of kSmallPlanOfBlocks or of the fused rule
     leaves one out, this says so."""
     for T in range(1, 31):
-        for n in (BLOCK * T, BLOCK * T - 37):
+        for n in sweep_sizes(T):
             if n not in SWEEP_PLANS:
                 with gpu.Simulation(n, soft=SOFT) as sim:
                     SWEEP_PLANS[n] = tuple(int(sim.info(k)) for k in ("variant", "sym_waves", "jsplit", "taper"))

@@ -1,8 +1,16 @@
 """CPU: the checker of the sparse-mass probes (tests/test_pair_coverage.py).  The sources oracle agrees with the full fp64
 direct sum, an honest fp32 sum passes the probe metric, and every kind of pair-coverage bug fails it: the GPU tests'
 tolerance is neither too tight nor blind."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+from ragged import ragged_offsets, ragged_sources   # noqa: E402
 
 SOFT = np.float32(2e8)
 TOL_F64_MAX = 2e-6     # tests/test_gpu_parity.py
@@ -122,3 +130,32 @@ def test_probe_sources_cover_every_block(O, mh, n, world):
     assert every >= set(firsts) | {f + c - 1 for f, c in zip(firsts, counts)} | {n - 3, n - 2, n - 1}
     for p, q in zip(probes, probes[1:]):
         assert not set(p.tolist()) & set(q.tolist())
+
+
+def test_ragged_offsets_straddle_every_cut():
+    """helpers/ragged.py: a ragged block's first body, both sides of every multiple of 64 below its `rem` bodies, rem - 2."""
+    assert ragged_offsets(130) == [0, 63, 64, 127, 128] and ragged_offsets(129) == [0, 63, 64, 127, 128]
+    assert ragged_offsets(128) == [0, 63, 64, 126] and ragged_offsets(65) == [0, 63, 64] and ragged_offsets(64) == [0, 62]
+    assert ragged_offsets(1) == [0] and ragged_offsets(2) == [0] and len(ragged_offsets(1023)) == 32
+    firsts, counts, slice_slots = [0, 1089, 2178], [1089, 1089, 1088], 2048      # n = 3 (1024 + 65) - 1
+    assert ragged_sources(firsts, counts, slice_slots).tolist() == [f + 1024 + o for f, c in zip(firsts, counts)
+                                                                    for o in ([0, 63, 64] if c == 1089 else [0, 62])]
+
+
+@pytest.mark.parametrize("rem", [2, 65, 513, 1023])
+def test_ragged_probes_keep_their_power(O, mh, rem):
+    """The probes of tests/test_ragged_block_gpu.py carry up to 33 more sources per ragged block: at its sizes with the most
+    of them the force probes still see one term on 99 % of the bodies and the potential probes one pair, 10x the tolerances."""
+    for n, world in [(rem, 1), (1024 + rem, 1), (3072 + rem, 1), (9 * 1024 + rem, 1)] + [(W * (1024 + rem) - k, W) for W in (2, 4) for k in (0, 1)]:
+        s = O.init_bodies(n, "galaxy")
+        firsts, counts, slice_slots = geometry(mh, n, world)
+        extra = ragged_sources(firsts, counts, slice_slots)
+        for src in O.probe_sources(n, firsts, counts, slice_slots, probes=4, k_max=128, per_block=8):
+            src = np.union1d(src, extra)
+            ps = O.probe_state(s, src)
+            _, abs_sum, min_term = O.accel_f64_sources(ps, src, SOFT)
+            assert (O.probe_power(abs_sum, min_term) >= 10 * TOL_F64_MAX).mean() >= 0.99, (n, world)
+        for src in O.probe_sources(n, firsts, counts, slice_slots, probes=2, k_max=64, per_block=8):
+            src = np.union1d(src, extra)
+            pe, min_pair = O.potential_f64_sources(O.probe_state(s, src), src, SOFT)
+            assert min_pair >= 10 * TOL_PE_FUSED * abs(pe), (n, world, min_pair / abs(pe))
