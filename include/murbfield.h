@@ -16,8 +16,9 @@
  * Call orders (murbhip.h, C1-C3).  murbfield_at and murbfield_of are observers: deleting them from a sequence of calls changes
  *   no bit of anything read afterwards, and each returns the bits it returns as the only observer at that point.  A refused call
  *   returns its code and changes nothing.  murbfield_set_option is an observer of everything murbhip.h declares: its keys are
- *   read by murbfield_at / murbfield_of alone.  tests/test_field_gpu.py checks this on runs of every integrator, and the
- *   values themselves against fp64 at the state those runs leave.
+ *   read by murbfield_at / murbfield_of and by murbtidal.h's murbtidal_at / murbtidal_of (which murbfield_layout plans too) and
+ *   by nothing else.  tests/test_field_gpu.py checks this on runs of every integrator, and the values themselves against fp64
+ *   at the state those runs leave.
  *
  * murbfield_at: px, py, pz the points; pvx, pvy, pvz their velocities, all three NULL = points at rest; skip NULL, or per point
  *   a body index or -1.  The skipped body is left out of all three sums BY SLOT: it never enters an fp32 sum (the reason

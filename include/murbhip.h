@@ -612,8 +612,8 @@ int murbhip_set_option(murbhip_ctx* ctx, const char* key, long value);
  *   "span_<kind>_ms_avg", "span_<kind>_count"               kind = tri1 | rect | tri2 (the three force launches of the exchange
  *       pipeline), reduce_scatter | all_gather (exchange stream: from "my input is ready" to "my output has arrived"),
  *       wait_gather | wait_reduce (compute stream idle, waiting for that collective), step (compute stream, first launch of
- *       a step to the end of its state update), field (compute stream: a sweep launch of the field read-out, murbfield.h; no
- *       part of the force_* figures); the last six need "profile" 2
+ *       a step to the end of its state update), field | tidal (compute stream: a sweep launch of the field read-out, murbfield.h,
+ *       or of the tidal read-out, murbtidal.h; no part of the force_* figures); the last seven need "profile" 2
  *   "compute_wait_ms_per_step"                              (wait_gather + wait_reduce) per profiled step
  *   "spans_dropped"                                         1 when the event pool (4096 spans per shard) ran out
  *   "sym_launches"                                          pair-symmetric launches of any form (force, force + pair potential,

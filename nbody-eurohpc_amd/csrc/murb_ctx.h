@@ -12,6 +12,7 @@
 #include "murb_kernels_block.h"     // murb_kernels_pair.h, _side.h, _hermite.h, _adaptive.h on the way
 #include "murb_kernels_field.h"
 #include "murb_kernels_sym.h"
+#include "murb_kernels_tidal.h"   // last: the kernels before it keep their places in the code object
 #include "murb_rccl.h"
 
 namespace {
@@ -109,7 +110,8 @@ struct Shard {
     float* herm_phi = nullptr;                // per slot: phi_i of the remembered evaluation (include/murbhip.h, "potential")
     double* pot_sums = nullptr;               // block sums of murbhip_potential_energy
     double* pot_sums_host = nullptr;          // ... and their pinned host copy
-    // field read-out (murbfield_at / murbfield_of): buffers of its own, allocated on first use and grown (ensure_field)
+    // field read-out (murbfield_at / murbfield_of): buffers of its own, allocated on first use and grown (ensure_field); the
+    // tidal read-out (murbtidal_at / murbtidal_of) uses the same ones: both are synchronous on the compute stream
     float* fld_in = nullptr;        // a launch's uploaded points: 6 planes of floats and one of ints (skip entries or bodies)
     float4* fld_pts = nullptr;      // ... packed: two records per point
     float* fld_out = nullptr;       // ... results: 7 planes
@@ -157,6 +159,7 @@ enum ProfKind {
     kProfWaitReduce,      // compute stream: idle in front of the state update, waiting for the reduced share
     kProfStep,            // compute stream: first launch of a step to the end of its state update
     kProfField,           // compute stream: a sweep launch of the field read-out (murbfield.h); never part of the force figures
+    kProfTidal,           // compute stream: a sweep launch of the tidal read-out (murbtidal.h); never part of the force figures
     kProfKinds
 };
 

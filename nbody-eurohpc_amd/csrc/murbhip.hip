@@ -38,6 +38,7 @@
 
 #include "../../include/murbhip.h"
 #include "../../include/murbfield.h"
+#include "../../include/murbtidal.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
 
@@ -775,6 +776,7 @@ int enqueue_iteration(murbhip_ctx* c, float dt, int update_state)
 // a change of the bodies evaluates (a0, j0) at the current state first.  One launch shape for every N: 4 i bodies per wave,
 // 4 waves per workgroup, 2 position + 2 velocity tiles per stage (32 KiB of LDS, like the one-sided force kernel).
 constexpr int kHermiteR = 4, kHermiteWaves = 4, kHermiteStage = 2;
+constexpr int kTidalStage = 4;   // the tidal sweep stages positions alone: 4 tiles fill the 32 KiB the sweeps' 2 tiles with velocities do
 
 int ensure_hermite(murbhip_ctx* c, Shard& sh, int rows)
 {
@@ -1322,6 +1324,68 @@ int field_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], c
         if (lo < hi) HIP_TRY(hipMemcpy(host.data() + lo * cap, sh.fld_out + lo * cap, (size_t)(hi - lo) * cap * sizeof(float), hipMemcpyDeviceToHost));
         for (int k = 0; k < 7; ++k)
             if (out[k]) std::memcpy(out[k] + first, host.data() + k * cap, bn * sizeof(float));
+    }
+    return 0;
+}
+
+// ---- tidal read-out (murbtidal_at / murbtidal_of; kernels: murb_kernels_tidal.h) -----------------------------------
+// field_run with another sweep: the same planning (murb_field_layout under "field_chunks" / "field_batch"), the same batching,
+// the same grid, and the field read-out's own buffers (both calls are synchronous on the compute stream, so neither sees the
+// other's rows).  p: the three position planes (murbtidal_at) or all null (murbtidal_of: idx are the bodies); out: txx tyy
+// tzz txy txz tyz, all set or all null.
+int tidal_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, float* const (&out)[6])
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, cap * (size_t)l.chunks));
+    std::vector<float> host(6 * cap, 0.f);
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (idx) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, idx + first, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.idx = idx ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbTidalArgs ta{};
+        ta.rec = sh.rec[c->cur];
+        ta.pts = sh.fld_pts;
+        ta.part_a = sh.fld_part;
+        ta.part_b = sh.fld_part + sh.fld_rows;
+        ta.groups = (int)(padded / MURB_FIELD_GROUP);
+        ta.chunks = l.chunks;
+        ta.tiles = l.tiles;
+        ta.stride = (unsigned int)padded;   // chunks * padded <= fld_rows
+        ta.soft2 = c->soft2;
+        const long units = (long)ta.groups * ta.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // field_run's: 4 workgroups per CU
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfTidal, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_tidal_sweep_kernel<kHermiteR, kHermiteWaves, kTidalStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                           sh.compute, ta);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        hipLaunchKernelGGL(murb_tidal_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)ta.part_a, (const float4*)ta.part_b, sh.fld_out, (int)bn, ta.chunks, ta.stride, (unsigned int)cap);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (!out[0]) continue;
+        HIP_TRY(hipMemcpy(host.data(), sh.fld_out, 6 * cap * sizeof(float), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; ++k) std::memcpy(out[k] + first, host.data() + k * cap, bn * sizeof(float));
     }
     return 0;
 }
@@ -1929,7 +1993,7 @@ int murbfield_set_option(murbhip_ctx* c, const char* key, long value)
     if (k != "field_chunks" && k != "field_batch") return MURBHIP_E_INVALID;
     const bool chunks = k == "field_chunks";
     if (!murb_field_options_valid(chunks ? value : 0, chunks ? 0 : value)) return MURBHIP_E_INVALID;
-    (chunks ? c->field_chunks : c->field_batch) = value;   // read by the field read-out alone
+    (chunks ? c->field_chunks : c->field_batch) = value;   // read by the field and tidal read-outs alone
     return 0;
 }
 
@@ -1942,6 +2006,37 @@ int murbfield_get_option(murbhip_ctx* c, const char* key, long* value)
     else if (k == "field_batch") *value = (long)l.batch;
     else return MURBHIP_E_INVALID;
     return 0;
+}
+
+int murbtidal_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const int* skip,
+                 float* txx, float* tyy, float* tzz, float* txy, float* txz, float* tyz)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !all_or_none({txx, tyy, tzz, txy, txz, tyz})) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz})
+        for (unsigned long i = 0; i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {px, py, pz};
+    float* const out[6] = {txx, tyy, tzz, txy, txz, tyz};
+    return tidal_run(c, count, p, skip, false, out);
+}
+
+int murbtidal_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* txx, float* tyy, float* tzz, float* txy, float* txz,
+                 float* tyz)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!bodies || !all_or_none({txx, tyy, tzz, txy, txz, tyz})) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    float* const out[6] = {txx, tyy, tzz, txy, txz, tyz};
+    return tidal_run(c, count, p, bodies, true, out);
 }
 
 int murbhip_upload_radii(murbhip_ctx* c, const float* r)
@@ -2524,10 +2619,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "force_launches" || k == "force_ms_avg" || k == "force_ms_total" || k.rfind("span_", 0) == 0 || k == "compute_wait_ms_per_step") {
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
-        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field
+        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field"};
+                                                      "wait_reduce", "step", "field", "tidal"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

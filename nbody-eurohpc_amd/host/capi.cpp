@@ -222,6 +222,12 @@ int murbhost_sim_field_at(void *p, unsigned long count, const float *px, const f
 {
     return static_cast<Sim *>(p)->sim->fieldAt(count, px, py, pz, pvx, pvy, pvz, skip, ax, ay, az, jx, jy, jz, phi);
 }
+// SimulationNBodyHIP::tidalAt (murbtidal_at's arguments); murbhip's code
+int murbhost_sim_tidal_at(void *p, unsigned long count, const float *px, const float *py, const float *pz, const int *skip,
+                          float *txx, float *tyy, float *tzz, float *txy, float *txz, float *tyz)
+{
+    return static_cast<Sim *>(p)->sim->tidalAt(count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
+}
 int murbhost_sim_history_csv(void *p, const char *path)
 {
     try {

@@ -5,6 +5,7 @@
 
 #include "murbfield.h"
 #include "murbhip.h"
+#include "murbtidal.h"
 
 template <typename T>
 SimulationNBodyHIP<T>::SimulationNBodyHIP(const BodiesAllocatorInterface<T> &allocator, const T soft,
@@ -54,6 +55,13 @@ int SimulationNBodyHIP<T>::fieldAt(unsigned long count, const T *px, const T *py
                                    const int *skip, T *ax, T *ay, T *az, T *jx, T *jy, T *jz, T *phi)
 {
     return murbfield_at(hipBodiesPtr->getContext(), count, px, py, pz, pvx, pvy, pvz, skip, ax, ay, az, jx, jy, jz, phi);
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::tidalAt(unsigned long count, const T *px, const T *py, const T *pz, const int *skip, T *txx, T *tyy, T *tzz,
+                                   T *txy, T *txz, T *tyz)
+{
+    return murbtidal_at(hipBodiesPtr->getContext(), count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
 }
 
 template class SimulationNBodyHIP<float>;

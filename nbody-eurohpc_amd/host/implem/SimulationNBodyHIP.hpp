@@ -34,6 +34,12 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // murbhip's code (0 = done) instead of ending the program: a refused call is the caller's to handle.
     int fieldAt(unsigned long count, const T *px, const T *py, const T *pz, const T *pvx, const T *pvy, const T *pvz, const int *skip,
                 T *ax, T *ay, T *az, T *jx, T *jy, T *jz, T *phi);
+
+    // The tidal tensor d a_a / d p_b of the bodies, as they are on the device, at `count` points of the caller's (murbtidal_at's
+    // arguments and rules: skip null, or per point a body left out, -1 = none; the six outputs all set or all null).  A read-out
+    // like fieldAt; returns murbhip's code.
+    int tidalAt(unsigned long count, const T *px, const T *py, const T *pz, const int *skip, T *txx, T *tyy, T *tzz, T *txy, T *txz,
+                T *tyz);
 };
 
 #endif

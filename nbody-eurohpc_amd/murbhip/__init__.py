@@ -87,6 +87,9 @@ def lib():
         L.murbfield_layout.argtypes = [C.c_ulong, C.c_long, C.c_long, C.POINTER(C.c_ulong)]
         L.murbfield_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.murbfield_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
+        # include/murbtidal.h
+        L.murbtidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
+        L.murbtidal_of.argtypes = [C.c_void_p, C.c_ulong, C.POINTER(C.c_int)] + [_fp] * 6
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -115,6 +118,8 @@ EXPORTS = ("murbhip_version murbhip_error_string murbhip_partition murbhip_slice
 
 FIELD_EXPORTS = "murbfield_at murbfield_of murbfield_layout murbfield_set_option murbfield_get_option".split()   # include/murbfield.h
 FIELD_OPTIONS = ("field_chunks", "field_batch")
+TIDAL_EXPORTS = "murbtidal_at murbtidal_of".split()   # include/murbtidal.h
+TIDAL_KEYS = ("txx", "tyy", "tzz", "txy", "txz", "tyz")
 
 
 def error_string(code):
@@ -187,6 +192,15 @@ def field_layout(n, chunks=0, batch=0, count=0):
     k = int(out[0])
     return {"chunks": k, "groups": int(out[1]), "batches": int(out[2]), "rows": int(out[3]), "tiles": tiles,
             "ranges": [(tiles * c // k, tiles * (c + 1) // k) for c in range(k)]}
+
+
+def tidal_matrix(d):
+    """(P, 3, 3) float32: the symmetric matrices of a tidal_at() / tidal_of() result, for numpy.linalg.eigvalsh."""
+    t = [np.asarray(d[k]) for k in TIDAL_KEYS]
+    m = np.empty(t[0].shape + (3, 3), t[0].dtype)
+    for (a, b), x in zip(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)), t):
+        m[..., a, b] = m[..., b, a] = x
+    return m
 
 
 def device_count():
@@ -393,6 +407,33 @@ class Simulation:
                "murbfield_of")
         return out
 
+    def tidal_at(self, points, skip=None):
+        """The tidal tensor d a_a / d p_b the bodies make at `points` (3, count), with body skip[k] (or none: -1, or skip=None)
+        left out for point k (include/murbtidal.h: murbtidal_at).  A dict of float32 arrays txx tyy tzz txy txz tyz
+        (tidal_matrix() makes the 3 x 3 matrices).  A read-out: synchronous, changes nothing of the simulation."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        out = {k: np.zeros(count, np.float32) for k in TIDAL_KEYS}
+        _check(lib().murbtidal_at(self._h, count, *[_ptr(x) for x in p], sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                  *[_ptr(out[k]) for k in TIDAL_KEYS]), "murbtidal_at")
+        return out
+
+    def tidal_of(self, bodies):
+        """tidal_at at the listed bodies' own current positions, each with itself left out (include/murbtidal.h: murbtidal_of);
+        the gather happens on the device."""
+        b = np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        out = {k: np.zeros(b.shape[0], np.float32) for k in TIDAL_KEYS}
+        _check(lib().murbtidal_of(self._h, b.shape[0], b.ctypes.data_as(C.POINTER(C.c_int)), *[_ptr(out[k]) for k in TIDAL_KEYS]),
+               "murbtidal_of")
+        return out
+
     def contacts(self):
         """dict of the step that ended the last evolve call by a contact ("contact" 2): i, j (int32), gap2 (float32) sorted by
         i, the count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
@@ -565,6 +606,7 @@ def host_lib():
         H.murbhost_sim_set_potential.argtypes = [C.c_void_p, C.c_int]
         H.murbhost_sim_potential.argtypes = [C.c_void_p, _fp]
         H.murbhost_sim_field_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [C.POINTER(C.c_int)] + [_fp] * 7
+        H.murbhost_sim_tidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                             C.POINTER(C.c_ulong), _dp]
         _host = H
@@ -666,6 +708,18 @@ class HostSim:
                                           sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
                                           *[_ptr(out[k]) for k in Simulation._FIELD_KEYS])
         _check(rc, "murbhost_sim_field_at")
+        return out
+
+    def tidal_at(self, points, skip=None):
+        """SimulationNBodyHIP::tidalAt: Simulation.tidal_at on the plugin's bodies as they are on the device."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        sk = np.ascontiguousarray(skip, np.int32) if skip is not None else None
+        out = {k: np.zeros(count, np.float32) for k in TIDAL_KEYS}
+        rc = self.H.murbhost_sim_tidal_at(self.h, count, *[_ptr(x) for x in p],
+                                          sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                          *[_ptr(out[k]) for k in TIDAL_KEYS])
+        _check(rc, "murbhost_sim_tidal_at")
         return out
 
     def encounters(self):
