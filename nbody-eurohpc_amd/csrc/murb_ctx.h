@@ -12,7 +12,8 @@
 #include "murb_kernels_block.h"     // murb_kernels_pair.h, _side.h, _hermite.h, _adaptive.h on the way
 #include "murb_kernels_field.h"
 #include "murb_kernels_sym.h"
-#include "murb_kernels_tidal.h"   // last: the kernels before it keep their places in the code object
+#include "murb_kernels_tidal.h"   // behind the others: the kernels before it keep their places in the code object
+#include "murb_kernels_tracer.h"  // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -118,6 +119,13 @@ struct Shard {
     size_t fld_points = 0;          // points the three hold
     float4* fld_part = nullptr;     // partial rows: fld_rows entries {ax, ay, az, phi}, then as many {jx, jy, jz, 0}
     size_t fld_rows = 0;
+    // massless tracers (include/murbtracer.h): buffers of their own, allocated on first upload and grown (ensure_tracers).  The
+    // steps that carry them are enqueue-only and the read-outs above synchronous, so the two share nothing
+    float* trc_state = nullptr;     // 18 planes of trc_cap floats: q, v, (a0, j0), (a1, j1), three each
+    float4* trc_pts = nullptr;      // the packed (predicted) records: two per tracer, whole groups
+    size_t trc_cap = 0;             // tracers the two hold (a multiple of 16)
+    float4* trc_part = nullptr;     // partial rows: trc_rows entries {ax, ay, az, 0}, then as many {jx, jy, jz, 0}
+    size_t trc_rows = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -160,6 +168,7 @@ enum ProfKind {
     kProfStep,            // compute stream: first launch of a step to the end of its state update
     kProfField,           // compute stream: a sweep launch of the field read-out (murbfield.h); never part of the force figures
     kProfTidal,           // compute stream: a sweep launch of the tidal read-out (murbtidal.h); never part of the force figures
+    kProfTracer,          // compute stream: a sweep launch of the tracers (murbtracer.h); never part of the force figures
     kProfKinds
 };
 
@@ -206,6 +215,12 @@ struct murbhip_ctx {
     int potential = 0;              // "potential": the sweeps keep every body's phi_i beside (a, j); excludes "nearest" and "contact"
     long field_chunks = 0;          // "field_chunks": j chunks of the field read-out; 0 = default (murb_field.h)
     long field_batch = 0;           // "field_batch": its points per launch; 0 = default
+    // massless tracers (include/murbtracer.h)
+    unsigned long tracers = 0;      // resident tracers; 0 = none, and then nothing of the context differs from a build without them
+    bool trc_current = false;       // their (a0, j0) are those of the tracers' and the bodies' current state
+    long tracer_chunks = 0;         // "tracer_chunks", "tracer_batch": the field options' meaning (murb_field.h)
+    long tracer_batch = 0;
+    int tracer_dt = 0;              // "tracer_dt": 1 = the tracers' Aarseth steps enter murbhip_evolve's step-size minimum
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions
     bool acc_current = false;        // acc_out holds them (a second evaluation would be bit-identical: skip it)

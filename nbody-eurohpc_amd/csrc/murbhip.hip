@@ -39,6 +39,7 @@
 #include "../../include/murbhip.h"
 #include "../../include/murbfield.h"
 #include "../../include/murbtidal.h"
+#include "../../include/murbtracer.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
 
@@ -737,6 +738,7 @@ void invalidate_cached_forces(murbhip_ctx* c)
     c->herm_proposal = false;
     c->blk_open = false;        // murbhip_evolve_block: an open block is closed, the bodies' levels are dropped
     c->blk_have_levels = 0;
+    c->trc_current = false;     // the tracers' (a0, j0) were made against the old bodies (murbtracer.h)
     ++c->state_serial;
 }
 
@@ -894,6 +896,124 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
     return 0;
 }
 
+// ---- massless tracers (include/murbtracer.h; kernels: murb_kernels_tracer.h, host logic: murb_tracer.h) ----------------------
+// Resident beside the bodies on the one shard, carried by the Hermite steps on the compute stream, enqueue-only.  Everything
+// they write is their own; of the context they read the records and velocities a sweep is made at, and soft2.
+inline int block_grid(const murbhip_ctx* c);   // below: workgroups the chip holds at once
+
+inline MurbFieldLayout tracer_layout(const murbhip_ctx* c) { return murb_field_layout(c->in.n, c->tracer_chunks, c->tracer_batch); }
+
+// room for `count` tracers; the caller has waited for enqueued work where buffers are replaced
+int ensure_tracers(Shard& sh, unsigned long count)
+{
+    const size_t cap = murb_tracer_padded(count);
+    if (cap <= sh.trc_cap) return 0;
+    shard_free(sh, sh.trc_state, 18 * sh.trc_cap * sizeof(float));
+    shard_free(sh, sh.trc_pts, 2 * sh.trc_cap * sizeof(float4));
+    sh.trc_cap = 0;
+    RC_TRY(shard_alloc(sh, sh.trc_state, 18 * cap * sizeof(float)));   // q, v: the upload fills them; the rest is written before it is read
+    RC_TRY(shard_alloc(sh, sh.trc_pts, 2 * cap * sizeof(float4)));
+    sh.trc_cap = cap;
+    return 0;
+}
+
+// the partial rows of one launch under the options in force ("tracer_chunks" may have grown since the last sweep)
+int ensure_tracer_rows(murbhip_ctx* c, Shard& sh)
+{
+    const MurbFieldLayout l = tracer_layout(c);
+    const size_t rows = std::min<size_t>(l.batch, murb_tracer_padded(c->tracers)) * (size_t)l.chunks;
+    if (rows <= sh.trc_rows) return 0;
+    HIP_TRY(hipStreamSynchronize(sh.compute));   // an enqueued rows kernel may still read the old ones
+    shard_free(sh, sh.trc_part, 2 * sh.trc_rows * sizeof(float4));
+    sh.trc_rows = 0;
+    RC_TRY(shard_alloc(sh, sh.trc_part, 2 * rows * sizeof(float4)));
+    sh.trc_rows = rows;
+    return 0;
+}
+
+MurbTracerArgs tracer_args(const murbhip_ctx* c, const Shard& sh, float dt, int predict)
+{
+    MurbTracerArgs a{};
+    const size_t cap = sh.trc_cap;
+    a.q = sh.trc_state;
+    a.v = sh.trc_state + 3 * cap;
+    a.a0 = sh.trc_state + 6 * cap;
+    a.j0 = sh.trc_state + 9 * cap;
+    a.a1 = sh.trc_state + 12 * cap;
+    a.j1 = sh.trc_state + 15 * cap;
+    a.pts = sh.trc_pts;
+    a.count = (int)c->tracers;
+    a.padded = (int)murb_tracer_padded(c->tracers);
+    a.stride = (unsigned int)cap;
+    a.dt = dt;
+    a.predict = predict;
+    a.fold_dt = c->tracer_dt;
+    return a;
+}
+
+// the tracers' predicted records (predict 1) or their current ones (0) into trc_pts
+int enqueue_tracer_predict(murbhip_ctx* c, Shard& sh, float dt, int predict, const MurbEvolveCtl* ctl = nullptr)
+{
+    RC_TRY(ensure_tracer_rows(c, sh));
+    const MurbTracerArgs a = tracer_args(c, sh, dt, predict);
+    hipLaunchKernelGGL(murb_tracer_predict_kernel, dim3((unsigned)((a.padded + 255) / 256)), dim3(256), 0, sh.compute, a, ctl);
+    return hip_rc(hipGetLastError());
+}
+
+// (a, j) of the records in trc_pts against the bodies' state (rec, vel), in launches of at most "tracer_batch" tracers, each
+// with its row sum: into (a1, j1), or into (a0, j0) for an evaluation at the current state.  `ctl`: the control-block form of
+// an adaptive step, which records no timing span.
+int enqueue_tracer_sweeps(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel, bool evaluation, const MurbEvolveCtl* ctl = nullptr)
+{
+    const MurbFieldLayout l = tracer_layout(c);
+    const MurbTracerArgs a = tracer_args(c, sh, 0.f, 0);
+    float* const out_a = evaluation ? a.a0 : a.a1;
+    float* const out_j = evaluation ? a.j0 : a.j1;
+    for (unsigned long first = 0; first < c->tracers; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, c->tracers - first), padded = murb_tracer_padded(bn);
+        MurbTracerSweepArgs s{};
+        s.rec = rec;
+        s.vel = vel;
+        s.pts = sh.trc_pts + 2 * first;   // first + padded <= trc_cap: only the last launch is ragged
+        s.part_a = sh.trc_part;
+        s.part_j = sh.trc_part + sh.trc_rows;
+        s.groups = (int)(padded / MURB_FIELD_GROUP);
+        s.chunks = l.chunks;
+        s.tiles = l.tiles;
+        s.stride = (unsigned int)padded;   // chunks * padded <= trc_rows
+        s.soft2 = c->soft2;
+        const long units = (long)s.groups * s.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // the field sweep's: 4 workgroups per CU
+        int rc = 0;
+        const int sp = ctl ? -1 : span_begin(c, sh, kProfTracer, sh.compute, &rc);   // "profile" 2: a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_tracer_sweep_kernel<4, 4, 2>), dim3(grid), dim3(256), 0, sh.compute, s, ctl);
+        RC_TRY(hip_rc(hipGetLastError()));
+        RC_TRY(span_end(sh, sp, sh.compute));
+        hipLaunchKernelGGL(murb_tracer_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const float4*)s.part_a,
+                           (const float4*)s.part_j, out_a + first, out_j + first, (int)bn, s.chunks, s.stride, a.stride, ctl);
+        RC_TRY(hip_rc(hipGetLastError()));
+    }
+    return 0;
+}
+
+// make sure the tracers' (a0, j0) are those of the current state; never touches the bodies' remembered evaluation
+int enqueue_tracer_evaluation(murbhip_ctx* c, Shard& sh)
+{
+    if (!c->tracers || c->trc_current) return 0;
+    RC_TRY(enqueue_tracer_predict(c, sh, 0.f, 0));
+    RC_TRY(enqueue_tracer_sweeps(c, sh, sh.rec[c->cur], sh.vel, true));
+    c->trc_current = true;
+    return 0;
+}
+
+int enqueue_tracer_correct(murbhip_ctx* c, Shard& sh, float dt, MurbEvolveCtl* ctl = nullptr)
+{
+    const MurbTracerArgs a = tracer_args(c, sh, dt, 1);
+    hipLaunchKernelGGL(murb_tracer_correct_kernel, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, sh.compute, a, ctl);
+    return hip_rc(hipGetLastError());
+}
+
 // update_state 0: make sure (a0, j0) of the current state are remembered; 1: one step.
 int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
 {
@@ -923,20 +1043,26 @@ int enqueue_hermite(murbhip_ctx* c, float dt, int update_state)
         }
         return 0;
     }
+    const bool tracers = c->tracers != 0;   // carried along (murbtracer.h): their launches behind the bodies' of the same kind
+    RC_TRY(enqueue_tracer_evaluation(c, sh));
     MurbHermiteArgs a = hermite_args(c, sh, parts, dt, 1);
     a.rec_out = sh.herm_rec;
     a.vel_out = sh.herm_vel;
     hipLaunchKernelGGL(murb_hermite_predict_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
     RC_TRY(hip_rc(hipGetLastError()));
+    if (tracers) RC_TRY(enqueue_tracer_predict(c, sh, dt, 1));
     RC_TRY(enqueue_hermite_sweep(c, sh, sh.herm_rec, sh.herm_vel, parts));
+    if (tracers) RC_TRY(enqueue_tracer_sweeps(c, sh, sh.herm_rec, sh.herm_vel, false));   // at the bodies' PREDICTED state
     a.rec_out = sh.rec[c->cur ^ 1];
     a.vel_out = nullptr;
     hipLaunchKernelGGL(murb_hermite_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
     RC_TRY(hip_rc(hipGetLastError()));
+    if (tracers) RC_TRY(enqueue_tracer_correct(c, sh, dt));
     c->cur ^= 1;
     invalidate_cached_forces(c);
     c->herm_current = true;   // (a1, j1) of this step are the next step's (a0, j0)
     c->herm_in_acc_out = true;
+    c->trc_current = tracers; // ... for the tracers too
     return 0;
 }
 
@@ -952,13 +1078,17 @@ int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
     MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 1);
     a.rec_out = sh.herm_rec;
     a.vel_out = sh.herm_vel;
+    const bool tracers = c->tracers != 0;   // murbtracer.h: every tracer launch reads dt and `done` from the control block too
     hipLaunchKernelGGL(murb_hermite_predict_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
     RC_TRY(hip_rc(hipGetLastError()));
+    if (tracers) RC_TRY(enqueue_tracer_predict(c, sh, 0.f, 1, sh.herm_ctl));
     RC_TRY(enqueue_hermite_sweep(c, sh, sh.herm_rec, sh.herm_vel, parts, sh.herm_ctl));
+    if (tracers) RC_TRY(enqueue_tracer_sweeps(c, sh, sh.herm_rec, sh.herm_vel, false, sh.herm_ctl));
     a.rec_out = sh.rec[c->cur ^ 1];
     a.vel_out = nullptr;
     hipLaunchKernelGGL(murb_hermite_correct_adaptive_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl);
     RC_TRY(hip_rc(hipGetLastError()));
+    if (tracers) RC_TRY(enqueue_tracer_correct(c, sh, 0.f, sh.herm_ctl));   // in front of the bookkeeping: its minimum is folded by then
     hipLaunchKernelGGL(murb_evolve_book_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl);
     RC_TRY(hip_rc(hipGetLastError()));
     c->cur ^= 1;
@@ -1597,6 +1727,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.nn_idx, sh.nn_r2, sh.enc);
         release(sh.herm_phi, sh.pot_sums);
         release(sh.fld_in, sh.fld_pts, sh.fld_out, sh.fld_part);
+        release(sh.trc_state, sh.trc_pts, sh.trc_part);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2039,6 +2170,124 @@ int murbtidal_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* 
     return tidal_run(c, count, p, bodies, true, out);
 }
 
+// ---- include/murbtracer.h
+int murbtracer_validate(unsigned long count, const float* qx, const float* qy, const float* qz, const float* vx, const float* vy,
+                        const float* vz)
+{
+    const float* const q[3] = {qx, qy, qz};
+    const float* const v[3] = {vx, vy, vz};
+    return count <= (1ul << 30) && murb_tracer_upload_valid(count, q, v) ? 0 : MURBHIP_E_INVALID;
+}
+
+int murbtracer_upload(murbhip_ctx* c, unsigned long count, const float* qx, const float* qy, const float* qz, const float* vx,
+                      const float* vy, const float* vz)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (c->integrator != 2 || c->in.world != 1 || c->shards.size() != 1 || c->force_exchange || c->blk_open) return MURBHIP_E_STATE;
+    RC_TRY(murbtracer_validate(count, qx, qy, qz, vx, vy, vz));
+    if (count == 0) return murbtracer_clear(c);
+    RC_TRY(murbhip_sync(c));   // enqueued steps still carry the old set
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    RC_TRY(ensure_tracers(sh, count));
+    const size_t cap = sh.trc_cap;
+    std::vector<float> host(6 * cap, 0.f);
+    const float* const src[6] = {qx, qy, qz, vx, vy, vz};
+    for (int k = 0; k < 6; ++k)
+        if (src[k]) std::memcpy(host.data() + k * cap, src[k], count * sizeof(float));
+    HIP_TRY(hipMemcpy(sh.trc_state, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (c->tracer_dt) c->herm_proposal = false;   // the retained step was proposed for another set
+    c->tracers = count;
+    c->trc_current = false;
+    return 0;
+}
+
+int murbtracer_clear(murbhip_ctx* c)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (c->blk_open) return MURBHIP_E_STATE;
+    if (!c->tracers) return 0;
+    RC_TRY(murbhip_sync(c));
+    if (c->tracer_dt) c->herm_proposal = false;
+    c->tracers = 0;
+    c->trc_current = false;
+    return 0;
+}
+
+int murbtracer_count(murbhip_ctx* c, unsigned long* count)
+{
+    if (!c || !count) return MURBHIP_E_INVALID;
+    *count = c->tracers;
+    return 0;
+}
+
+int murbtracer_compute(murbhip_ctx* c)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->uploaded || c->blk_open || c->shards.size() != 1) return MURBHIP_E_STATE;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    return enqueue_tracer_evaluation(c, sh);
+}
+
+namespace {
+// planes [first, first + 6) of the tracers' state into the caller's arrays (null: not asked for)
+int tracer_read(murbhip_ctx* c, int first, float* const (&out)[6])
+{
+    RC_TRY(murbhip_sync(c));
+    if (!c->tracers) return 0;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const size_t cap = sh.trc_cap;
+    std::vector<float> host(6 * cap);
+    HIP_TRY(hipMemcpy(host.data(), sh.trc_state + (size_t)first * cap, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 6; ++k)
+        if (out[k]) std::memcpy(out[k], host.data() + k * cap, c->tracers * sizeof(float));
+    return 0;
+}
+}  // namespace
+
+int murbtracer_download(murbhip_ctx* c, float* qx, float* qy, float* qz, float* vx, float* vy, float* vz)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    float* const out[6] = {qx, qy, qz, vx, vy, vz};
+    return tracer_read(c, 0, out);
+}
+
+int murbtracer_download_forces(murbhip_ctx* c, float* ax, float* ay, float* az, float* jx, float* jy, float* jz)
+{
+    if (!c || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    if (!c->tracers || !c->trc_current) return MURBHIP_E_STATE;
+    float* const out[6] = {ax, ay, az, jx, jy, jz};
+    return tracer_read(c, 6, out);
+}
+
+int murbtracer_set_option(murbhip_ctx* c, const char* key, long value)
+{
+    if (!c || !murb_tracer_option_valid(key, value)) return MURBHIP_E_INVALID;
+    const std::string k(key);
+    if (k == "tracer_dt") {
+        if (c->tracers && c->tracer_dt != (int)value) c->herm_proposal = false;   // the retained step was proposed under the other rule
+        c->tracer_dt = (int)value;
+    } else if (k == "tracer_chunks") {
+        if (c->tracer_chunks != value) c->trc_current = false;   // another cut of the row sums
+        c->tracer_chunks = value;
+    } else c->tracer_batch = value;
+    return 0;
+}
+
+int murbtracer_get_option(murbhip_ctx* c, const char* key, long* value)
+{
+    if (!c || !key || !value) return MURBHIP_E_INVALID;
+    const std::string k(key);
+    const MurbFieldLayout l = tracer_layout(c);   // as resolved
+    if (k == "tracer_chunks") *value = l.chunks;
+    else if (k == "tracer_batch") *value = (long)l.batch;
+    else if (k == "tracer_dt") *value = c->tracer_dt;
+    else return MURBHIP_E_INVALID;
+    return 0;
+}
+
 int murbhip_upload_radii(murbhip_ctx* c, const float* r)
 {
     if (!c || !r) return MURBHIP_E_INVALID;
@@ -2052,6 +2301,7 @@ int murbhip_upload_radii(murbhip_ctx* c, const float* r)
     std::vector<float> buf(c->in.slice, 0.f);
     std::copy(r, r + c->in.n, buf.begin());
     HIP_TRY(hipMemcpy(sh.radius, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->trc_current = false;   // murbtracer.h: the tracers stay, their remembered evaluation goes
     if (c->contact) {
         invalidate_cached_forces(c);   // the remembered (cp, gap2) belong to the old radii
         RC_TRY(enqueue_radii_lanes(c));
@@ -2069,6 +2319,7 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
     if (!c->uploaded || c->integrator != 2 || c->blk_open) return MURBHIP_E_STATE;
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
     Shard& sh = c->shards[0];
+    RC_TRY(enqueue_tracer_evaluation(c, sh));   // murbtracer.h: beside the bodies' starting evaluation, or alone
     RC_TRY(shard_alloc(sh, sh.herm_ctl, sizeof(MurbEvolveCtl)));
     if (!sh.herm_ctl_host) HIP_TRY(hipHostMalloc((void**)&sh.herm_ctl_host, kEvolveHead, hipHostMallocDefault));
     const int parts = hermite_parts(c->in);
@@ -2082,6 +2333,11 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
         const MurbHermiteArgs a = hermite_args(c, sh, parts, 0.f, 0);
         hipLaunchKernelGGL(murb_evolve_first_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a, sh.herm_ctl, eta_start);
         RC_TRY(hip_rc(hipGetLastError()));
+        if (c->tracers && c->tracer_dt) {   // "tracer_dt" 1: the tracers' starting steps enter the same minimum
+            const MurbTracerArgs ta = tracer_args(c, sh, 0.f, 0);
+            hipLaunchKernelGGL(murb_tracer_first_kernel, dim3((unsigned)((ta.count + 255) / 256)), dim3(256), 0, sh.compute, ta, sh.herm_ctl, eta_start);
+            RC_TRY(hip_rc(hipGetLastError()));
+        }
         hipLaunchKernelGGL(murb_evolve_start_kernel, dim3(1), dim3(1), 0, sh.compute, sh.herm_ctl);
         RC_TRY(hip_rc(hipGetLastError()));
     }
@@ -2111,6 +2367,7 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
         c->herm_current = true;
         c->herm_in_acc_out = true;
         c->herm_proposal = true;
+        c->trc_current = c->tracers != 0;   // carried through the same steps
         RC_TRY(rc);
         HIP_TRY(hipMemcpyAsync(&head, sh.herm_ctl, kEvolveHead, hipMemcpyDeviceToHost, sh.compute));
         HIP_TRY(hipStreamSynchronize(sh.compute));
@@ -2154,7 +2411,7 @@ int murbhip_evolve_block(murbhip_ctx* c, float dt_max, unsigned long blocks, dou
     if (!std::isfinite(dt_max) || !(dt_max > 0.f) || blocks == 0 || blocks > 0xfffffffful || !(eta > 0.0) || !(eta_start > 0.0) ||
         kmax < 0 || kmax > 20 || max_steps == 0 || !std::isnormal(std::ldexp(dt_max, -kmax)))
         return MURBHIP_E_INVALID;
-    if (!c->uploaded || c->integrator != 2) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->integrator != 2 || c->tracers) return MURBHIP_E_STATE;   // tracers take no block steps (murbtracer.h)
     if (c->blk_open && (dt_max != c->blk_dt_max || kmax != c->blk_kmax)) return MURBHIP_E_STATE;   // the open block is another grid's
     const bool resume = c->blk_open;
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
@@ -2235,7 +2492,7 @@ int murbhip_block_set_levels(murbhip_ctx* c, const int* levels, int kmax)
     if (!c || !levels || kmax < 0 || kmax > 20) return MURBHIP_E_INVALID;
     for (unsigned long i = 0; i < c->in.n; ++i)
         if (levels[i] < 0 || levels[i] > kmax) return MURBHIP_E_INVALID;
-    if (!c->uploaded || c->integrator != 2 || c->blk_open || c->in.world != 1 || c->shards.size() != 1) return MURBHIP_E_STATE;
+    if (!c->uploaded || c->integrator != 2 || c->blk_open || c->in.world != 1 || c->shards.size() != 1 || c->tracers) return MURBHIP_E_STATE;
     Shard& sh = c->shards[0];
     HIP_TRY(hipSetDevice(sh.device));
     RC_TRY(ensure_block(c, sh));
@@ -2528,6 +2785,7 @@ int murbhip_set_option(murbhip_ctx* c, const char* key, long value)
         if (c->lf_half && value != c->integrator) return MURBHIP_E_STATE;   // half-step velocities on the device: upload first
         if (value == 2 && (c->in.world != 1 || c->shards.size() != 1 || c->force_exchange)) return MURBHIP_E_STATE;   // Hermite: one shard, no exchange (murbhip.h)
         if (value != 2 && (c->nearest || c->contact || c->potential)) return MURBHIP_E_STATE;   // they belong to the Hermite sweeps: switch them off first
+        if (value != 2 && c->tracers) return MURBHIP_E_STATE;   // the Hermite steps carry them (murbtracer.h): clear them first
         c->integrator = (int)value;
     }
     else if (k == "evolve_batch") {
@@ -2619,10 +2877,11 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
     else if (k == "force_launches" || k == "force_ms_avg" || k == "force_ms_total" || k.rfind("span_", 0) == 0 || k == "compute_wait_ms_per_step") {
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
-        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal
+        //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
+        //                                 tracer
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

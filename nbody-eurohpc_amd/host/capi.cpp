@@ -228,6 +228,19 @@ int murbhost_sim_tidal_at(void *p, unsigned long count, const float *px, const f
 {
     return static_cast<Sim *>(p)->sim->tidalAt(count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
 }
+// SimulationNBodyHIP::setTracers / getTracers (murbtracer_upload's and murbtracer_download's arguments); murbhip's code
+int murbhost_sim_set_tracers(void *p, unsigned long count, const float *qx, const float *qy, const float *qz, const float *vx,
+                             const float *vy, const float *vz)
+{
+    return static_cast<Sim *>(p)->sim->setTracers(count, qx, qy, qz, vx, vy, vz);
+}
+int murbhost_sim_get_tracers(void *p, unsigned long *count, float *qx, float *qy, float *qz, float *vx, float *vy, float *vz)
+{
+    if (count)
+        if (const int rc = static_cast<Sim *>(p)->sim->getTracerCount(count)) return rc;
+    if (!qx && !qy && !qz && !vx && !vy && !vz) return 0;   // the count alone
+    return static_cast<Sim *>(p)->sim->getTracers(qx, qy, qz, vx, vy, vz);
+}
 int murbhost_sim_history_csv(void *p, const char *path)
 {
     try {

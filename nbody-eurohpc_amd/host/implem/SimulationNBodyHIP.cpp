@@ -6,6 +6,7 @@
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbtidal.h"
+#include "murbtracer.h"
 
 template <typename T>
 SimulationNBodyHIP<T>::SimulationNBodyHIP(const BodiesAllocatorInterface<T> &allocator, const T soft,
@@ -62,6 +63,22 @@ int SimulationNBodyHIP<T>::tidalAt(unsigned long count, const T *px, const T *py
                                    T *txy, T *txz, T *tyz)
 {
     return murbtidal_at(hipBodiesPtr->getContext(), count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::setTracers(unsigned long count, const T *qx, const T *qy, const T *qz, const T *vx, const T *vy, const T *vz)
+{
+    return murbtracer_upload(hipBodiesPtr->getContext(), count, qx, qy, qz, vx, vy, vz);
+}
+
+template <typename T> int SimulationNBodyHIP<T>::getTracers(T *qx, T *qy, T *qz, T *vx, T *vy, T *vz)
+{
+    return murbtracer_download(hipBodiesPtr->getContext(), qx, qy, qz, vx, vy, vz);
+}
+
+template <typename T> int SimulationNBodyHIP<T>::getTracerCount(unsigned long *count)
+{
+    return murbtracer_count(hipBodiesPtr->getContext(), count);
 }
 
 template class SimulationNBodyHIP<float>;

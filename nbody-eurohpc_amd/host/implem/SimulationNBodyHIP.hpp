@@ -40,6 +40,14 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // like fieldAt; returns murbhip's code.
     int tidalAt(unsigned long count, const T *px, const T *py, const T *pz, const int *skip, T *txx, T *tyy, T *tzz, T *txy, T *txz,
                 T *tyz);
+
+    // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
+    // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
+    // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return
+    // murbhip's code.
+    int setTracers(unsigned long count, const T *qx, const T *qy, const T *qz, const T *vx, const T *vy, const T *vz);
+    int getTracers(T *qx, T *qy, T *qz, T *vx, T *vy, T *vz);
+    int getTracerCount(unsigned long *count);
 };
 
 #endif

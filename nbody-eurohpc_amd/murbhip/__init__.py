@@ -90,6 +90,16 @@ def lib():
         # include/murbtidal.h
         L.murbtidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
         L.murbtidal_of.argtypes = [C.c_void_p, C.c_ulong, C.POINTER(C.c_int)] + [_fp] * 6
+        # include/murbtracer.h
+        L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
+        L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
+        L.murbtracer_download_forces.argtypes = [C.c_void_p] + [_fp] * 6
+        L.murbtracer_compute.argtypes = [C.c_void_p]
+        L.murbtracer_count.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)]
+        L.murbtracer_clear.argtypes = [C.c_void_p]
+        L.murbtracer_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
+        L.murbtracer_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
+        L.murbtracer_validate.argtypes = [C.c_ulong] + [_fp] * 6
         L.murbhip_warmup.argtypes = [C.c_void_p, C.c_double]
         L.murbhip_step.argtypes = [C.c_void_p, C.c_float]
         L.murbhip_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
@@ -120,6 +130,9 @@ FIELD_EXPORTS = "murbfield_at murbfield_of murbfield_layout murbfield_set_option
 FIELD_OPTIONS = ("field_chunks", "field_batch")
 TIDAL_EXPORTS = "murbtidal_at murbtidal_of".split()   # include/murbtidal.h
 TIDAL_KEYS = ("txx", "tyy", "tzz", "txy", "txz", "tyz")
+TRACER_EXPORTS = ("murbtracer_upload murbtracer_download murbtracer_download_forces murbtracer_compute murbtracer_count "
+                  "murbtracer_clear murbtracer_set_option murbtracer_get_option murbtracer_validate").split()   # include/murbtracer.h
+TRACER_OPTIONS = ("tracer_chunks", "tracer_batch", "tracer_dt")
 
 
 def error_string(code):
@@ -434,6 +447,50 @@ class Simulation:
                "murbtidal_of")
         return out
 
+    # -- massless tracers (include/murbtracer.h)
+    def upload_tracers(self, q, v=None):
+        """`q` (3, count) positions and `v` (3, count; None = at rest) velocities of massless test particles at the bodies'
+        current model time; replaces any earlier set, count 0 clears (include/murbtracer.h: murbtracer_upload).  The Hermite
+        steps (steps() under "integrator" 2, evolve()) carry them along on the device."""
+        qa, va = _tracer_arrays(q, v)
+        count = qa[0].shape[0]
+        _check(lib().murbtracer_upload(self._h, count, *[_ptr(x) for x in qa], *([_ptr(x) for x in va] if va else [None] * 3)),
+               "murbtracer_upload")
+
+    def tracer_count(self):
+        count = C.c_ulong()
+        _check(lib().murbtracer_count(self._h, C.byref(count)), "murbtracer_count")
+        return int(count.value)
+
+    def tracers(self):
+        """dict of float32 arrays qx qy qz vx vy vz of the resident tracers (murbtracer_download); syncs."""
+        out = {k: np.zeros(self.tracer_count(), np.float32) for k in FIELDS[:6]}
+        _check(lib().murbtracer_download(self._h, *[_ptr(out[k]) for k in FIELDS[:6]]), "murbtracer_download")
+        return out
+
+    def tracer_forces(self):
+        """dict of float32 arrays ax ay az jx jy jz: the tracers' remembered evaluation (murbtracer_download_forces); syncs."""
+        out = {k: np.zeros(self.tracer_count(), np.float32) for k in self._FIELD_KEYS[:6]}
+        _check(lib().murbtracer_download_forces(self._h, *[_ptr(out[k]) for k in self._FIELD_KEYS[:6]]), "murbtracer_download_forces")
+        return out
+
+    def compute_tracers(self):
+        """(a, j) of the tracers at the current state (murbtracer_compute; enqueue only); read with tracer_forces()."""
+        _check(lib().murbtracer_compute(self._h), "murbtracer_compute")
+
+    def clear_tracers(self):
+        _check(lib().murbtracer_clear(self._h), "murbtracer_clear")
+
+    def set_tracer_option(self, key, value):
+        """"tracer_chunks" / "tracer_batch" / "tracer_dt" (include/murbtracer.h: murbtracer_set_option)."""
+        _check(lib().murbtracer_set_option(self._h, key.encode(), int(value)), f"murbtracer_set_option({key})")
+
+    def tracer_option(self, key):
+        """The value of a tracer option in force, defaults resolved (murbtracer_get_option)."""
+        f = C.c_long()
+        _check(lib().murbtracer_get_option(self._h, key.encode(), C.byref(f)), f"murbtracer_get_option({key})")
+        return f.value
+
     def contacts(self):
         """dict of the step that ended the last evolve call by a contact ("contact" 2): i, j (int32), gap2 (float32) sorted by
         i, the count the device saw (the arrays hold at most 4096) and the model time advanced in that call; count 0 otherwise."""
@@ -503,6 +560,18 @@ class Simulation:
             self.close()
         except Exception:
             pass
+
+
+def _tracer_arrays(q, v):
+    """The six arrays of an upload of tracers, checked the way murbtracer_upload checks them (murbtracer_validate: host only),
+    so that a refused set raises before any device is touched."""
+    qa = [_f32(x) for x in q]
+    va = [_f32(x) for x in v] if v is not None else None
+    if len(qa) != 3 or (va is not None and len(va) != 3) or any(x.ndim != 1 or x.shape != qa[0].shape for x in qa + (va or [])):
+        raise ValueError("positions and velocities are three arrays of one length each")
+    _check(lib().murbtracer_validate(qa[0].shape[0], *[_ptr(x) for x in qa], *([_ptr(x) for x in va] if va else [None] * 3)),
+           "murbtracer_upload")
+    return qa, va
 
 
 def merge_contacts(state, radii, i, j):
@@ -607,6 +676,8 @@ def host_lib():
         H.murbhost_sim_potential.argtypes = [C.c_void_p, _fp]
         H.murbhost_sim_field_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [C.POINTER(C.c_int)] + [_fp] * 7
         H.murbhost_sim_tidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
+        H.murbhost_sim_set_tracers.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
+        H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                             C.POINTER(C.c_ulong), _dp]
         _host = H
@@ -647,7 +718,8 @@ class HostSim:
     """SimulationNBodyHIP<float> behind HIPBodiesAllocator<float> — the `--im hip+tile[+multi]` plugin."""
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
-                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0, potential=False):
+                 leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0, potential=False,
+                 tracers=None):
         """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
         driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
@@ -656,7 +728,12 @@ class HostSim:
         behind the substep in which a body has its nearest neighbour within R; encounters() then has the pairs.  contact=True
         (integrator 3 or 4, not beside encounter=): it ends behind the substep in which two bodies touch, their radii being
         the scheme's times rscale; contacts() then has the pairs.  potential=True (integrator 2, 3 or 4, not beside encounter= or
-        contact=): the sweeps keep every body's potential; potential() then has it."""
+        contact=): the sweeps keep every body's potential; potential() then has it.  tracers=(q, v) (integrator 2 or 3; v may be
+        None: at rest): massless test particles the iterations carry along (Simulation.upload_tracers); tracers() has them."""
+        if tracers is not None and integrator not in (2, 3):
+            raise ValueError("tracers= needs integrator 2 or 3")
+        if tracers is not None:
+            tq, tv = _tracer_arrays(*tracers)
         if integrator is None:
             integrator = int(bool(leapfrog))
         if contact and integrator not in (3, 4):
@@ -688,6 +765,17 @@ class HostSim:
         if potential:
             if self.H.murbhost_sim_set_potential(self.h, 1) != 0:
                 raise ValueError("potential= needs integrator 2, 3 or 4")
+        if tracers is not None:
+            _check(self.H.murbhost_sim_set_tracers(self.h, tq[0].shape[0], *[_ptr(x) for x in tq],
+                                                   *([_ptr(x) for x in tv] if tv else [None] * 3)), "murbhost_sim_set_tracers")
+
+    def tracers(self):
+        """SimulationNBodyHIP::getTracers: dict of float32 arrays qx qy qz vx vy vz of the tracers the plugin carries."""
+        count = C.c_ulong()
+        _check(self.H.murbhost_sim_get_tracers(self.h, C.byref(count), *([None] * 6)), "murbhost_sim_get_tracers")
+        out = {k: np.zeros(count.value, np.float32) for k in FIELDS[:6]}
+        _check(self.H.murbhost_sim_get_tracers(self.h, C.byref(count), *[_ptr(out[k]) for k in FIELDS[:6]]), "murbhost_sim_get_tracers")
+        return out
 
     def potential(self):
         """potential=True: float32 phi_i of every body in the last sweep (Simulation.potential; after an iteration: of its last
