@@ -14,6 +14,7 @@
 #include "murb_kernels_sym.h"
 #include "murb_kernels_tidal.h"   // behind the others: the kernels before it keep their places in the code object
 #include "murb_kernels_tracer.h"  // likewise
+#include "murb_kernels_knn.h"     // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -126,6 +127,18 @@ struct Shard {
     size_t trc_cap = 0;             // tracers the two hold (a multiple of 16)
     float4* trc_part = nullptr;     // partial rows: trc_rows entries {ax, ay, az, 0}, then as many {jx, jy, jz, 0}
     size_t trc_rows = 0;
+    // k nearest neighbours and densities (include/murbknn.h): the points go through the field read-out's fld_in / fld_pts (every
+    // call of either is synchronous on the compute stream); the lists and rows are its own, allocated on first use and grown
+    float* knn_part_r2 = nullptr;   // the chunks' lists: knn_part entries of r2 ...
+    int* knn_part_idx = nullptr;    // ... and of indices
+    size_t knn_part = 0;
+    float* knn_list_r2 = nullptr;   // a launch's merged lists: knn_list entries each
+    int* knn_list_idx = nullptr;
+    size_t knn_list = 0;
+    float* knn_rho = nullptr;       // densities: of a launch's points, or of all bodies (murbdensity_centre); knn_rhos floats
+    size_t knn_rhos = 0;
+    double* knn_sums = nullptr;     // block rows of murb_knn_centre_kernel: knn_blocks rows
+    size_t knn_blocks = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -169,6 +182,7 @@ enum ProfKind {
     kProfField,           // compute stream: a sweep launch of the field read-out (murbfield.h); never part of the force figures
     kProfTidal,           // compute stream: a sweep launch of the tidal read-out (murbtidal.h); never part of the force figures
     kProfTracer,          // compute stream: a sweep launch of the tracers (murbtracer.h); never part of the force figures
+    kProfKnn,             // compute stream: a sweep launch of the neighbour read-out (murbknn.h); never part of the force figures
     kProfKinds
 };
 

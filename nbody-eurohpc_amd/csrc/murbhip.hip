@@ -39,6 +39,7 @@
 #include "../../include/murbhip.h"
 #include "../../include/murbfield.h"
 #include "../../include/murbtidal.h"
+#include "../../include/murbknn.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
@@ -1520,6 +1521,149 @@ int tidal_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], c
     return 0;
 }
 
+// ---- k nearest neighbours, densities, density centre (include/murbknn.h; kernels: murb_kernels_knn.h) --------------
+constexpr int kKnnStage = 2;   // positions alone: 2 tiles of 8 KiB
+
+template <typename T>
+int grow(Shard& sh, T*& p, size_t& have, size_t want)
+{
+    if (want <= have) return 0;
+    shard_free(sh, p, have * sizeof(T));
+    have = 0;
+    RC_TRY(shard_alloc(sh, p, want * sizeof(T)));
+    have = want;
+    return 0;
+}
+
+// field_run with a list in the place of the sums: the same planning (murb_field_layout under "field_chunks" / "field_batch"),
+// the same batching and grid, the field read-out's point buffers, lists and rows of its own.  p: the three position planes
+// (murbknn_at) or all null (of bodies: idx lists them, or null for all n in order).  out_idx, out_r2, out_rho: host arrays, null
+// where not asked for; rho_all: the densities stay on the device, knn_rho[body] (murbdensity_centre; all bodies in order).
+int knn_run(murbhip_ctx* c, int k, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, int* out_idx,
+            float* out_r2, float* out_rho, bool rho_all)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    const bool want_rho = out_rho || rho_all;
+    RC_TRY(ensure_field(sh, cap, 0));
+    {   // r2 and indices grow together: each pair shares one size
+        const size_t part = cap * (size_t)l.chunks * (size_t)k, list = cap * (size_t)k;
+        size_t part_r2 = sh.knn_part, list_r2 = sh.knn_list;
+        RC_TRY(grow(sh, sh.knn_part_r2, part_r2, part));
+        RC_TRY(grow(sh, sh.knn_part_idx, sh.knn_part, part));
+        RC_TRY(grow(sh, sh.knn_list_r2, list_r2, list));
+        RC_TRY(grow(sh, sh.knn_list_idx, sh.knn_list, list));
+        if (want_rho) RC_TRY(grow(sh, sh.knn_rho, sh.knn_rhos, rho_all ? std::max<size_t>(count, cap) : cap));
+    }
+    std::vector<float> host(3 * cap, 0.f);
+    std::vector<int> all;
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            for (int e = 0; e < 3; ++e) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        const int* list = idx ? idx + first : nullptr;
+        if (of_bodies && !idx) {   // all bodies in order
+            all.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
+            list = all.data();
+        }
+        if (list) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.idx = list ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbKnnArgs ka{};
+        ka.rec = sh.rec[c->cur];
+        ka.pts = sh.fld_pts;
+        ka.part_r2 = sh.knn_part_r2;
+        ka.part_idx = sh.knn_part_idx;
+        ka.groups = (int)(padded / MURB_FIELD_GROUP);
+        // The layout's chunk count is the MOST a launch is cut into.  A list, unlike a sum, does not depend on the cut, and
+        // every chunk starts its lists empty and pays the slow path's first trips again: a launch whose groups fill the grid
+        // on their own is not cut at all, one with fewer into as many chunks as fill it.
+        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
+        ka.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + ka.groups - 1) / ka.groups));
+        ka.tiles = l.tiles;
+        ka.count = (int)c->in.n;
+        ka.k = k;
+        ka.stride = (unsigned int)padded;   // chunks * padded * k <= knn_part
+        ka.soft2 = c->soft2;
+        const long units = (long)ka.groups * ka.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfKnn, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_knn_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                           sh.compute, ka);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        const dim3 per_point((unsigned)((bn + 255) / 256));
+        hipLaunchKernelGGL(murb_knn_rows_kernel, per_point, dim3(256), 0, sh.compute, (const float*)ka.part_r2,
+                           (const int*)ka.part_idx, sh.knn_list_idx, sh.knn_list_r2, (int)bn, ka.chunks, ka.stride, k);
+        float* const rho = want_rho ? sh.knn_rho + (rho_all ? first : 0ul) : nullptr;
+        if (rho)
+            hipLaunchKernelGGL(murb_knn_density_kernel, per_point, dim3(256), 0, sh.compute, (const int*)sh.knn_list_idx,
+                               (const float*)sh.knn_list_r2, (const float*)sh.mass, rho, (int)bn, k, c->soft2);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first * k, sh.knn_list_idx, bn * k * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + first * k, sh.knn_list_r2, bn * k * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rho) HIP_TRY(hipMemcpy(out_rho + first, rho, bn * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// The density of every body, then the centre: two launches of block sums, their rows added on the host in index order.
+int knn_centre(murbhip_ctx* c, int k, double* out8)
+{
+    const float* const none[3] = {nullptr, nullptr, nullptr};
+    const unsigned long n = c->in.n;
+    RC_TRY(knn_run(c, k, n, none, nullptr, true, nullptr, nullptr, nullptr, true));
+    Shard& sh = c->shards[0];
+    const size_t blocks = (n + 255) / 256;
+    RC_TRY(grow(sh, sh.knn_sums, sh.knn_blocks, blocks * MURB_KNN_CENTRE_VALUES));
+    std::vector<double> rows(blocks * MURB_KNN_CENTRE_VALUES);
+    double sum[MURB_KNN_CENTRE_VALUES], x[3] = {0.0, 0.0, 0.0};
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(murb_knn_centre_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float4*)sh.rec[c->cur],
+                           (const float*)sh.knn_rho, sh.knn_sums, (int)n, pass, x[0], x[1], x[2]);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipMemcpyAsync(rows.data(), sh.knn_sums, rows.size() * sizeof(double), hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        double s[MURB_KNN_CENTRE_VALUES] = {0};
+        for (size_t b = 0; b < blocks; ++b)
+            for (int e = 0; e < MURB_KNN_CENTRE_VALUES; ++e) s[e] += rows[b * MURB_KNN_CENTRE_VALUES + e];
+        if (pass == 0) {
+            for (int e = 0; e < MURB_KNN_CENTRE_VALUES; ++e) sum[e] = s[e];
+            for (int e = 0; e < 3; ++e) x[e] = sum[2 + e] / sum[0];
+            out8[5] = sum[0];
+            out8[6] = sum[5];
+            out8[7] = (double)n - sum[5];
+            if (sum[0] == 0.0) {
+                for (int e = 0; e < 5; ++e) out8[e] = std::numeric_limits<double>::quiet_NaN();
+                return 0;
+            }
+        } else {
+            for (int e = 0; e < 3; ++e) out8[e] = x[e];
+            out8[3] = std::sqrt(s[0] / sum[1]);
+            out8[4] = sum[1] / sum[0];
+        }
+    }
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -1728,6 +1872,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.herm_phi, sh.pot_sums);
         release(sh.fld_in, sh.fld_pts, sh.fld_out, sh.fld_part);
         release(sh.trc_state, sh.trc_pts, sh.trc_part);
+        release(sh.knn_part_r2, sh.knn_part_idx, sh.knn_list_r2, sh.knn_list_idx, sh.knn_rho, sh.knn_sums);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2168,6 +2313,79 @@ int murbtidal_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* 
     const float* const p[3] = {nullptr, nullptr, nullptr};
     float* const out[6] = {txx, tyy, tzz, txy, txz, tyz};
     return tidal_run(c, count, p, bodies, true, out);
+}
+
+// ---- include/murbknn.h
+namespace {
+inline bool knn_k_valid(int k, int least) { return k >= least && k <= MURBKNN_KMAX; }
+
+// the checks murbknn_of and murbdensity_of share; 1: nothing to do
+int knn_of_checks(murbhip_ctx* c, int k, int least, unsigned long count, const int* bodies)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 1;
+    RC_TRY(field_state(c));
+    if (!knn_k_valid(k, least)) return MURBHIP_E_INVALID;
+    if (!bodies) return count == c->in.n ? 0 : MURBHIP_E_INVALID;
+    for (unsigned long i = 0; i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    return 0;
+}
+}  // namespace
+
+int murbknn_of(murbhip_ctx* c, int k, unsigned long count, const int* bodies, int* idx, float* r2)
+{
+    const int rc = knn_of_checks(c, k, 1, count, bodies);
+    if (rc != 0) return rc == 1 ? 0 : rc;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    return knn_run(c, k, count, p, bodies, true, idx, r2, nullptr, false);
+}
+
+int murbknn_at(murbhip_ctx* c, int k, unsigned long count, const float* px, const float* py, const float* pz, const int* skip,
+               int* idx, float* r2)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!knn_k_valid(k, 1) || !px || !py || !pz) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz})
+        for (unsigned long i = 0; i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {px, py, pz};
+    return knn_run(c, k, count, p, skip, false, idx, r2, nullptr, false);
+}
+
+int murbdensity_of(murbhip_ctx* c, int k, unsigned long count, const int* bodies, float* rho)
+{
+    const int rc = knn_of_checks(c, k, 2, count, bodies);
+    if (rc != 0) return rc == 1 ? 0 : rc;
+    if (!rho) return MURBHIP_E_INVALID;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    return knn_run(c, k, count, p, bodies, true, nullptr, nullptr, rho, false);
+}
+
+int murbdensity_centre(murbhip_ctx* c, int k, double* out8)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    RC_TRY(field_state(c));
+    if (!knn_k_valid(k, 2) || !out8) return MURBHIP_E_INVALID;
+    return knn_centre(c, k, out8);
+}
+
+int murbknn_merge(int k, const int* idx_a, const float* r2_a, const int* idx_b, const float* r2_b, int* idx_out, float* r2_out)
+{
+    if (!knn_k_valid(k, 1) || !idx_a || !r2_a || !idx_b || !r2_b || !idx_out || !r2_out) return MURBHIP_E_INVALID;
+    murb_knn_merge(k, idx_a, r2_a, idx_b, r2_b, idx_out, r2_out);
+    return 0;
+}
+
+int murbknn_density(int k, const int* idx, const float* r2, const float* masses, float soft, float* rho_out)
+{
+    if (!knn_k_valid(k, 2) || !idx || !r2 || !masses || !rho_out) return MURBHIP_E_INVALID;
+    *rho_out = murb_knn_density(k, idx, r2, masses, soft * soft);
+    return 0;
 }
 
 // ---- include/murbtracer.h
@@ -2878,10 +3096,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer
+        //                                 tracer, knn
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal", "tracer"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

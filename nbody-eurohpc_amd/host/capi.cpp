@@ -228,6 +228,19 @@ int murbhost_sim_tidal_at(void *p, unsigned long count, const float *px, const f
 {
     return static_cast<Sim *>(p)->sim->tidalAt(count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
 }
+// SimulationNBodyHIP::densityCentre (murbdensity_centre's arguments); murbhip's code
+int murbhost_sim_density_centre(void *p, int k, double *out8)
+{
+    return static_cast<Sim *>(p)->sim->densityCentre(k, out8);
+}
+// --im hip+tracking+density: SimulationNBodyHIPTracking::setDensityCentre.  0, or -1 for a simulation without a history.
+int murbhost_sim_set_density_centre(void *p, int on)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    if (!t) return -1;
+    t->setDensityCentre(on != 0);
+    return 0;
+}
 // SimulationNBodyHIP::setTracers / getTracers (murbtracer_upload's and murbtracer_download's arguments); murbhip's code
 int murbhost_sim_set_tracers(void *p, unsigned long count, const float *qx, const float *qy, const float *qz, const float *vx,
                              const float *vy, const float *vz)

@@ -5,6 +5,7 @@
 
 #include "murbfield.h"
 #include "murbhip.h"
+#include "murbknn.h"
 #include "murbtidal.h"
 #include "murbtracer.h"
 
@@ -63,6 +64,11 @@ int SimulationNBodyHIP<T>::tidalAt(unsigned long count, const T *px, const T *py
                                    T *txy, T *txz, T *tyz)
 {
     return murbtidal_at(hipBodiesPtr->getContext(), count, px, py, pz, skip, txx, tyy, tzz, txy, txz, tyz);
+}
+
+template <typename T> int SimulationNBodyHIP<T>::densityCentre(int k, double *out8)
+{
+    return murbdensity_centre(hipBodiesPtr->getContext(), k, out8);
 }
 
 template <typename T>

@@ -41,6 +41,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     int tidalAt(unsigned long count, const T *px, const T *py, const T *pz, const int *skip, T *txx, T *tyy, T *tzz, T *txy, T *txz,
                 T *tyz);
 
+    // Density centre, core radius and core density of the bodies as they are on the device, from every body's local density
+    // over its k nearest (murbdensity_centre's arguments and rules: out8 = {X_x, X_y, X_z, r_c, rho_c, sum rho, used, left out}).
+    // A read-out like fieldAt; returns murbhip's code.
+    int densityCentre(int k, double *out8);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

@@ -29,6 +29,12 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
     history->setEnergyAt(currentIteration, (Q)(kinetic + potential));
     history->setAngMomentumAt(currentIteration, (Q)std::sqrt(mom[3] * mom[3] + mom[4] * mom[4] + mom[5] * mom[5]));
     const double mass = mom[9] != 0 ? mom[9] : 1;
+    if (densityCentreOn) {   // hip+tracking+density: the density centre over every body's 6 nearest in the centre of mass's place
+        double out8[8];
+        murbhipCheck(this->densityCentre(6, out8), "murbdensity_centre");
+        history->setDensityCenterAt(currentIteration, {(Q)out8[0], (Q)out8[1], (Q)out8[2]});
+        return;
+    }
     history->setDensityCenterAt(currentIteration, {(Q)(mom[6] / mass), (Q)(mom[7] / mass), (Q)(mom[8] / mass)});
 }
 

@@ -9,7 +9,8 @@
 //
 // Filled per iteration: energy (kinetic + potential, reference definitions), |angular momentum| and the
 // centre of mass — the reference reserves the last two columns but never computes them
-// (SimulationNBodyCUDAPropertyTracking.cu:5-8).
+// (SimulationNBodyCUDAPropertyTracking.cu:5-8).  `--im hip+tracking+density` is hip+tracking with the density centre
+// over every body's 6 nearest neighbours (include/murbknn.h) in the centre's columns.
 #ifndef SIMULATION_N_BODY_HIP_TRACKING_HPP_
 #define SIMULATION_N_BODY_HIP_TRACKING_HPP_
 
@@ -47,6 +48,7 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     std::vector<Encounter> contacts;     // (i, contact partner of i, gap2) of that substep, sorted by i (the device keeps 4096)
     unsigned long contactCount = 0;
     double contactTime = 0;
+    bool densityCentreOn = false;        // the density_center columns hold the density centre, not the centre of mass
 
   public:
     // integrator: murbhip option "integrator" — 0 (false) the reference's update, 1 (true) kick-drift-kick leapfrog,
@@ -96,6 +98,10 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     // integrators and beside either of the two.
     bool setPotential(const bool on);
     bool hasPotential() const { return potentialOn; }
+    // hip+tracking+density: the history's density_center columns hold the density centre over every body's 6 nearest
+    // (densityCentre(6)) instead of the centre of mass.  Every integrator.
+    void setDensityCentre(const bool on) { densityCentreOn = on; }
+    bool hasDensityCentre() const { return densityCentreOn; }
     // phi_i of the last sweep in the bodies' order (murbhip_download_potential; after an iteration: of its last substep's
     // predicted end state); empty where the option is off or no sweep has run yet
     std::vector<float> getPotential() const;

@@ -77,6 +77,7 @@ static std::vector<Option> optionTable()
          "\t\t\t - \"hip+tile\"        one MI355X, device-resident bodies\n"
          "\t\t\t - \"hip+tile+multi\"  bodies partitioned over --ngpu MI355X, RCCL position exchange\n"
          "\t\t\t - \"hip+tracking\"    hip+tile + energy / angular momentum / centre of mass per iteration\n"
+         "\t\t\t - \"hip+tracking+density\"  hip+tracking with the density centre (6 nearest neighbours) in the centre's columns\n"
          "\t\t\t - \"hip+leapfrog\"    hip+tracking with a kick-drift-kick leapfrog integrator\n"
          "\t\t\t - \"hip+hermite\"     hip+tracking with a 4th-order Hermite integrator (its sweep also computes the jerks:\n"
          "\t\t\t                      about twice the arithmetic of the 20 N^2 flops per iteration reported)\n"
@@ -206,15 +207,17 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
                                          use <= visible ? 1 : 0);
     }
     if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite" || ImplTag == "hip+hermite+adaptive" ||
-        ImplTag == "hip+hermite+block") {
+        ImplTag == "hip+hermite+block" || ImplTag == "hip+tracking+density") {
         // shaped like main.cpp:245-261
         const std::map<std::string, int> integrator = {{"hip+tracking", 0}, {"hip+leapfrog", 1}, {"hip+hermite", 2},
-                                                       {"hip+hermite+adaptive", 3}, {"hip+hermite+block", 4}};
+                                                       {"hip+hermite+adaptive", 3}, {"hip+hermite+block", 4},
+                                                       {"hip+tracking+density", 0}};
         HIPBodiesAllocator<T> hipAllocator(NBodies, BodiesScheme);
         History = std::make_shared<SimulationHistory<double>>((int)NIterations);
         auto *tracking = new SimulationNBodyHIPTracking<T, double>(hipAllocator, History, Softening, integrator.at(ImplTag));
         tracking->setEta(Eta);
         tracking->setKmax(Kmax);
+        tracking->setDensityCentre(ImplTag == "hip+tracking+density");
         if (Renc > 0.f && !tracking->setEncounterRadius(Renc)) {
             std::cout << "--renc needs hip+hermite+adaptive or hip+hermite+block... exiting." << std::endl;
             exit(-1);

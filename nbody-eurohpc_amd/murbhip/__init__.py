@@ -90,6 +90,14 @@ def lib():
         # include/murbtidal.h
         L.murbtidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
         L.murbtidal_of.argtypes = [C.c_void_p, C.c_ulong, C.POINTER(C.c_int)] + [_fp] * 6
+        # include/murbknn.h
+        _ip = C.POINTER(C.c_int)
+        L.murbknn_of.argtypes = [C.c_void_p, C.c_int, C.c_ulong, _ip, _ip, _fp]
+        L.murbknn_at.argtypes = [C.c_void_p, C.c_int, C.c_ulong] + [_fp] * 3 + [_ip, _ip, _fp]
+        L.murbdensity_of.argtypes = [C.c_void_p, C.c_int, C.c_ulong, _ip, _fp]
+        L.murbdensity_centre.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+        L.murbknn_merge.argtypes = [C.c_int, _ip, _fp, _ip, _fp, _ip, _fp]
+        L.murbknn_density.argtypes = [C.c_int, _ip, _fp, _fp, C.c_float, _fp]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -133,6 +141,9 @@ TIDAL_KEYS = ("txx", "tyy", "tzz", "txy", "txz", "tyz")
 TRACER_EXPORTS = ("murbtracer_upload murbtracer_download murbtracer_download_forces murbtracer_compute murbtracer_count "
                   "murbtracer_clear murbtracer_set_option murbtracer_get_option murbtracer_validate").split()   # include/murbtracer.h
 TRACER_OPTIONS = ("tracer_chunks", "tracer_batch", "tracer_dt")
+KNN_EXPORTS = "murbknn_of murbknn_at murbdensity_of murbdensity_centre murbknn_merge murbknn_density".split()   # include/murbknn.h
+KNN_KMAX = 32
+CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
 def error_string(code):
@@ -214,6 +225,39 @@ def tidal_matrix(d):
     for (a, b), x in zip(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)), t):
         m[..., a, b] = m[..., b, a] = x
     return m
+
+
+def knn_merge(idx_a, r2_a, idx_b, r2_b):
+    """(idx, r2): the k first entries of the merge of two sorted neighbour lists of k entries each under the order (r2, index),
+    tails of -1 / +inf (host only; include/murbknn.h: murbknn_merge)."""
+    ia, ib = (np.ascontiguousarray(x, np.int32) for x in (idx_a, idx_b))
+    ra, rb = _f32(r2_a), _f32(r2_b)
+    k = ia.shape[0]
+    if any(x.shape != (k,) for x in (ia, ib, ra, rb)):
+        raise ValueError("four lists of one length")
+    io, ro = np.zeros(k, np.int32), np.zeros(k, np.float32)
+    ip = C.POINTER(C.c_int)
+    _check(lib().murbknn_merge(k, ia.ctypes.data_as(ip), _ptr(ra), ib.ctypes.data_as(ip), _ptr(rb), io.ctypes.data_as(ip), _ptr(ro)),
+           "murbknn_merge")
+    return io, ro
+
+
+def knn_density(idx, r2, masses, soft):
+    """float32 density of one sorted neighbour list: the mass of its k - 1 first entries over the sphere through the k-th
+    (host only; include/murbknn.h: murbknn_density).  masses is indexed by the list's indices."""
+    i, r, m = np.ascontiguousarray(idx, np.int32), _f32(r2), _f32(masses)
+    if i.shape != r.shape or i.ndim != 1:
+        raise ValueError("idx and r2 are one list")
+    if i.size and i.max() >= m.shape[0]:
+        raise ValueError("an index has no mass")
+    out = np.zeros(1, np.float32)
+    _check(lib().murbknn_density(i.shape[0], i.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r), _ptr(m), float(np.float32(soft)), _ptr(out)),
+           "murbknn_density")
+    return out[0]
+
+
+def _centre_dict(out):
+    return {"x": np.array(out[:3]), "r_core": out[3], "rho_core": out[4], "rho_sum": out[5], "used": int(out[6]), "left_out": int(out[7])}
 
 
 def device_count():
@@ -447,6 +491,54 @@ class Simulation:
                "murbtidal_of")
         return out
 
+    # -- k nearest neighbours and densities (include/murbknn.h)
+    def _knn_bodies(self, bodies):
+        if bodies is None:
+            return self.n, None
+        b = np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        return b.shape[0], b.ctypes.data_as(C.POINTER(C.c_int))
+
+    def knn_of(self, bodies=None, k=6):
+        """(idx (count, k) int32, r2 (count, k) float32): the k nearest other bodies of the listed bodies (None: all, in order) by
+        (r2, index), r2 the sweeps' |d|^2 + soft^2; -1 / +inf where there are fewer (include/murbknn.h: murbknn_of).  A read-out:
+        synchronous, changes nothing of the simulation."""
+        count, bp = self._knn_bodies(bodies)
+        idx, r2 = np.full((count, max(k, 0)), -1, np.int32), np.full((count, max(k, 0)), np.inf, np.float32)
+        _check(lib().murbknn_of(self._h, k, count, bp, idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r2)), "murbknn_of")
+        return idx, r2
+
+    def knn_at(self, points, k=6, skip=None):
+        """knn_of at `points` (3, count) of the caller's, with body skip[p] (or none: -1, or skip=None) no candidate of point p
+        (include/murbknn.h: murbknn_at)."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        idx, r2 = np.full((count, max(k, 0)), -1, np.int32), np.full((count, max(k, 0)), np.inf, np.float32)
+        _check(lib().murbknn_at(self._h, k, count, *[_ptr(x) for x in p], sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r2)), "murbknn_at")
+        return idx, r2
+
+    def density(self, k=6, bodies=None):
+        """float32 local density of the listed bodies (None: all, in order): the mass of a body's k - 1 nearest over the sphere
+        through its k-th (include/murbknn.h: murbdensity_of)."""
+        count, bp = self._knn_bodies(bodies)
+        rho = np.zeros(count, np.float32)
+        _check(lib().murbdensity_of(self._h, k, count, bp, _ptr(rho)), "murbdensity_of")
+        return rho
+
+    def density_centre(self, k=6):
+        """dict of the density centre x (3,), the core radius r_core, the core density rho_core, rho_sum, and the counts of bodies
+        used and left_out (those k - 1 others share a point with) (include/murbknn.h: murbdensity_centre)."""
+        out = (C.c_double * 8)()
+        _check(lib().murbdensity_centre(self._h, k, out), "murbdensity_centre")
+        return _centre_dict(out[:])
+
     # -- massless tracers (include/murbtracer.h)
     def upload_tracers(self, q, v=None):
         """`q` (3, count) positions and `v` (3, count; None = at rest) velocities of massless test particles at the bodies'
@@ -676,7 +768,9 @@ def host_lib():
         H.murbhost_sim_potential.argtypes = [C.c_void_p, _fp]
         H.murbhost_sim_field_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [C.POINTER(C.c_int)] + [_fp] * 7
         H.murbhost_sim_tidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
-        H.murbhost_sim_set_tracers.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
+        H.murbhost_sim_density_centre.argtypes = [C.c_void_p, C.c_int, _dp]
+        H.murbhost_sim_set_density_centre.argtypes = [C.c_void_p, C.c_int]
+        H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
                                             C.POINTER(C.c_ulong), _dp]
@@ -719,8 +813,10 @@ class HostSim:
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
                  leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0, potential=False,
-                 tracers=None):
-        """tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
+                 tracers=None, density_centre=False):
+        """density_centre=True (with tracking=True or an integrator): `--im hip+tracking+density`, the history's density_center
+        columns hold density_centre()'s x instead of the centre of mass.
+        tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
         driven by murbhip_evolve: an iteration advances dt of model time in as many substeps as the criterion asks for; 4 is
         `hip+hermite+block`, option 2 driven by murbhip_evolve_block: an iteration is one block of dt, every body in steps of
@@ -765,6 +861,9 @@ class HostSim:
         if potential:
             if self.H.murbhost_sim_set_potential(self.h, 1) != 0:
                 raise ValueError("potential= needs integrator 2, 3 or 4")
+        if density_centre:
+            if self.H.murbhost_sim_set_density_centre(self.h, 1) != 0:
+                raise ValueError("density_centre= needs tracking=True or an integrator")
         if tracers is not None:
             _check(self.H.murbhost_sim_set_tracers(self.h, tq[0].shape[0], *[_ptr(x) for x in tq],
                                                    *([_ptr(x) for x in tv] if tv else [None] * 3)), "murbhost_sim_set_tracers")
@@ -809,6 +908,12 @@ class HostSim:
                                           *[_ptr(out[k]) for k in TIDAL_KEYS])
         _check(rc, "murbhost_sim_tidal_at")
         return out
+
+    def density_centre(self, k=6):
+        """SimulationNBodyHIP::densityCentre: Simulation.density_centre on the plugin's bodies as they are on the device."""
+        out = (C.c_double * 8)()
+        _check(self.H.murbhost_sim_density_centre(self.h, k, out), "murbhost_sim_density_centre")
+        return _centre_dict(out[:])
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
