@@ -334,7 +334,7 @@ int murbhip_block_set_levels(murbhip_ctx* ctx, const int* levels, int kmax);
  *   when the hit was seen.  The list is cleared at the head of every evolve call.  NULL arrays ask for the count (and time)
  *   alone; MURBHIP_E_INVALID when capacity < min(*count, 4096).
  * Not covered: several shards or ranks; the other integrators and the pair-symmetric force kernel; full neighbour lists
- * (per-body radii: "contact" below). */
+ * (an interface of their own, murbnbr.h: all bodies within a radius; per-body radii: "contact" below). */
 int murbhip_download_nearest(murbhip_ctx* ctx, int* idx, float* r2);
 int murbhip_set_encounter(murbhip_ctx* ctx, float radius);
 int murbhip_encounters(murbhip_ctx* ctx, int* i, int* j, float* r2, unsigned long capacity, unsigned long* count, double* time);

@@ -67,7 +67,7 @@
  *   Both return MURBHIP_E_INVALID for k out of range or a NULL pointer.
  *
  * Not covered: several shards or ranks; block-open states; k > 32; neighbour lists as an integrator input (an Ahmad-Cohen
- *   scheme); neighbours within a radius.
+ *   scheme); neighbours within a radius (murbnbr.h: counts and full lists, per body or point).
  */
 #ifndef MURBKNN_H_
 #define MURBKNN_H_

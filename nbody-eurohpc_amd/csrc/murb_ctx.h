@@ -15,6 +15,7 @@
 #include "murb_kernels_tidal.h"   // behind the others: the kernels before it keep their places in the code object
 #include "murb_kernels_tracer.h"  // likewise
 #include "murb_kernels_knn.h"     // likewise
+#include "murb_kernels_nbr.h"     // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -139,6 +140,16 @@ struct Shard {
     size_t knn_rhos = 0;
     double* knn_sums = nullptr;     // block rows of murb_knn_centre_kernel: knn_blocks rows
     size_t knn_blocks = 0;
+    // neighbours within a radius (include/murbnbr.h): the points go through the field read-out's fld_in / fld_pts like the knn
+    // read-out's; counts, bases and the list buffer are its own, allocated on first use and grown
+    unsigned int* nbr_part = nullptr;    // the chunks' counts, then their prefix sums per point: nbr_parts entries
+    size_t nbr_parts = 0;
+    unsigned int* nbr_counts = nullptr;  // a launch's counts per point: nbr_points entries ...
+    unsigned int* nbr_base = nullptr;    // ... and a range's bases per point
+    size_t nbr_points = 0;
+    int* nbr_idx = nullptr;              // the list buffer ("list_entries"): nbr_list entries of indices ...
+    float* nbr_r2 = nullptr;             // ... and of r2
+    size_t nbr_list = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -183,6 +194,7 @@ enum ProfKind {
     kProfTidal,           // compute stream: a sweep launch of the tidal read-out (murbtidal.h); never part of the force figures
     kProfTracer,          // compute stream: a sweep launch of the tracers (murbtracer.h); never part of the force figures
     kProfKnn,             // compute stream: a sweep launch of the neighbour read-out (murbknn.h); never part of the force figures
+    kProfNbr,             // compute stream: a count or fill sweep launch of the radius read-out (murbnbr.h); never part of the force figures
     kProfKinds
 };
 
@@ -229,6 +241,7 @@ struct murbhip_ctx {
     int potential = 0;              // "potential": the sweeps keep every body's phi_i beside (a, j); excludes "nearest" and "contact"
     long field_chunks = 0;          // "field_chunks": j chunks of the field read-out; 0 = default (murb_field.h)
     long field_batch = 0;           // "field_batch": its points per launch; 0 = default
+    long nbr_list_entries = 0;      // "list_entries" (murbnbr.h): the device list buffer's entries; 0 = default (murb_nbr.h)
     // massless tracers (include/murbtracer.h)
     unsigned long tracers = 0;      // resident tracers; 0 = none, and then nothing of the context differs from a build without them
     bool trc_current = false;       // their (a0, j0) are those of the tracers' and the bodies' current state

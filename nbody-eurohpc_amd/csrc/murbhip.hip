@@ -40,6 +40,7 @@
 #include "../../include/murbfield.h"
 #include "../../include/murbtidal.h"
 #include "../../include/murbknn.h"
+#include "../../include/murbnbr.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
@@ -1664,6 +1665,142 @@ int knn_centre(murbhip_ctx* c, int k, double* out8)
     return 0;
 }
 
+// ---- neighbours within a radius (include/murbnbr.h; kernels: murb_kernels_nbr.h, the cut: murb_nbr.h) -----------------
+// knn_run's planning, batching, grid and point buffers with a count per point in the place of the list, then (lists asked
+// for, and they fit) a second pass that fills them.  p: the three position planes (murbnbr_at) or all null (of bodies: idx
+// lists them, or null for all n in order).  thr: a threshold per point.  offsets: count + 1 entries.  out_idx, out_r2: host
+// arrays of `capacity` entries, null where not asked for; both null: the count pass alone.
+int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const std::vector<float>& thr,
+            unsigned long* offsets, int* out_idx, float* out_r2, unsigned long capacity)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    const bool lists = out_idx || out_r2;
+    const unsigned long launches = murb_field_batches(l, count);
+    RC_TRY(ensure_field(sh, cap, 0));
+    // with lists every launch keeps its rows of prefix sums until the fill pass: launch b's rows start at b * batch * chunks
+    RC_TRY(grow(sh, sh.nbr_part, sh.nbr_parts, (lists ? (launches - 1) * l.batch + cap : cap) * (size_t)l.chunks));
+    {
+        size_t points = sh.nbr_points;
+        RC_TRY(grow(sh, sh.nbr_counts, points, cap));
+        RC_TRY(grow(sh, sh.nbr_base, sh.nbr_points, cap));
+    }
+    const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
+    std::vector<float> host(4 * cap, 0.f);
+    std::vector<int> all;
+    std::vector<unsigned int> counts(cap), base(cap);
+
+    // uploads and packs the points [first, first + bn) of the call; the sweeps' arguments but for the fill's own
+    const auto stage = [&](unsigned long first, unsigned long bn, MurbNbrArgs& na) -> int {
+        const unsigned long padded = whole_groups(bn);
+        if (!of_bodies)
+            for (int e = 0; e < 3; ++e) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
+        std::memcpy(host.data() + 3 * cap, thr.data() + first, bn * sizeof(float));
+        if (of_bodies) HIP_TRY(hipMemcpy(sh.fld_in + 3 * cap, host.data() + 3 * cap, cap * sizeof(float), hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 4 * cap * sizeof(float), hipMemcpyHostToDevice));
+        const int* list = idx ? idx + first : nullptr;
+        if (of_bodies && !idx) {   // all bodies in order
+            all.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
+            list = all.data();
+        }
+        if (list) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbNbrPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.thr = sh.fld_in + 3 * cap;
+        pa.idx = list ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        hipLaunchKernelGGL(murb_nbr_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        na = MurbNbrArgs{};
+        na.rec = sh.rec[c->cur];
+        na.pts = sh.fld_pts;
+        na.part = sh.nbr_part + (lists ? first * (size_t)l.chunks : 0ul);   // first is a multiple of the batch
+        na.group_first = 0;
+        na.groups = (int)(padded / MURB_FIELD_GROUP);
+        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a count does not depend on the cut
+        na.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + na.groups - 1) / na.groups));
+        na.tiles_each = l.tiles / na.chunks;   // chunks <= tiles: at least one tile each
+        na.tiles_more = l.tiles % na.chunks;
+        na.count = (int)c->in.n;
+        na.stride = (unsigned int)padded;   // chunks * padded <= the launch's rows
+        na.soft2 = c->soft2;
+        return 0;
+    };
+    const auto sweep = [&](const MurbNbrArgs& na, bool fill) -> int {
+        const long units = (long)na.groups * na.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfNbr, sh.compute, &rc);   // "profile" 2: the sweeps alone, a span kind of their own
+        RC_TRY(rc);
+        if (fill)
+            hipLaunchKernelGGL((murb_nbr_fill_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, na);
+        else
+            hipLaunchKernelGGL((murb_nbr_count_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, na);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        return hip_rc(hipGetLastError());
+    };
+
+    offsets[0] = 0;
+    MurbNbrArgs na{};
+    for (unsigned long first = 0; first < count; first += l.batch) {   // the count pass
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
+        RC_TRY(stage(first, bn, na));
+        RC_TRY(sweep(na, false));
+        hipLaunchKernelGGL(murb_nbr_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, na.part, sh.nbr_counts,
+                           (int)bn, na.chunks, na.stride);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipMemcpyAsync(counts.data(), sh.nbr_counts, bn * sizeof(unsigned int), hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        for (unsigned long e = 0; e < bn; ++e) offsets[first + e + 1] = offsets[first + e] + counts[e];
+    }
+    if (!lists) return 0;
+    if (offsets[count] > capacity) return MURBHIP_E_INVALID;   // idx and r2 untouched: the caller sizes them from the offsets
+
+    const unsigned long entries = murb_nbr_entries(c->nbr_list_entries);
+    for (unsigned long first = 0; first < count; first += l.batch) {   // the fill pass
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
+        if (offsets[first + bn] == offsets[first]) continue;
+        if (launches > 1) RC_TRY(stage(first, bn, na));   // one launch: its points are still packed
+        for (unsigned long lo = 0, hi; lo < bn; lo = hi) {   // ranges of the launch's points whose lists fit the buffer
+            hi = murb_nbr_cut(bn, offsets + first, lo, entries);
+            const unsigned long total = offsets[first + hi] - offsets[first + lo];
+            if (total == 0) continue;
+            {   // a single list longer than "list_entries" grows the buffer to that list
+                size_t have = sh.nbr_list;
+                const size_t want = std::max(have, (size_t)std::min<unsigned long>(std::max(entries, total), offsets[count]));
+                RC_TRY(grow(sh, sh.nbr_idx, have, want));
+                RC_TRY(grow(sh, sh.nbr_r2, sh.nbr_list, want));
+            }
+            const unsigned long g0 = lo / MURB_FIELD_GROUP, g1 = (hi + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP;
+            for (unsigned long e = g0 * MURB_FIELD_GROUP; e < g1 * MURB_FIELD_GROUP; ++e)
+                base[e - g0 * MURB_FIELD_GROUP] = e >= lo && e < hi ? (unsigned int)(offsets[first + e] - offsets[first + lo]) : MURB_NBR_NO_BASE;
+            HIP_TRY(hipMemcpyAsync(sh.nbr_base, base.data(), (g1 - g0) * MURB_FIELD_GROUP * sizeof(unsigned int), hipMemcpyHostToDevice, sh.compute));
+            MurbNbrArgs fa = na;
+            fa.base = sh.nbr_base;
+            fa.out_idx = sh.nbr_idx;
+            fa.out_r2 = sh.nbr_r2;
+            fa.capacity = (unsigned int)sh.nbr_list;   // >= total: no place of the range lies beyond it
+            fa.group_first = (int)g0;
+            fa.groups = (int)(g1 - g0);
+            RC_TRY(sweep(fa, true));
+            HIP_TRY(hipStreamSynchronize(sh.compute));
+            if (out_idx) HIP_TRY(hipMemcpy(out_idx + offsets[first + lo], sh.nbr_idx, total * sizeof(int), hipMemcpyDeviceToHost));
+            if (out_r2) HIP_TRY(hipMemcpy(out_r2 + offsets[first + lo], sh.nbr_r2, total * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -1873,6 +2010,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.fld_in, sh.fld_pts, sh.fld_out, sh.fld_part);
         release(sh.trc_state, sh.trc_pts, sh.trc_part);
         release(sh.knn_part_r2, sh.knn_part_idx, sh.knn_list_r2, sh.knn_list_idx, sh.knn_rho, sh.knn_sums);
+        release(sh.nbr_part, sh.nbr_counts, sh.nbr_base, sh.nbr_idx, sh.nbr_r2);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2385,6 +2523,82 @@ int murbknn_density(int k, const int* idx, const float* r2, const float* masses,
 {
     if (!knn_k_valid(k, 2) || !idx || !r2 || !masses || !rho_out) return MURBHIP_E_INVALID;
     *rho_out = murb_knn_density(k, idx, r2, masses, soft * soft);
+    return 0;
+}
+
+// ---- include/murbnbr.h
+namespace {
+// the radii of a call, checked, as thresholds; false: a radius that is negative or not finite
+bool nbr_thresholds(const murbhip_ctx* c, unsigned long count, const float* h, float h_all, std::vector<float>& thr)
+{
+    const auto valid = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    if (!h && !valid(h_all)) return false;
+    for (unsigned long i = 0; h && i < count; ++i)
+        if (!valid(h[i])) return false;
+    thr.resize(count);
+    for (unsigned long i = 0; i < count; ++i) thr[i] = murb_nbr_threshold(h ? h[i] : h_all, c->soft2);
+    return true;
+}
+}  // namespace
+
+int murbnbr_of(murbhip_ctx* c, unsigned long count, const int* bodies, const float* h, float h_all, unsigned long* offsets, int* idx,
+               float* r2, unsigned long capacity)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!offsets || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    std::vector<float> thr;
+    if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    return nbr_run(c, count, p, bodies, true, thr, offsets, idx, r2, capacity);
+}
+
+int murbnbr_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const int* skip, const float* h,
+               float h_all, unsigned long* offsets, int* idx, float* r2, unsigned long capacity)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !offsets) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz})
+        for (unsigned long i = 0; i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    std::vector<float> thr;
+    if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
+    const float* const p[3] = {px, py, pz};
+    return nbr_run(c, count, p, skip, false, thr, offsets, idx, r2, capacity);
+}
+
+int murbnbr_set_option(murbhip_ctx* c, const char* key, long value)
+{
+    if (!c || !key || std::string(key) != "list_entries" || !murb_nbr_option_valid(value)) return MURBHIP_E_INVALID;
+    c->nbr_list_entries = value;   // read by the radius read-out's fill pass alone
+    return 0;
+}
+
+int murbnbr_get_option(murbhip_ctx* c, const char* key, long* value)
+{
+    if (!c || !key || !value || std::string(key) != "list_entries") return MURBHIP_E_INVALID;
+    *value = (long)murb_nbr_entries(c->nbr_list_entries);   // as resolved
+    return 0;
+}
+
+int murbnbr_threshold(float h, float soft, float* thr)
+{
+    if (!thr || !std::isfinite(h) || h < 0.f || !std::isfinite(soft) || soft < 0.f) return MURBHIP_E_INVALID;
+    *thr = murb_nbr_threshold(h, soft * soft);
+    return 0;
+}
+
+int murbnbr_cut(unsigned long count, const unsigned long* offsets, unsigned long first, unsigned long entries, unsigned long* last)
+{
+    if (!offsets || !last || first >= count) return MURBHIP_E_INVALID;
+    *last = murb_nbr_cut(count, offsets, first, entries);
     return 0;
 }
 
@@ -3096,10 +3310,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn
+        //                                 tracer, knn, nbr
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -233,6 +233,20 @@ int murbhost_sim_density_centre(void *p, int k, double *out8)
 {
     return static_cast<Sim *>(p)->sim->densityCentre(k, out8);
 }
+// SimulationNBodyHIP::neighboursOf: offsets (n + 1 entries) always; idx where it is given and holds the total (capacity entries),
+// else MURBHIP_E_INVALID (-2000) with the offsets complete, like murbnbr_of; murbhip's code
+int murbhost_sim_neighbours_of(void *p, float h, unsigned long *offsets, int *idx, unsigned long capacity)
+{
+    std::vector<unsigned long> o;
+    std::vector<int> i;
+    const int rc = static_cast<Sim *>(p)->sim->neighboursOf(h, o, i);
+    if (rc != 0) return rc;
+    std::copy(o.begin(), o.end(), offsets);
+    if (!idx) return 0;
+    if (i.size() > capacity) return -2000;   // MURBHIP_E_INVALID
+    std::copy(i.begin(), i.end(), idx);
+    return 0;
+}
 // --im hip+tracking+density: SimulationNBodyHIPTracking::setDensityCentre.  0, or -1 for a simulation without a history.
 int murbhost_sim_set_density_centre(void *p, int on)
 {

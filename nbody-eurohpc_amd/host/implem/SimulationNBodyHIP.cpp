@@ -6,6 +6,7 @@
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
+#include "murbnbr.h"
 #include "murbtidal.h"
 #include "murbtracer.h"
 
@@ -69,6 +70,17 @@ int SimulationNBodyHIP<T>::tidalAt(unsigned long count, const T *px, const T *py
 template <typename T> int SimulationNBodyHIP<T>::densityCentre(int k, double *out8)
 {
     return murbdensity_centre(hipBodiesPtr->getContext(), k, out8);
+}
+
+template <typename T> int SimulationNBodyHIP<T>::neighboursOf(float h, std::vector<unsigned long> &offsets, std::vector<int> &idx)
+{
+    const unsigned long n = this->getBodies()->getN();
+    offsets.assign(n + 1, 0ul);
+    idx.clear();
+    const int rc = murbnbr_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, h, offsets.data(), nullptr, nullptr, 0);
+    if (rc != 0 || offsets[n] == 0) return rc;
+    idx.resize(offsets[n]);
+    return murbnbr_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, h, offsets.data(), idx.data(), nullptr, idx.size());
 }
 
 template <typename T>

@@ -46,6 +46,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // A read-out like fieldAt; returns murbhip's code.
     int densityCentre(int k, double *out8);
 
+    // Neighbours within h of every body as the bodies are on the device, in CSR form (murbnbr_of's rules, include/murbnbr.h):
+    // offsets gets n + 1 entries, idx offsets[n]: body p's neighbours are idx[offsets[p] .. offsets[p + 1]) in ascending
+    // index.  The count-only call, then the sized one.  A read-out like fieldAt; returns murbhip's code.
+    int neighboursOf(float h, std::vector<unsigned long> &offsets, std::vector<int> &idx);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

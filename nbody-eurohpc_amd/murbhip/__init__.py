@@ -98,6 +98,14 @@ def lib():
         L.murbdensity_centre.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         L.murbknn_merge.argtypes = [C.c_int, _ip, _fp, _ip, _fp, _ip, _fp]
         L.murbknn_density.argtypes = [C.c_int, _ip, _fp, _fp, C.c_float, _fp]
+        # include/murbnbr.h
+        _up = C.POINTER(C.c_ulong)
+        L.murbnbr_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _fp, C.c_float, _up, _ip, _fp, C.c_ulong]
+        L.murbnbr_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [_ip, _fp, C.c_float, _up, _ip, _fp, C.c_ulong]
+        L.murbnbr_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
+        L.murbnbr_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
+        L.murbnbr_threshold.argtypes = [C.c_float, C.c_float, _fp]
+        L.murbnbr_cut.argtypes = [C.c_ulong, _up, C.c_ulong, C.c_ulong, _up]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -143,6 +151,8 @@ TRACER_EXPORTS = ("murbtracer_upload murbtracer_download murbtracer_download_for
 TRACER_OPTIONS = ("tracer_chunks", "tracer_batch", "tracer_dt")
 KNN_EXPORTS = "murbknn_of murbknn_at murbdensity_of murbdensity_centre murbknn_merge murbknn_density".split()   # include/murbknn.h
 KNN_KMAX = 32
+NBR_EXPORTS = "murbnbr_of murbnbr_at murbnbr_set_option murbnbr_get_option murbnbr_threshold murbnbr_cut".split()   # include/murbnbr.h
+NBR_OPTIONS = ("list_entries",)
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -254,6 +264,45 @@ def knn_density(idx, r2, masses, soft):
     _check(lib().murbknn_density(i.shape[0], i.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r), _ptr(m), float(np.float32(soft)), _ptr(out)),
            "murbknn_density")
     return out[0]
+
+
+def neighbour_threshold(h, soft):
+    """float32 thr = (float)((double)h * h + (double)soft2) of a radius and a softening length: body j is a neighbour if and only
+    if r2 <= thr (host only; include/murbnbr.h: murbnbr_threshold)."""
+    out = np.zeros(1, np.float32)
+    _check(lib().murbnbr_threshold(float(np.float32(h)), float(np.float32(soft)), _ptr(out)), "murbnbr_threshold")
+    return out[0]
+
+
+def neighbour_cut(offsets, first, entries):
+    """The furthest point `last` with offsets[last] - offsets[first] <= entries, at least first + 1: how the fill pass cuts a
+    launch's points into ranges (host only; include/murbnbr.h: murbnbr_cut)."""
+    o = np.ascontiguousarray(offsets, np.uint64)
+    last = C.c_ulong()
+    _check(lib().murbnbr_cut(max(o.shape[0] - 1, 0), o.ctypes.data_as(C.POINTER(C.c_ulong)), int(first), int(entries), C.byref(last)),
+           "murbnbr_cut")
+    return last.value
+
+
+def fof_groups(offsets, idx):
+    """int32 group label of each body from the neighbour lists of ALL n bodies at a common h (Simulation.neighbours_of(h=b)): the
+    smallest body index of its connected component under "j is listed for i": friends-of-friends groups at linking length b.
+    Host only, numpy: minimum propagation along the links and pointer jumping, to a fixed point."""
+    o = np.asarray(offsets, np.int64)
+    n = o.shape[0] - 1
+    j = np.asarray(idx, np.int64)
+    if j.shape != (int(o[-1]),):
+        raise ValueError("idx holds offsets[-1] entries")
+    i = np.repeat(np.arange(n, dtype=np.int64), np.diff(o))
+    label = np.arange(n, dtype=np.int64)
+    while True:
+        new = label.copy()
+        np.minimum.at(new, i, label[j])
+        np.minimum.at(new, j, label[i])   # a common h makes the relation symmetric; this costs nothing where it is
+        new = new[new]                    # pointer jumping: a label is a body, whose label is no larger
+        if np.array_equal(new, label):
+            return label.astype(np.int32)
+        label = new
 
 
 def _centre_dict(out):
@@ -539,6 +588,66 @@ class Simulation:
         _check(lib().murbdensity_centre(self._h, k, out), "murbdensity_centre")
         return _centre_dict(out[:])
 
+    # -- neighbours within a radius (include/murbnbr.h)
+    def _nbr_radii(self, h, count):
+        """(h array pointer or None, h_all) of a scalar or of one radius per point."""
+        if np.ndim(h) == 0:
+            return None, None, float(np.float32(h))
+        ha = _f32(h)
+        if ha.shape != (count,):
+            raise ValueError("h is a scalar or has one entry per point")
+        return ha, _ptr(ha), 0.0
+
+    def _nbr_call(self, name, head, count, lists):
+        """The count-only call, then the call sized from its offsets."""
+        fn = getattr(lib(), name)
+        up = C.POINTER(C.c_ulong)
+        offsets = np.zeros(count + 1, np.uint64)
+        _check(fn(*head, offsets.ctypes.data_as(up), None, None, 0), name)
+        if not lists:
+            return offsets, None, None
+        total = int(offsets[count])
+        idx, r2 = np.zeros(total, np.int32), np.zeros(total, np.float32)
+        if total:
+            _check(fn(*head, offsets.ctypes.data_as(up), idx.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r2), total), name)
+        return offsets, idx, r2
+
+    def neighbours_of(self, bodies=None, h=0.0, lists=True):
+        """(offsets (count + 1) uint64, idx int32, r2 float32): the other bodies within h (a scalar, or one radius per listed body)
+        of the listed bodies (None: all, in order), in CSR form: body p's neighbours are idx[offsets[p]:offsets[p + 1]] in
+        ascending index, r2 the sweeps' |d|^2 + soft^2, a neighbour having r2 <= neighbour_threshold(h, soft)
+        (include/murbnbr.h: murbnbr_of).  lists=False: the counts alone, (offsets, None, None).  A read-out: synchronous,
+        changes nothing of the simulation."""
+        count, bp = self._knn_bodies(bodies)
+        keep, hp, h_all = self._nbr_radii(h, count)
+        return self._nbr_call("murbnbr_of", (self._h, count, bp, hp, h_all), count, lists)
+
+    def neighbours_at(self, points, h, skip=None, lists=True):
+        """neighbours_of at `points` (3, count) of the caller's, with body skip[p] (or none: -1, or skip=None) no candidate of
+        point p (include/murbnbr.h: murbnbr_at)."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        keep, hp, h_all = self._nbr_radii(h, count)
+        head = (self._h, count, *[_ptr(x) for x in p], sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, hp, h_all)
+        return self._nbr_call("murbnbr_at", head, count, lists)
+
+    def set_neighbour_option(self, key, value):
+        """"list_entries" of neighbours_of() and neighbours_at() (include/murbnbr.h: murbnbr_set_option)."""
+        _check(lib().murbnbr_set_option(self._h, key.encode(), int(value)), f"murbnbr_set_option({key})")
+
+    def neighbour_option(self, key):
+        """The value of a neighbour option in force, defaults resolved (include/murbnbr.h: murbnbr_get_option)."""
+        f = C.c_long()
+        _check(lib().murbnbr_get_option(self._h, key.encode(), C.byref(f)), f"murbnbr_get_option({key})")
+        return f.value
+
     # -- massless tracers (include/murbtracer.h)
     def upload_tracers(self, q, v=None):
         """`q` (3, count) positions and `v` (3, count; None = at rest) velocities of massless test particles at the bodies'
@@ -770,6 +879,7 @@ def host_lib():
         H.murbhost_sim_tidal_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [C.POINTER(C.c_int)] + [_fp] * 6
         H.murbhost_sim_density_centre.argtypes = [C.c_void_p, C.c_int, _dp]
         H.murbhost_sim_set_density_centre.argtypes = [C.c_void_p, C.c_int]
+        H.murbhost_sim_neighbours_of.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong), C.POINTER(C.c_int), C.c_ulong]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -914,6 +1024,18 @@ class HostSim:
         out = (C.c_double * 8)()
         _check(self.H.murbhost_sim_density_centre(self.h, k, out), "murbhost_sim_density_centre")
         return _centre_dict(out[:])
+
+    def neighbours_of(self, h):
+        """SimulationNBodyHIP::neighboursOf: (offsets, idx) of Simulation.neighbours_of(h=h) for all of the plugin's bodies as they
+        are on the device."""
+        up, ip = C.POINTER(C.c_ulong), C.POINTER(C.c_int)
+        offsets = np.zeros(self.n + 1, np.uint64)
+        _check(self.H.murbhost_sim_neighbours_of(self.h, float(np.float32(h)), offsets.ctypes.data_as(up), None, 0), "murbhost_sim_neighbours_of")
+        idx = np.zeros(int(offsets[self.n]), np.int32)
+        if idx.size:
+            _check(self.H.murbhost_sim_neighbours_of(self.h, float(np.float32(h)), offsets.ctypes.data_as(up), idx.ctypes.data_as(ip), idx.size),
+                   "murbhost_sim_neighbours_of")
+        return offsets, idx
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
