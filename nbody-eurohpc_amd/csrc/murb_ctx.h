@@ -16,6 +16,7 @@
 #include "murb_kernels_tracer.h"  // likewise
 #include "murb_kernels_knn.h"     // likewise
 #include "murb_kernels_nbr.h"     // likewise
+#include "murb_kernels_bind.h"    // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -150,6 +151,21 @@ struct Shard {
     int* nbr_idx = nullptr;              // the list buffer ("list_entries"): nbr_list entries of indices ...
     float* nbr_r2 = nullptr;             // ... and of r2
     size_t nbr_list = 0;
+    // bound pairs (include/murbbind.h): the packed points go through the field read-out's fld_pts like the knn read-out's; the
+    // uploaded planes, rows and results are its own, allocated on first use and grown
+    float* bnd_in = nullptr;        // a launch's uploaded points: 7 planes of floats and one of ints (skip entries or bodies)
+    size_t bnd_ins = 0;             // floats it holds
+    uint2* bnd_part = nullptr;      // the chunks' (key, index): bnd_parts entries
+    size_t bnd_parts = 0;
+    int* bnd_idx = nullptr;         // partners: of a launch's points, or of all bodies (murbbind_pairs); bnd_points entries ...
+    float* bnd_h = nullptr;         // ... and their h
+    size_t bnd_points = 0;
+    double* bnd_elems = nullptr;    // murbbind_pairs: 6 doubles per body, bnd_elem doubles ...
+    size_t bnd_elem = 0;
+    int* bnd_flag = nullptr;        // ... which bodies hold a pair: bnd_flags entries ...
+    size_t bnd_flags = 0;
+    double* bnd_sums = nullptr;     // ... and the block rows of murb_bind_pairs_kernel: bnd_rows doubles
+    size_t bnd_rows = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -195,6 +211,7 @@ enum ProfKind {
     kProfTracer,          // compute stream: a sweep launch of the tracers (murbtracer.h); never part of the force figures
     kProfKnn,             // compute stream: a sweep launch of the neighbour read-out (murbknn.h); never part of the force figures
     kProfNbr,             // compute stream: a count or fill sweep launch of the radius read-out (murbnbr.h); never part of the force figures
+    kProfBind,            // compute stream: a sweep launch of the bound-pair read-out (murbbind.h); never part of the force figures
     kProfKinds
 };
 

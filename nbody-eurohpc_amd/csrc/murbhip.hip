@@ -39,6 +39,7 @@
 #include "../../include/murbhip.h"
 #include "../../include/murbfield.h"
 #include "../../include/murbtidal.h"
+#include "../../include/murbbind.h"
 #include "../../include/murbknn.h"
 #include "../../include/murbnbr.h"
 #include "../../include/murbtracer.h"
@@ -1801,6 +1802,142 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
     return 0;
 }
 
+// ---- bound pairs (include/murbbind.h; kernels: murb_kernels_bind.h, the elements: murb_bind.h) ----------------------------
+// knn_run's planning, batching, grid and packed-point buffer with one (partner, h) per point in the place of the list.
+// p: the seven input planes px py pz pvx pvy pvz gm (murbbind_at; p[3..5] null: at rest, p[6] null: massless) or all null (of
+// bodies: idx lists them, or null for all n in order).  out_idx, out_h: host arrays, null where not asked for; all: the
+// results stay on the device, bnd_idx / bnd_h [body] (murbbind_pairs; all bodies in order).
+int bind_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[7], const int* idx, bool of_bodies, int* out_idx, float* out_h,
+             bool all)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, 0));
+    {   // partners and h grow together: they share one size
+        size_t h_points = sh.bnd_points;
+        RC_TRY(grow(sh, sh.bnd_in, sh.bnd_ins, 8 * cap));
+        RC_TRY(grow(sh, sh.bnd_part, sh.bnd_parts, cap * (size_t)l.chunks));
+        RC_TRY(grow(sh, sh.bnd_h, h_points, all ? std::max<size_t>(count, cap) : cap));
+        RC_TRY(grow(sh, sh.bnd_idx, sh.bnd_points, all ? std::max<size_t>(count, cap) : cap));
+    }
+    const bool has_vel = p[3] != nullptr, has_gm = p[6] != nullptr;
+    std::vector<float> host(7 * cap, 0.f);
+    std::vector<int> every;
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            for (int e = 0; e < 7; ++e)
+                if (p[e]) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.bnd_in, host.data(), 7 * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        const int* list = idx ? idx + first : nullptr;
+        if (of_bodies && !idx) {   // all bodies in order
+            every.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
+            list = every.data();
+        }
+        if (list) HIP_TRY(hipMemcpy(sh.bnd_in + 7 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbBindPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.bnd_in;
+        pa.idx = list ? (const int*)(sh.bnd_in + 7 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = has_vel ? 1 : 0;
+        pa.has_gm = has_gm ? 1 : 0;
+        hipLaunchKernelGGL(murb_bind_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbBindArgs ba{};
+        ba.rec = sh.rec[c->cur];
+        ba.vel = sh.vel;
+        ba.pts = sh.fld_pts;
+        ba.part = sh.bnd_part;
+        ba.groups = (int)(padded / MURB_FIELD_GROUP);
+        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a minimum does not depend on the cut
+        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
+        ba.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + ba.groups - 1) / ba.groups));
+        ba.tiles_each = l.tiles / ba.chunks;   // chunks <= tiles: every chunk holds a tile
+        ba.tiles_more = l.tiles % ba.chunks;
+        ba.count = (int)c->in.n;
+        ba.stride = (unsigned int)padded;   // chunks * padded <= bnd_parts
+        ba.soft2 = c->soft2;
+        const long units = (long)ba.groups * ba.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfBind, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_bind_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                           sh.compute, ba);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        int* const res_idx = sh.bnd_idx + (all ? first : 0ul);
+        float* const res_h = sh.bnd_h + (all ? first : 0ul);
+        hipLaunchKernelGGL(murb_bind_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)ba.part,
+                           res_idx, res_h, (int)bn, ba.chunks, ba.stride);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first, res_idx, bn * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_h) HIP_TRY(hipMemcpy(out_h + first, res_h, bn * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// The sweep over all bodies, then one thread per body: the elements of the bound pairs in dense per-body arrays, compacted
+// here in index order, and the census.  pi, pj, elems: all set (capacity pairs each) or all null.
+int bind_pairs(murbhip_ctx* c, int* pi, int* pj, double* elems, unsigned long capacity, unsigned long* count, double* out8)
+{
+    const float* const none[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const unsigned long n = c->in.n;
+    RC_TRY(bind_run(c, n, none, nullptr, true, nullptr, nullptr, true));
+    Shard& sh = c->shards[0];
+    const size_t blocks = (n + 255) / 256;
+    RC_TRY(grow(sh, sh.bnd_flag, sh.bnd_flags, (size_t)n));
+    RC_TRY(grow(sh, sh.bnd_sums, sh.bnd_rows, blocks * MURB_BIND_SUMS));
+    RC_TRY(grow(sh, sh.bnd_elems, sh.bnd_elem, (size_t)n * MURB_BIND_ELEMS));
+    hipLaunchKernelGGL(murb_bind_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float4*)sh.rec[c->cur],
+                       (const float4*)sh.vel, (const float*)sh.mass, (const int*)sh.bnd_idx, (const float*)sh.bnd_h, sh.bnd_elems,
+                       sh.bnd_flag, sh.bnd_sums, (int)n, c->soft2);
+    RC_TRY(hip_rc(hipGetLastError()));
+    std::vector<double> rows(blocks * MURB_BIND_SUMS), dense(n * MURB_BIND_ELEMS);
+    std::vector<int> flag(n), partner(n);
+    HIP_TRY(hipMemcpyAsync(rows.data(), sh.bnd_sums, rows.size() * sizeof(double), hipMemcpyDeviceToHost, sh.compute));
+    HIP_TRY(hipMemcpyAsync(flag.data(), sh.bnd_flag, n * sizeof(int), hipMemcpyDeviceToHost, sh.compute));
+    HIP_TRY(hipMemcpyAsync(partner.data(), sh.bnd_idx, n * sizeof(int), hipMemcpyDeviceToHost, sh.compute));
+    HIP_TRY(hipMemcpyAsync(dense.data(), sh.bnd_elems, dense.size() * sizeof(double), hipMemcpyDeviceToHost, sh.compute));
+    HIP_TRY(hipStreamSynchronize(sh.compute));
+    double s[MURB_BIND_SUMS] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t b = 0; b < blocks; ++b)
+        for (int e = 0; e < MURB_BIND_SUMS; ++e) s[e] += rows[b * MURB_BIND_SUMS + e];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    double hard_i = nan, hard_j = nan, hard_e = nan, least_a = nan;
+    unsigned long pairs = 0;
+    for (unsigned long i = 0; i < n; ++i) {
+        if (!flag[i]) continue;
+        const double* const e = dense.data() + i * MURB_BIND_ELEMS;
+        if (pairs == 0 || e[4] < hard_e) { hard_i = (double)i; hard_j = (double)partner[i]; hard_e = e[4]; }   // the lowest i among equals
+        if (pairs == 0 || e[0] < least_a) least_a = e[0];
+        ++pairs;
+    }
+    *count = pairs;
+    out8[0] = s[0]; out8[1] = s[1]; out8[2] = hard_i; out8[3] = hard_j; out8[4] = hard_e; out8[5] = least_a; out8[6] = s[2]; out8[7] = s[3];
+    if (!pi) return 0;
+    if (capacity < pairs) return MURBHIP_E_INVALID;
+    unsigned long at = 0;
+    for (unsigned long i = 0; i < n; ++i) {
+        if (!flag[i]) continue;
+        pi[at] = (int)i;
+        pj[at] = partner[i];
+        std::memcpy(elems + at * MURB_BIND_ELEMS, dense.data() + i * MURB_BIND_ELEMS, MURB_BIND_ELEMS * sizeof(double));
+        ++at;
+    }
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2011,6 +2148,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.trc_state, sh.trc_pts, sh.trc_part);
         release(sh.knn_part_r2, sh.knn_part_idx, sh.knn_list_r2, sh.knn_list_idx, sh.knn_rho, sh.knn_sums);
         release(sh.nbr_part, sh.nbr_counts, sh.nbr_base, sh.nbr_idx, sh.nbr_r2);
+        release(sh.bnd_in, sh.bnd_part, sh.bnd_idx, sh.bnd_h, sh.bnd_elems, sh.bnd_flag, sh.bnd_sums);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2526,6 +2664,63 @@ int murbknn_density(int k, const int* idx, const float* r2, const float* masses,
     return 0;
 }
 
+// ---- include/murbbind.h
+int murbbind_of(murbhip_ctx* c, unsigned long count, const int* bodies, int* partner, float* h)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!bodies && count != c->in.n) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return bind_run(c, count, p, bodies, true, partner, h, false);
+}
+
+int murbbind_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const float* pvx,
+                const float* pvy, const float* pvz, const float* m, const int* skip, int* partner, float* h)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz})) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz, pvx, pvy, pvz})
+        for (unsigned long i = 0; q && i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; m && i < count; ++i)
+        if (!std::isfinite(m[i]) || m[i] < 0.f) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    std::vector<float> gm;
+    if (m) {
+        gm.resize(count);
+        for (unsigned long i = 0; i < count; ++i) gm[i] = c->g * m[i];   // the upload's one fp32 multiply (pack_records)
+    }
+    const float* const p[7] = {px, py, pz, pvx, pvy, pvz, m ? gm.data() : nullptr};
+    return bind_run(c, count, p, skip, false, partner, h, false);
+}
+
+int murbbind_pairs(murbhip_ctx* c, int* i, int* j, double* elems, unsigned long capacity, unsigned long* count, double* out8)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    RC_TRY(field_state(c));
+    if (!count || !out8 || !all_or_none({i, j, elems})) return MURBHIP_E_INVALID;
+    return bind_pairs(c, i, j, elems, capacity, count, out8);
+}
+
+int murbbind_elements(float g, float soft, const float* qi, const float* vi, float mi, const float* qj, const float* vj, float mj,
+                      double* out6)
+{
+    if (!qi || !vi || !qj || !vj || !out6) return MURBHIP_E_INVALID;
+    for (const float* q : {qi, vi, qj, vj})
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(q[k])) return MURBHIP_E_INVALID;
+    for (const float v : {g, soft, mi, mj})
+        if (!std::isfinite(v) || v < 0.f) return MURBHIP_E_INVALID;
+    murb_bind_elements(soft * soft, qi, vi, g * mi, mi, qj, vj, g * mj, mj, out6);
+    return 0;
+}
+
 // ---- include/murbnbr.h
 namespace {
 // the radii of a call, checked, as thresholds; false: a radius that is negative or not finite
@@ -2930,7 +3125,10 @@ int murbhip_block_set_levels(murbhip_ctx* c, const int* levels, int kmax)
     RC_TRY(ensure_block(c, sh));
     RC_TRY(murbhip_sync(c));
     HIP_TRY(hipMemcpy(sh.blk_levels, levels, c->in.n * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(sh.blk_ticks, 0, c->in.slots * sizeof(unsigned int)));
+    // on the compute stream, and waited for: a fill on the null stream returns before it has run, and the compute stream
+    // (non-blocking) does not wait for that stream, so the next call's first launches could still read the ticks of the last block
+    HIP_TRY(hipMemsetAsync(sh.blk_ticks, 0, c->in.slots * sizeof(unsigned int), sh.compute));
+    HIP_TRY(hipStreamSynchronize(sh.compute));
     c->blk_have_levels = 2;
     c->blk_kmax = kmax;
     return 0;
@@ -3310,10 +3508,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr
+        //                                 tracer, knn, nbr, bind
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -247,6 +247,22 @@ int murbhost_sim_neighbours_of(void *p, float h, unsigned long *offsets, int *id
     std::copy(i.begin(), i.end(), idx);
     return 0;
 }
+// SimulationNBodyHIP::binaries: *count and out8 always; i, j (capacity entries) and elems (6 * capacity) where they are given and
+// hold the pairs, else MURBHIP_E_INVALID (-2000) with *count and out8 filled, like murbbind_pairs; murbhip's code
+int murbhost_sim_binaries(void *p, int *i, int *j, double *elems, unsigned long capacity, unsigned long *count, double *out8)
+{
+    std::vector<int> vi, vj;
+    std::vector<double> ve;
+    const int rc = static_cast<Sim *>(p)->sim->binaries(vi, vj, ve, out8);
+    if (rc != 0) return rc;
+    *count = vi.size();
+    if (!i) return 0;
+    if (capacity < vi.size()) return -2000;
+    std::copy(vi.begin(), vi.end(), i);
+    std::copy(vj.begin(), vj.end(), j);
+    std::copy(ve.begin(), ve.end(), elems);
+    return 0;
+}
 // --im hip+tracking+density: SimulationNBodyHIPTracking::setDensityCentre.  0, or -1 for a simulation without a history.
 int murbhost_sim_set_density_centre(void *p, int on)
 {

@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "murbbind.h"
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
@@ -81,6 +82,21 @@ template <typename T> int SimulationNBodyHIP<T>::neighboursOf(float h, std::vect
     if (rc != 0 || offsets[n] == 0) return rc;
     idx.resize(offsets[n]);
     return murbnbr_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, h, offsets.data(), idx.data(), nullptr, idx.size());
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::binaries(std::vector<int> &i, std::vector<int> &j, std::vector<double> &elems, double *out8)
+{
+    unsigned long pairs = 0;
+    i.clear();
+    j.clear();
+    elems.clear();
+    const int rc = murbbind_pairs(hipBodiesPtr->getContext(), nullptr, nullptr, nullptr, 0, &pairs, out8);
+    if (rc != 0 || pairs == 0) return rc;
+    i.resize(pairs);
+    j.resize(pairs);
+    elems.resize(6 * pairs);
+    return murbbind_pairs(hipBodiesPtr->getContext(), i.data(), j.data(), elems.data(), pairs, &pairs, out8);
 }
 
 template <typename T>

@@ -51,6 +51,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // index.  The count-only call, then the sized one.  A read-out like fieldAt; returns murbhip's code.
     int neighboursOf(float h, std::vector<unsigned long> &offsets, std::vector<int> &idx);
 
+    // Bound pairs of the bodies as they are on the device (murbbind_pairs' rules, include/murbbind.h): the mutual pairs whose
+    // sweep value h < 0, i < j ascending in i, with six doubles a pair in elems {a, e, P, h64, E_b, r}, and the census out8.
+    // The count-only call, then the sized one.  A read-out like fieldAt; returns murbhip's code.
+    int binaries(std::vector<int> &i, std::vector<int> &j, std::vector<double> &elems, double *out8);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

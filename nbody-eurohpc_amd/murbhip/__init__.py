@@ -106,6 +106,12 @@ def lib():
         L.murbnbr_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
         L.murbnbr_threshold.argtypes = [C.c_float, C.c_float, _fp]
         L.murbnbr_cut.argtypes = [C.c_ulong, _up, C.c_ulong, C.c_ulong, _up]
+        # include/murbbind.h
+        _dp = C.POINTER(C.c_double)
+        L.murbbind_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _ip, _fp]
+        L.murbbind_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 7 + [_ip, _ip, _fp]
+        L.murbbind_pairs.argtypes = [C.c_void_p, _ip, _ip, _dp, C.c_ulong, _up, _dp]
+        L.murbbind_elements.argtypes = [C.c_float, C.c_float, _fp, _fp, C.c_float, _fp, _fp, C.c_float, _dp]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -153,6 +159,9 @@ KNN_EXPORTS = "murbknn_of murbknn_at murbdensity_of murbdensity_centre murbknn_m
 KNN_KMAX = 32
 NBR_EXPORTS = "murbnbr_of murbnbr_at murbnbr_set_option murbnbr_get_option murbnbr_threshold murbnbr_cut".split()   # include/murbnbr.h
 NBR_OPTIONS = ("list_entries",)
+BIND_EXPORTS = "murbbind_of murbbind_at murbbind_pairs murbbind_elements".split()   # include/murbbind.h
+BIND_ELEMENT_KEYS = ("a", "e", "period", "h", "energy", "r")
+BIND_CENSUS_KEYS = ("pairs", "energy_sum", "hardest_i", "hardest_j", "hardest_energy", "a_min", "bound_bodies", "mutual_pairs")
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -264,6 +273,30 @@ def knn_density(idx, r2, masses, soft):
     _check(lib().murbknn_density(i.shape[0], i.ctypes.data_as(C.POINTER(C.c_int)), _ptr(r), _ptr(m), float(np.float32(soft)), _ptr(out)),
            "murbknn_density")
     return out[0]
+
+
+def binary_elements(g, soft, qi, vi, mi, qj, vj, mj):
+    """dict of the two-body elements a, e, period, h, energy, r (float64) of one pair from its float32 state: positions and
+    velocities of three floats each, masses, G and the softening length (host only; include/murbbind.h: murbbind_elements)."""
+    q = [_f32(x) for x in (qi, vi, qj, vj)]
+    if any(x.shape != (3,) for x in q):
+        raise ValueError("positions and velocities have three components")
+    out = (C.c_double * 6)()
+    _check(lib().murbbind_elements(float(np.float32(g)), float(np.float32(soft)), _ptr(q[0]), _ptr(q[1]), float(np.float32(mi)),
+                                   _ptr(q[2]), _ptr(q[3]), float(np.float32(mj)), out), "murbbind_elements")
+    return dict(zip(BIND_ELEMENT_KEYS, out[:]))
+
+
+def _binaries_dict(i, j, elems, out8):
+    d = {"i": i, "j": j}
+    for k, key in enumerate(BIND_ELEMENT_KEYS):
+        d[key] = np.ascontiguousarray(elems[:, k])
+    d["census"] = dict(zip(BIND_CENSUS_KEYS, out8))
+    for key in ("pairs", "bound_bodies", "mutual_pairs"):
+        d["census"][key] = int(d["census"][key])
+    for key in ("hardest_i", "hardest_j"):
+        d["census"][key] = int(d["census"][key]) if d["census"][key] == d["census"][key] else -1
+    return d
 
 
 def neighbour_threshold(h, soft):
@@ -588,6 +621,61 @@ class Simulation:
         _check(lib().murbdensity_centre(self._h, k, out), "murbdensity_centre")
         return _centre_dict(out[:])
 
+    # -- bound pairs (include/murbbind.h)
+    def bound_partner_of(self, bodies=None):
+        """(partner int32, h float32) of the listed bodies (None: all, in order): the other body with the smallest specific
+        two-body energy h = w^2 / 2 - G (m_i + m_j) / sqrt(d^2 + soft^2) by (h, index); -1 / +inf where there is none
+        (include/murbbind.h: murbbind_of).  A read-out: synchronous, changes nothing of the simulation."""
+        count, bp = self._knn_bodies(bodies)
+        partner, h = np.full(count, -1, np.int32), np.full(count, np.inf, np.float32)
+        _check(lib().murbbind_of(self._h, count, bp, partner.ctypes.data_as(C.POINTER(C.c_int)), _ptr(h)), "murbbind_of")
+        return partner, h
+
+    def bound_partner_at(self, points, velocities=None, masses=None, skip=None):
+        """bound_partner_of for probes of the caller's at `points` (3, count) with `velocities` (3, count; None: at rest) and
+        `masses` (count; None: massless), with body skip[p] (or none: -1, or skip=None) no candidate of point p
+        (include/murbbind.h: murbbind_at)."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        v = [None] * 3
+        if velocities is not None:
+            v = [_f32(x) for x in velocities]
+            if len(v) != 3 or any(x.shape != (count,) for x in v):
+                raise ValueError("velocities are three arrays, one entry per point")
+        m = None
+        if masses is not None:
+            m = _f32(masses)
+            if m.shape != (count,):
+                raise ValueError("masses has one entry per point")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        partner, h = np.full(count, -1, np.int32), np.full(count, np.inf, np.float32)
+        opt = lambda x: _ptr(x) if x is not None else None
+        _check(lib().murbbind_at(self._h, count, *[_ptr(x) for x in p], *[opt(x) for x in v], opt(m),
+                                 sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                 partner.ctypes.data_as(C.POINTER(C.c_int)), _ptr(h)), "murbbind_at")
+        return partner, h
+
+    def binaries(self):
+        """dict of the bound pairs (mutual most bound partners with h < 0), i < j ascending in i: arrays i, j (int32) and a, e,
+        period, h, energy, r (float64, from the float32 state), plus "census": pairs, energy_sum, hardest_i, hardest_j,
+        hardest_energy, a_min, bound_bodies (bodies whose partner has h < 0, mutual or not), mutual_pairs
+        (include/murbbind.h: murbbind_pairs).  The count-only call, then the sized one."""
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        count, out8 = C.c_ulong(), (C.c_double * 8)()
+        _check(lib().murbbind_pairs(self._h, None, None, None, 0, C.byref(count), out8), "murbbind_pairs")
+        pairs = int(count.value)
+        i, j, elems = np.zeros(pairs, np.int32), np.zeros(pairs, np.int32), np.zeros((pairs, 6), np.float64)
+        if pairs:
+            _check(lib().murbbind_pairs(self._h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), elems.ctypes.data_as(dp), pairs,
+                                        C.byref(count), out8), "murbbind_pairs")
+        return _binaries_dict(i, j, elems, out8[:])
+
     # -- neighbours within a radius (include/murbnbr.h)
     def _nbr_radii(self, h, count):
         """(h array pointer or None, h_all) of a scalar or of one radius per point."""
@@ -880,6 +968,7 @@ def host_lib():
         H.murbhost_sim_density_centre.argtypes = [C.c_void_p, C.c_int, _dp]
         H.murbhost_sim_set_density_centre.argtypes = [C.c_void_p, C.c_int]
         H.murbhost_sim_neighbours_of.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong), C.POINTER(C.c_int), C.c_ulong]
+        H.murbhost_sim_binaries.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.c_ulong, C.POINTER(C.c_ulong), _dp]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1036,6 +1125,18 @@ class HostSim:
             _check(self.H.murbhost_sim_neighbours_of(self.h, float(np.float32(h)), offsets.ctypes.data_as(up), idx.ctypes.data_as(ip), idx.size),
                    "murbhost_sim_neighbours_of")
         return offsets, idx
+
+    def binaries(self):
+        """SimulationNBodyHIP::binaries: Simulation.binaries() for the plugin's bodies as they are on the device."""
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        count, out8 = C.c_ulong(), (C.c_double * 8)()
+        _check(self.H.murbhost_sim_binaries(self.h, None, None, None, 0, C.byref(count), out8), "murbhost_sim_binaries")
+        pairs = int(count.value)
+        i, j, elems = np.zeros(pairs, np.int32), np.zeros(pairs, np.int32), np.zeros((pairs, 6), np.float64)
+        if pairs:
+            _check(self.H.murbhost_sim_binaries(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), elems.ctypes.data_as(dp), pairs,
+                                                C.byref(count), out8), "murbhost_sim_binaries")
+        return _binaries_dict(i, j, elems, out8[:])
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
