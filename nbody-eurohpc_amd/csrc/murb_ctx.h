@@ -17,6 +17,7 @@
 #include "murb_kernels_knn.h"     // likewise
 #include "murb_kernels_nbr.h"     // likewise
 #include "murb_kernels_bind.h"    // likewise
+#include "murb_kernels_pot.h"     // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -166,6 +167,22 @@ struct Shard {
     size_t bnd_flags = 0;
     double* bnd_sums = nullptr;     // ... and the block rows of murb_bind_pairs_kernel: bnd_rows doubles
     size_t bnd_rows = 0;
+    // potential read-out and bound members (include/murbbound.h): the packed points go through the field read-out's fld_pts like the
+    // knn read-out's; the uploaded planes, the masked records, rows and results are its own, allocated on first use and grown
+    float* pot_in = nullptr;        // a launch's uploaded points: 3 planes of floats and one of ints (skip entries or bodies)
+    size_t pot_ins = 0;             // floats it holds
+    float4* pot_rec = nullptr;      // the masked copy of the position + G m records: pot_recs records
+    size_t pot_recs = 0;
+    unsigned char* pot_member = nullptr;   // the mask, one byte per body: pot_members bytes
+    size_t pot_members = 0;
+    float* pot_part = nullptr;      // the chunks' rows: pot_parts floats
+    size_t pot_parts = 0;
+    float* pot_phi = nullptr;       // phi: of a launch's points, or of all bodies (murbbound_members); pot_phis floats
+    size_t pot_phis = 0;
+    double* pot_e = nullptr;        // murbbound_members: e per body, pot_es doubles ...
+    size_t pot_es = 0;
+    double* pot_rows = nullptr;     // ... and the block rows of its two kernels: pot_row doubles
+    size_t pot_row = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -212,6 +229,7 @@ enum ProfKind {
     kProfKnn,             // compute stream: a sweep launch of the neighbour read-out (murbknn.h); never part of the force figures
     kProfNbr,             // compute stream: a count or fill sweep launch of the radius read-out (murbnbr.h); never part of the force figures
     kProfBind,            // compute stream: a sweep launch of the bound-pair read-out (murbbind.h); never part of the force figures
+    kProfPot,             // compute stream: a sweep launch of the potential read-out (murbbound.h); never part of the force figures
     kProfKinds
 };
 

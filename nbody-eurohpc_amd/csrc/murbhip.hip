@@ -40,6 +40,7 @@
 #include "../../include/murbfield.h"
 #include "../../include/murbtidal.h"
 #include "../../include/murbbind.h"
+#include "../../include/murbbound.h"
 #include "../../include/murbknn.h"
 #include "../../include/murbnbr.h"
 #include "../../include/murbtracer.h"
@@ -1938,6 +1939,190 @@ int bind_pairs(murbhip_ctx* c, int* pi, int* pj, double* elems, unsigned long ca
     return 0;
 }
 
+// ---- potential read-out and bound members (include/murbbound.h; kernels: murb_kernels_pot.h, the arithmetic: murb_bound.h) ----
+// The masked copy of the records from the mask on the device (pot_member): the sweep's j side under a mask.
+int pot_mask(murbhip_ctx* c, Shard& sh)
+{
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const size_t records = (size_t)l.tiles * MURB_TILE_F4;   // the tiles that hold real bodies: all the sweep reads
+    RC_TRY(grow(sh, sh.pot_rec, sh.pot_recs, records));
+    hipLaunchKernelGGL(murb_pot_mask_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, sh.compute,
+                       (const float4*)sh.rec[c->cur], (const unsigned char*)sh.pot_member, sh.pot_rec, (int)c->in.n, (unsigned int)records);
+    return hip_rc(hipGetLastError());
+}
+
+int pot_upload_mask(murbhip_ctx* c, Shard& sh, const unsigned char* member)
+{
+    RC_TRY(grow(sh, sh.pot_member, sh.pot_members, (size_t)c->in.n));
+    HIP_TRY(hipMemcpy(sh.pot_member, member, c->in.n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// knn_run's planning, batching, grid and packed-point buffer with one float per point in the place of the list.  p: the three
+// position planes (murbpot_at) or all null (of bodies: idx lists them, or null for all n in order).  masked: the j side is the
+// masked copy (pot_mask has run on the compute stream).  out: a host array, or null; all: the results stay on the device,
+// pot_phi[body] (murbbound_members; all bodies in order).
+int pot_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, bool masked, float* out,
+            bool all)
+{
+    Shard& sh = c->shards[0];
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, 0));
+    RC_TRY(grow(sh, sh.pot_in, sh.pot_ins, 4 * cap));
+    RC_TRY(grow(sh, sh.pot_part, sh.pot_parts, cap * (size_t)l.chunks));
+    RC_TRY(grow(sh, sh.pot_phi, sh.pot_phis, all ? std::max<size_t>(count, cap) : cap));
+    std::vector<float> host(3 * cap, 0.f);
+    std::vector<int> every;
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.pot_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        const int* list = idx ? idx + first : nullptr;
+        if (of_bodies && !idx) {   // all bodies in order
+            every.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
+            list = every.data();
+        }
+        if (list) HIP_TRY(hipMemcpy(sh.pot_in + 3 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.pot_in;
+        pa.idx = list ? (const int*)(sh.pot_in + 3 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbPotArgs ta{};
+        ta.rec = masked ? sh.pot_rec : sh.rec[c->cur];
+        ta.pts = sh.fld_pts;
+        ta.part = sh.pot_part;
+        ta.groups = (int)(padded / MURB_FIELD_GROUP);
+        ta.chunks = l.chunks;   // the field read-out's cut: a sum depends on it
+        ta.tiles = l.tiles;
+        ta.stride = (unsigned int)padded;   // chunks * padded <= pot_parts
+        ta.soft2 = c->soft2;
+        const long units = (long)ta.groups * ta.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // field_run's: 4 workgroups per CU
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfPot, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_pot_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute,
+                           ta);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        float* const res = sh.pot_phi + (all ? first : 0ul);
+        hipLaunchKernelGGL(murb_pot_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const float*)ta.part, res,
+                           (int)bn, ta.chunks, ta.stride);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (out) HIP_TRY(hipMemcpy(out + first, res, bn * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// murbpot_of / murbpot_at once their arguments are checked
+int pot_call(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const unsigned char* member,
+             float* phi)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    if (member) {
+        RC_TRY(pot_upload_mask(c, sh, member));
+        RC_TRY(pot_mask(c, sh));
+    }
+    return pot_run(c, count, p, idx, of_bodies, member != nullptr, phi, false);
+}
+
+// The rounds of include/murbbound.h, 2.  Every round sweeps all bodies against the masked records, so the evaluation of the
+// round that converges is the final pass.
+int bound_members(murbhip_ctx* c, const unsigned char* start, const double* frame_v, int max_iter, unsigned char* member, double* e,
+                  double* out16)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const unsigned long n = c->in.n;
+    const size_t blocks = (n + 255) / 256;
+    const float* const none[3] = {nullptr, nullptr, nullptr};
+    RC_TRY(grow(sh, sh.pot_e, sh.pot_es, (size_t)n));
+    RC_TRY(grow(sh, sh.pot_rows, sh.pot_row, blocks * (MURB_BOUND_SUMS + 1)));
+    {
+        std::vector<unsigned char> s0(n, 1);   // 0 / 1: the bytes go back to the caller as they are
+        for (unsigned long i = 0; start && i < n; ++i) s0[i] = start[i] ? 1 : 0;
+        RC_TRY(pot_upload_mask(c, sh, s0.data()));
+    }
+    double* const sums_dev = sh.pot_rows;
+    double* const removed_dev = sh.pot_rows + blocks * MURB_BOUND_SUMS;
+    std::vector<double> rows(blocks * (MURB_BOUND_SUMS + 1));
+    double s[MURB_BOUND_SUMS + 1], V[3] = {0.0, 0.0, 0.0};
+    // the sums of the set on the device (with_energy: K, m phi and the bodies with e >= 0 too), the block rows added in index
+    // order; the rows of the energy kernel before it come along in the same copy
+    const auto sums = [&](bool with_energy, bool with_removed) -> int {
+        hipLaunchKernelGGL(murb_bound_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float4*)sh.rec[c->cur],
+                           (const float4*)sh.vel, (const float*)sh.mass, (const unsigned char*)sh.pot_member, (const float*)sh.pot_phi,
+                           (const double*)sh.pot_e, sums_dev, (int)n, with_energy ? 1 : 0, V[0], V[1], V[2]);
+        RC_TRY(hip_rc(hipGetLastError()));
+        const size_t take = blocks * (MURB_BOUND_SUMS + (with_removed ? 1 : 0));
+        HIP_TRY(hipMemcpyAsync(rows.data(), sh.pot_rows, take * sizeof(double), hipMemcpyDeviceToHost, sh.compute));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        for (int k = 0; k <= MURB_BOUND_SUMS; ++k) s[k] = 0.0;
+        for (size_t b = 0; b < blocks; ++b)
+            for (int k = 0; k < MURB_BOUND_SUMS; ++k) s[k] += rows[b * MURB_BOUND_SUMS + k];
+        for (size_t b = 0; with_removed && b < blocks; ++b) s[MURB_BOUND_SUMS] += rows[blocks * MURB_BOUND_SUMS + b];
+        return 0;
+    };
+    const auto frame = [&]() {
+        if (frame_v) { V[0] = frame_v[0]; V[1] = frame_v[1]; V[2] = frame_v[2]; }
+        else murb_bound_frame(s[1], s + 2, V);
+    };
+    const auto evaluate = [&](bool update) -> int {
+        RC_TRY(pot_mask(c, sh));
+        RC_TRY(pot_run(c, n, none, nullptr, true, true, nullptr, true));
+        hipLaunchKernelGGL(murb_bound_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float4*)sh.vel,
+                           (const float*)sh.pot_phi, sh.pot_member, sh.pot_e, removed_dev, (int)n, update ? 1 : 0, V[0], V[1], V[2]);
+        return hip_rc(hipGetLastError());
+    };
+    RC_TRY(sums(false, false));
+    const double members_start = s[0];
+    frame();
+    int rounds = 0;
+    bool converged = false;
+    while (rounds < max_iter && !converged) {
+        RC_TRY(evaluate(true));
+        ++rounds;
+        RC_TRY(sums(false, true));   // of S_{t+1}
+        converged = s[MURB_BOUND_SUMS] == 0.0;
+        if (!converged) frame();     // the same set has the same frame: nothing to redo
+    }
+    if (!converged) RC_TRY(evaluate(false));   // the final pass against S_{max_iter} and its V
+    RC_TRY(sums(true, false));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const bool empty = s[0] == 0.0;
+    const double K = s[8], W = -0.5 * s[9];
+    out16[0] = s[0];
+    out16[1] = s[1];
+    out16[2] = (double)rounds;
+    out16[3] = converged ? 1.0 : 0.0;
+    for (int k = 0; k < 3; ++k) out16[4 + k] = empty ? nan : V[k];
+    for (int k = 0; k < 3; ++k) out16[7 + k] = s[5 + k] / s[1];   // 0 / 0: NaN
+    out16[10] = K;
+    out16[11] = W;
+    out16[12] = K / std::fabs(W);
+    out16[13] = members_start - s[0];
+    out16[14] = s[10];
+    out16[15] = 0.0;
+    if (member) HIP_TRY(hipMemcpy(member, sh.pot_member, n, hipMemcpyDeviceToHost));
+    if (e) HIP_TRY(hipMemcpy(e, sh.pot_e, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2149,6 +2334,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.knn_part_r2, sh.knn_part_idx, sh.knn_list_r2, sh.knn_list_idx, sh.knn_rho, sh.knn_sums);
         release(sh.nbr_part, sh.nbr_counts, sh.nbr_base, sh.nbr_idx, sh.nbr_r2);
         release(sh.bnd_in, sh.bnd_part, sh.bnd_idx, sh.bnd_h, sh.bnd_elems, sh.bnd_flag, sh.bnd_sums);
+        release(sh.pot_in, sh.pot_rec, sh.pot_member, sh.pot_part, sh.pot_phi, sh.pot_e, sh.pot_rows);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2718,6 +2904,63 @@ int murbbind_elements(float g, float soft, const float* qi, const float* vi, flo
     for (const float v : {g, soft, mi, mj})
         if (!std::isfinite(v) || v < 0.f) return MURBHIP_E_INVALID;
     murb_bind_elements(soft * soft, qi, vi, g * mi, mi, qj, vj, g * mj, mj, out6);
+    return 0;
+}
+
+// ---- include/murbbound.h
+int murbpot_of(murbhip_ctx* c, unsigned long count, const int* bodies, const unsigned char* member, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!phi || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    return pot_call(c, count, p, bodies, true, member, phi);
+}
+
+int murbpot_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const int* skip,
+               const unsigned char* member, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !phi) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz})
+        for (unsigned long i = 0; i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {px, py, pz};
+    return pot_call(c, count, p, skip, false, member, phi);
+}
+
+int murbbound_members(murbhip_ctx* c, const unsigned char* start, const double* frame_v, int max_iter, unsigned char* member, double* e,
+                      double* out16)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    RC_TRY(field_state(c));
+    if (!out16 || max_iter < 1 || max_iter > 4096) return MURBHIP_E_INVALID;
+    for (int k = 0; frame_v && k < 3; ++k)
+        if (!std::isfinite(frame_v[k])) return MURBHIP_E_INVALID;
+    return bound_members(c, start, frame_v, max_iter, member, e, out16);
+}
+
+int murbbound_radii(unsigned long n, const float* qx, const float* qy, const float* qz, const float* m, const unsigned char* member,
+                    const double* centre3, int nfrac, const double* frac, double* radii)
+{
+    if (nfrac < 0 || !centre3) return MURBHIP_E_INVALID;
+    if (nfrac == 0) return 0;
+    if (!frac || !radii || (n > 0 && (!qx || !qy || !qz || !m))) return MURBHIP_E_INVALID;
+    for (const float* q : {qx, qy, qz, m})
+        for (unsigned long i = 0; i < n; ++i)
+            if (!std::isfinite(q[i]) || (q == m && q[i] < 0.f)) return MURBHIP_E_INVALID;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(centre3[k])) return MURBHIP_E_INVALID;
+    for (int f = 0; f < nfrac; ++f)
+        if (!(frac[f] > 0.0 && frac[f] <= 1.0)) return MURBHIP_E_INVALID;
+    murb_bound_radii(n, qx, qy, qz, m, member, centre3, nfrac, frac, radii);
     return 0;
 }
 
@@ -3508,10 +3751,10 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr, bind
+        //                                 tracer, knn, nbr, bind, pot
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

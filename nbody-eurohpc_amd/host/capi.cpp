@@ -247,6 +247,17 @@ int murbhost_sim_neighbours_of(void *p, float h, unsigned long *offsets, int *id
     std::copy(i.begin(), i.end(), idx);
     return 0;
 }
+// SimulationNBodyHIP::boundMembers: member (n bytes) and e (n doubles) where they are given, out16 always; murbhip's code
+int murbhost_sim_bound_members(void *p, int max_iter, unsigned char *member, double *e, double *out16)
+{
+    std::vector<unsigned char> vm;
+    std::vector<double> ve;
+    const int rc = static_cast<Sim *>(p)->sim->boundMembers(max_iter, vm, ve, out16);
+    if (rc != 0) return rc;
+    if (member) std::copy(vm.begin(), vm.end(), member);
+    if (e) std::copy(ve.begin(), ve.end(), e);
+    return 0;
+}
 // SimulationNBodyHIP::binaries: *count and out8 always; i, j (capacity entries) and elems (6 * capacity) where they are given and
 // hold the pairs, else MURBHIP_E_INVALID (-2000) with *count and out8 filled, like murbbind_pairs; murbhip's code
 int murbhost_sim_binaries(void *p, int *i, int *j, double *elems, unsigned long capacity, unsigned long *count, double *out8)

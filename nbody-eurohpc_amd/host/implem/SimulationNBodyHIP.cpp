@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "murbbind.h"
+#include "murbbound.h"
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
@@ -97,6 +98,15 @@ int SimulationNBodyHIP<T>::binaries(std::vector<int> &i, std::vector<int> &j, st
     j.resize(pairs);
     elems.resize(6 * pairs);
     return murbbind_pairs(hipBodiesPtr->getContext(), i.data(), j.data(), elems.data(), pairs, &pairs, out8);
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::boundMembers(int maxIter, std::vector<unsigned char> &member, std::vector<double> &e, double *out16)
+{
+    const unsigned long n = this->getBodies()->getN();
+    member.assign(n, 0);
+    e.assign(n, 0.0);
+    return murbbound_members(hipBodiesPtr->getContext(), nullptr, nullptr, maxIter, member.data(), e.data(), out16);
 }
 
 template <typename T>

@@ -56,6 +56,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // The count-only call, then the sized one.  A read-out like fieldAt; returns murbhip's code.
     int binaries(std::vector<int> &i, std::vector<int> &j, std::vector<double> &elems, double *out8);
 
+    // Bound members of the bodies as they are on the device (murbbound_members' rules, include/murbbound.h): iterative unbinding
+    // from all bodies in the members' own frame, at most maxIter rounds.  member gets n bytes (0 / 1), e the n energies per unit
+    // mass against the final members, out16 the summary.  A read-out like fieldAt; returns murbhip's code.
+    int boundMembers(int maxIter, std::vector<unsigned char> &member, std::vector<double> &e, double *out16);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

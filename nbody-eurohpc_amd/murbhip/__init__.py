@@ -112,6 +112,12 @@ def lib():
         L.murbbind_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 7 + [_ip, _ip, _fp]
         L.murbbind_pairs.argtypes = [C.c_void_p, _ip, _ip, _dp, C.c_ulong, _up, _dp]
         L.murbbind_elements.argtypes = [C.c_float, C.c_float, _fp, _fp, C.c_float, _fp, _fp, C.c_float, _dp]
+        # include/murbbound.h
+        _bp = C.POINTER(C.c_ubyte)
+        L.murbpot_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _bp, _fp]
+        L.murbpot_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [_ip, _bp, _fp]
+        L.murbbound_members.argtypes = [C.c_void_p, _bp, _dp, C.c_int, _bp, _dp, _dp]
+        L.murbbound_radii.argtypes = [C.c_ulong] + [_fp] * 4 + [_bp, _dp, C.c_int, _dp, _dp]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -162,6 +168,9 @@ NBR_OPTIONS = ("list_entries",)
 BIND_EXPORTS = "murbbind_of murbbind_at murbbind_pairs murbbind_elements".split()   # include/murbbind.h
 BIND_ELEMENT_KEYS = ("a", "e", "period", "h", "energy", "r")
 BIND_CENSUS_KEYS = ("pairs", "energy_sum", "hardest_i", "hardest_j", "hardest_energy", "a_min", "bound_bodies", "mutual_pairs")
+BOUND_EXPORTS = "murbpot_of murbpot_at murbbound_members murbbound_radii".split()   # include/murbbound.h
+BOUND_KEYS = ("members", "mass", "rounds", "converged", "vx", "vy", "vz", "cx", "cy", "cz", "kinetic", "potential", "virial_ratio",
+              "removed", "unbound_bodies")
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -285,6 +294,49 @@ def binary_elements(g, soft, qi, vi, mi, qj, vj, mj):
     _check(lib().murbbind_elements(float(np.float32(g)), float(np.float32(soft)), _ptr(q[0]), _ptr(q[1]), float(np.float32(mi)),
                                    _ptr(q[2]), _ptr(q[3]), float(np.float32(mj)), out), "murbbind_elements")
     return dict(zip(BIND_ELEMENT_KEYS, out[:]))
+
+
+def _mask(member, n):
+    """(array or None, pointer or None) of a mask of n bodies: nonzero = in."""
+    if member is None:
+        return None, None
+    mk = np.ascontiguousarray(np.asarray(member) != 0, np.uint8).reshape(-1)
+    if mk.shape != (n,):
+        raise ValueError("a mask has one entry per body")
+    return mk, mk.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+def _bound_dict(member, e, out16):
+    d = {"member": member.astype(bool), "e": e}
+    d.update(zip(BOUND_KEYS, out16[:15]))
+    for key in ("members", "rounds", "removed", "unbound_bodies"):
+        d[key] = int(d[key])
+    d["converged"] = bool(d["converged"])
+    d["v"] = np.array(out16[4:7])
+    d["centre"] = np.array(out16[7:10])
+    return d
+
+
+def lagrangian_radii(q, m, fractions, centre, member=None):
+    """float64 radii about `centre` (three values) inside which the listed mass `fractions` (each in (0, 1]) of the members lie:
+    q = (qx, qy, qz) and m float32 arrays of n bodies, member a mask (None: all).  The distance of the first body, by
+    (distance, index), at which the running mass reaches the fraction of the total; NaN when the members have no mass (host
+    only; include/murbbound.h: murbbound_radii)."""
+    qa = [_f32(x) for x in q]
+    ma = _f32(m)
+    n = ma.shape[0]
+    if len(qa) != 3 or any(x.shape != (n,) for x in qa):
+        raise ValueError("positions are three arrays, one entry per body")
+    _, mp = _mask(member, n)
+    fr = np.ascontiguousarray(fractions, np.float64).reshape(-1)
+    ce = np.ascontiguousarray(centre, np.float64).reshape(-1)
+    if ce.shape != (3,):
+        raise ValueError("the centre has three components")
+    out = np.full(fr.shape[0], np.nan)
+    dp = C.POINTER(C.c_double)
+    _check(lib().murbbound_radii(n, *[_ptr(x) for x in qa], _ptr(ma), mp, ce.ctypes.data_as(dp), fr.shape[0], fr.ctypes.data_as(dp),
+                                 out.ctypes.data_as(dp)), "murbbound_radii")
+    return out
 
 
 def _binaries_dict(i, j, elems, out8):
@@ -676,6 +728,52 @@ class Simulation:
                                         C.byref(count), out8), "murbbind_pairs")
         return _binaries_dict(i, j, elems, out8[:])
 
+    # -- potential of a subset and bound members (include/murbbound.h)
+    def potential_of(self, bodies=None, member=None):
+        """phi float32 of the listed bodies (None: all, in order): the sum of G m_j / sqrt(d^2 + soft^2) over the other bodies, or
+        over those of them the mask `member` (n entries, nonzero = in; None: all) lets in; positive, like the field read-out's
+        phi and bit for bit its value (include/murbbound.h: murbpot_of).  A read-out: synchronous, changes nothing."""
+        count, bp = self._knn_bodies(bodies)
+        _, mp = _mask(member, self.n)
+        phi = np.zeros(count, np.float32)
+        _check(lib().murbpot_of(self._h, count, bp, mp, _ptr(phi)), "murbpot_of")
+        return phi
+
+    def potential_at(self, points, skip=None, member=None):
+        """potential_of at `points` (3, count) of the caller's, with body skip[p] (or none: -1, or skip=None) left out of point p
+        (include/murbbound.h: murbpot_at)."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (count,):
+                raise ValueError("skip has one entry per point")
+        _, mp = _mask(member, self.n)
+        phi = np.zeros(count, np.float32)
+        _check(lib().murbpot_at(self._h, count, *[_ptr(x) for x in p], sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                                mp, _ptr(phi)), "murbpot_at")
+        return phi
+
+    def bound_members(self, start=None, frame_v=None, max_iter=64):
+        """dict of the bound members by iterative unbinding from the mask `start` (None: all bodies) in the members' own
+        centre-of-mass frame (or the fixed velocity `frame_v`), at most max_iter rounds: member (bool, n), e (float64, n: the
+        energy per unit mass of every body against the final members), members, mass, rounds, converged, v, centre, vx .. cz,
+        kinetic, potential, virial_ratio, removed, unbound_bodies (include/murbbound.h: murbbound_members)."""
+        _, sp = _mask(start, self.n)
+        fv = None
+        if frame_v is not None:
+            fv = np.ascontiguousarray(frame_v, np.float64).reshape(-1)
+            if fv.shape != (3,):
+                raise ValueError("frame_v has three components")
+        dp = C.POINTER(C.c_double)
+        member, e, out16 = np.zeros(self.n, np.uint8), np.zeros(self.n, np.float64), (C.c_double * 16)()
+        _check(lib().murbbound_members(self._h, sp, fv.ctypes.data_as(dp) if fv is not None else None, int(max_iter),
+                                       member.ctypes.data_as(C.POINTER(C.c_ubyte)), e.ctypes.data_as(dp), out16), "murbbound_members")
+        return _bound_dict(member, e, out16[:])
+
     # -- neighbours within a radius (include/murbnbr.h)
     def _nbr_radii(self, h, count):
         """(h array pointer or None, h_all) of a scalar or of one radius per point."""
@@ -969,6 +1067,7 @@ def host_lib():
         H.murbhost_sim_set_density_centre.argtypes = [C.c_void_p, C.c_int]
         H.murbhost_sim_neighbours_of.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong), C.POINTER(C.c_int), C.c_ulong]
         H.murbhost_sim_binaries.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.c_ulong, C.POINTER(C.c_ulong), _dp]
+        H.murbhost_sim_bound_members.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1137,6 +1236,13 @@ class HostSim:
             _check(self.H.murbhost_sim_binaries(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), elems.ctypes.data_as(dp), pairs,
                                                 C.byref(count), out8), "murbhost_sim_binaries")
         return _binaries_dict(i, j, elems, out8[:])
+
+    def bound_members(self, max_iter=64):
+        """SimulationNBodyHIP::boundMembers: Simulation.bound_members() for the plugin's bodies as they are on the device."""
+        member, e, out16 = np.zeros(self.n, np.uint8), np.zeros(self.n, np.float64), (C.c_double * 16)()
+        _check(self.H.murbhost_sim_bound_members(self.h, int(max_iter), member.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                 e.ctypes.data_as(C.POINTER(C.c_double)), out16), "murbhost_sim_bound_members")
+        return _bound_dict(member, e, out16[:])
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
