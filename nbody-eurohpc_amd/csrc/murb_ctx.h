@@ -18,6 +18,7 @@
 #include "murb_kernels_nbr.h"     // likewise
 #include "murb_kernels_bind.h"    // likewise
 #include "murb_kernels_pot.h"     // likewise
+#include "murb_kernels_mst.h"     // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -183,6 +184,20 @@ struct Shard {
     size_t pot_es = 0;
     double* pot_rows = nullptr;     // ... and the block rows of its two kernels: pot_row doubles
     size_t pot_row = 0;
+    // nearest body of another label and the spanning tree (include/murbmst.h): the packed points go through the field read-out's
+    // fld_pts like the knn read-out's; the labels, the labelled records, the listed bodies, rows and results are its own,
+    // allocated on first use and grown
+    int* mst_label = nullptr;       // the labels, one int per body: mst_labels entries
+    size_t mst_labels = 0;
+    float4* mst_rec = nullptr;      // the labelled copy of the position + G m records: mst_recs records
+    size_t mst_recs = 0;
+    int* mst_in = nullptr;          // a launch's listed bodies: mst_ins entries
+    size_t mst_ins = 0;
+    uint2* mst_part = nullptr;      // the chunks' (r2 bits, index): mst_parts entries
+    size_t mst_parts = 0;
+    int* mst_idx = nullptr;         // a launch's partners: mst_points entries ...
+    float* mst_r2 = nullptr;        // ... and their r2
+    size_t mst_points = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -230,6 +245,7 @@ enum ProfKind {
     kProfNbr,             // compute stream: a count or fill sweep launch of the radius read-out (murbnbr.h); never part of the force figures
     kProfBind,            // compute stream: a sweep launch of the bound-pair read-out (murbbind.h); never part of the force figures
     kProfPot,             // compute stream: a sweep launch of the potential read-out (murbbound.h); never part of the force figures
+    kProfMst,             // compute stream: a sweep launch of the foreign-nearest read-out (murbmst.h); never part of the force figures
     kProfKinds
 };
 

@@ -42,10 +42,12 @@
 #include "../../include/murbbind.h"
 #include "../../include/murbbound.h"
 #include "../../include/murbknn.h"
+#include "../../include/murbmst.h"
 #include "../../include/murbnbr.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
+#include "murb_mst.h"
 
 namespace {
 
@@ -2123,6 +2125,165 @@ int bound_members(murbhip_ctx* c, const unsigned char* start, const double* fram
     return 0;
 }
 
+// ---- nearest body of another label and the spanning tree (include/murbmst.h; kernels: murb_kernels_mst.h, the rounds: murb_mst.h)
+// The labels to the device and the labelled copy of the records from them: the sweep's j side.
+int foreign_labels(murbhip_ctx* c, Shard& sh, const int* label)
+{
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const size_t records = (size_t)l.tiles * MURB_TILE_F4;   // the tiles that hold real bodies: all the sweep reads
+    RC_TRY(grow(sh, sh.mst_label, sh.mst_labels, (size_t)c->in.n));
+    RC_TRY(grow(sh, sh.mst_rec, sh.mst_recs, records));
+    HIP_TRY(hipMemcpy(sh.mst_label, label, c->in.n * sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(murb_mst_label_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, sh.compute,
+                       (const float4*)sh.rec[c->cur], (const int*)sh.mst_label, sh.mst_rec, (int)c->in.n, (unsigned int)records);
+    return hip_rc(hipGetLastError());
+}
+
+// knn_run's planning, batching, grid and packed-point buffer with one (partner, r2) per point in the place of the list.  The
+// points are listed bodies (idx, or null for all n in order); foreign_labels has run on the compute stream.
+int foreign_run(murbhip_ctx* c, unsigned long count, const int* idx, int* out_idx, float* out_r2)
+{
+    Shard& sh = c->shards[0];
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, 0));
+    {   // partners and r2 grow together: they share one size
+        size_t r2_points = sh.mst_points;
+        RC_TRY(grow(sh, sh.mst_in, sh.mst_ins, cap));
+        RC_TRY(grow(sh, sh.mst_part, sh.mst_parts, cap * (size_t)l.chunks));
+        RC_TRY(grow(sh, sh.mst_r2, r2_points, cap));
+        RC_TRY(grow(sh, sh.mst_idx, sh.mst_points, cap));
+    }
+    std::vector<int> every;
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
+        const int* list = idx ? idx + first : nullptr;
+        if (!idx) {   // all bodies in order
+            every.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
+            list = every.data();
+        }
+        HIP_TRY(hipMemcpy(sh.mst_in, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(murb_foreign_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)sh.rec[c->cur], (const int*)sh.mst_label, (const int*)sh.mst_in, sh.fld_pts, (int)bn, (int)padded);
+        MurbForeignArgs fa{};
+        fa.rec = sh.mst_rec;
+        fa.pts = sh.fld_pts;
+        fa.part = sh.mst_part;
+        fa.groups = (int)(padded / MURB_FIELD_GROUP);
+        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a minimum does not depend on the cut
+        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
+        fa.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + fa.groups - 1) / fa.groups));
+        fa.tiles_each = l.tiles / fa.chunks;   // chunks <= tiles: every chunk holds a tile
+        fa.tiles_more = l.tiles % fa.chunks;
+        fa.stride = (unsigned int)padded;   // chunks * padded <= mst_parts
+        fa.soft2 = c->soft2;
+        const long units = (long)fa.groups * fa.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfMst, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        hipLaunchKernelGGL((murb_foreign_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                           sh.compute, fa);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        hipLaunchKernelGGL(murb_foreign_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)fa.part,
+                           (const float4*)sh.fld_pts, sh.mst_idx, sh.mst_r2, (int)bn, fa.chunks, fa.stride);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first, sh.mst_idx, bn * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + first, sh.mst_r2, bn * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// murbforeign_of once its arguments are checked
+int foreign_call(murbhip_ctx* c, unsigned long count, const int* bodies, const int* label, int* partner, float* r2)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    RC_TRY(foreign_labels(c, sh, label));
+    return foreign_run(c, count, bodies, partner, r2);
+}
+
+// The rounds of include/murbmst.h.  The points of every round are the members alone.
+int mst_call(murbhip_ctx* c, const unsigned char* member, unsigned long capacity, int* ei, int* ej, float* er2, double* elen, int* label,
+             double* out8)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const unsigned long n = c->in.n;
+    std::vector<int> lab(n), members;
+    for (unsigned long i = 0; i < n; ++i) {
+        lab[i] = !member || member[i] ? (int)i : -1;
+        if (lab[i] >= 0) members.push_back((int)i);
+    }
+    const unsigned long m = members.size();
+    std::vector<int> got_idx(m), partner(n, -1);
+    std::vector<float> got_r2(m), r2(n, std::numeric_limits<float>::infinity());
+    std::vector<MurbMstEdge> tree, chosen;
+    int rounds = 0;
+    // a round that adds no edge ends the rounds and is not counted; with one component left there is nothing to sweep for
+    for (bool more = m > 1; more;) {
+        if (rounds == MURB_MST_ROUNDS_MAX) return MURBHIP_E_STATE;   // never reached: every round at least halves the components
+        RC_TRY(foreign_labels(c, sh, lab.data()));
+        RC_TRY(foreign_run(c, m, members.data(), got_idx.data(), got_r2.data()));
+        for (unsigned long k = 0; k < m; ++k) {
+            partner[members[k]] = got_idx[k];
+            r2[members[k]] = got_r2[k];
+        }
+        if (!murb_mst_round(n, lab.data(), partner.data(), r2.data(), chosen)) return MURBHIP_E_STATE;   // the sweep's rule rules it out
+        rounds += chosen.empty() ? 0 : 1;
+        tree.insert(tree.end(), chosen.begin(), chosen.end());
+        more = !chosen.empty() && tree.size() + 1 < m;
+    }
+    std::sort(tree.begin(), tree.end(), murb_mst_before);
+    unsigned long components = 0;
+    for (unsigned long k = 0; k < m; ++k) components += lab[members[k]] == members[k];
+    // the lengths from the device's fp32 coordinates
+    std::vector<double> len(tree.size());
+    if (!tree.empty()) {
+        const MurbFieldLayout l = murb_field_layout(n, c->field_chunks, c->field_batch);
+        std::vector<float4> rec((size_t)l.tiles * MURB_TILE_F4);
+        HIP_TRY(hipMemcpy(rec.data(), sh.rec[c->cur], rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        const auto q = [&](int s, float (&out)[3]) {
+            const float* const f = (const float*)(rec.data() + murb_rec_a((unsigned long)(s >> 1))) + (s & 1);
+            out[0] = f[0]; out[1] = f[2]; out[2] = f[4 * MURB_TILE_PAIRS];
+        };
+        for (size_t e = 0; e < tree.size(); ++e) {
+            float a[3], b[3];
+            q(tree[e].i, a);
+            q(tree[e].j, b);
+            len[e] = murb_mst_length(a[0], a[1], a[2], b[0], b[1], b[2]);
+        }
+    }
+    double total = 0.0, longest = 0.0;
+    for (const double v : len) {
+        total += v;
+        longest = std::max(longest, v);
+    }
+    out8[0] = (double)m;
+    out8[1] = (double)tree.size();
+    out8[2] = (double)components;
+    out8[3] = (double)rounds;
+    out8[4] = total;
+    out8[5] = tree.empty() ? std::numeric_limits<double>::quiet_NaN() : total / (double)tree.size();
+    out8[6] = longest;
+    out8[7] = 0.0;
+    if (label) std::memcpy(label, lab.data(), n * sizeof(int));
+    if (!ei && !ej && !er2 && !elen) return 0;
+    if (capacity < tree.size()) return MURBHIP_E_INVALID;   // the edge arrays untouched: the caller sizes them from out8[1]
+    for (size_t e = 0; e < tree.size(); ++e) {
+        if (ei) ei[e] = tree[e].i;
+        if (ej) ej[e] = tree[e].j;
+        if (er2) er2[e] = tree[e].r2;
+        if (elen) elen[e] = len[e];
+    }
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2335,6 +2496,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.nbr_part, sh.nbr_counts, sh.nbr_base, sh.nbr_idx, sh.nbr_r2);
         release(sh.bnd_in, sh.bnd_part, sh.bnd_idx, sh.bnd_h, sh.bnd_elems, sh.bnd_flag, sh.bnd_sums);
         release(sh.pot_in, sh.pot_rec, sh.pot_member, sh.pot_part, sh.pot_phi, sh.pot_e, sh.pot_rows);
+        release(sh.mst_label, sh.mst_rec, sh.mst_in, sh.mst_part, sh.mst_idx, sh.mst_r2);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -2962,6 +3124,51 @@ int murbbound_radii(unsigned long n, const float* qx, const float* qy, const flo
         if (!(frac[f] > 0.0 && frac[f] <= 1.0)) return MURBHIP_E_INVALID;
     murb_bound_radii(n, qx, qy, qz, m, member, centre3, nfrac, frac, radii);
     return 0;
+}
+
+// ---- include/murbmst.h
+int murbforeign_of(murbhip_ctx* c, unsigned long count, const int* bodies, const int* label, int* partner, float* r2)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!label || !partner || !r2 || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    return foreign_call(c, count, bodies, label, partner, r2);
+}
+
+int murbmst_of(murbhip_ctx* c, const unsigned char* member, unsigned long capacity, int* ei, int* ej, float* er2, double* elen, int* label,
+               double* out8)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    RC_TRY(field_state(c));
+    if (!out8) return MURBHIP_E_INVALID;
+    return mst_call(c, member, capacity, ei, ej, er2, elen, label, out8);
+}
+
+int murbmst_round(unsigned long n, int* label, const int* partner, const float* r2, int* ei, int* ej, float* er2, unsigned long capacity,
+                  unsigned long* edges)
+{
+    if (!edges || (n > 0 && (!label || !partner || !r2))) return MURBHIP_E_INVALID;
+    std::vector<int> next(label, label + n);
+    std::vector<MurbMstEdge> chosen;
+    if (!murb_mst_round(n, next.data(), partner, r2, chosen)) return MURBHIP_E_INVALID;
+    if ((ei || ej || er2) && *edges + chosen.size() > capacity) return MURBHIP_E_INVALID;
+    for (size_t e = 0; e < chosen.size(); ++e) {
+        if (ei) ei[*edges + e] = chosen[e].i;
+        if (ej) ej[*edges + e] = chosen[e].j;
+        if (er2) er2[*edges + e] = chosen[e].r2;
+    }
+    std::copy(next.begin(), next.end(), label);
+    *edges += chosen.size();
+    return 0;
+}
+
+int murbmst_cut(unsigned long n, unsigned long edges, const int* ei, const int* ej, const float* er2, float thr, int* label)
+{
+    if ((n > 0 && !label) || (edges > 0 && (!ei || !ej || !er2)) || thr != thr) return MURBHIP_E_INVALID;
+    return murb_mst_cut(n, edges, ei, ej, er2, thr, label) ? 0 : MURBHIP_E_INVALID;
 }
 
 // ---- include/murbnbr.h
@@ -3751,10 +3958,11 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr, bind, pot
+        //                                 tracer, knn, nbr, bind, pot, mst
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
-                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot"};
+                                                      "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot",
+                                                      "mst"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

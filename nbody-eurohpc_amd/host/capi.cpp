@@ -258,6 +258,22 @@ int murbhost_sim_bound_members(void *p, int max_iter, unsigned char *member, dou
     if (e) std::copy(ve.begin(), ve.end(), e);
     return 0;
 }
+// SimulationNBodyHIP::spanningTree: out8 always; i, j, r2, length (capacity entries each) where they are given and hold the edges, else
+// MURBHIP_E_INVALID (-2000) with out8 filled, like murbmst_of; murbhip's code
+int murbhost_sim_spanning_tree(void *p, int *i, int *j, float *r2, double *length, unsigned long capacity, double *out8)
+{
+    std::vector<int> vi, vj;
+    std::vector<float> vr;
+    std::vector<double> vl;
+    const int rc = static_cast<Sim *>(p)->sim->spanningTree(vi, vj, vr, vl, out8);
+    if (rc != 0) return rc;
+    if ((i || j || r2 || length) && capacity < vi.size()) return -2000;
+    if (i) std::copy(vi.begin(), vi.end(), i);
+    if (j) std::copy(vj.begin(), vj.end(), j);
+    if (r2) std::copy(vr.begin(), vr.end(), r2);
+    if (length) std::copy(vl.begin(), vl.end(), length);
+    return 0;
+}
 // SimulationNBodyHIP::binaries: *count and out8 always; i, j (capacity entries) and elems (6 * capacity) where they are given and
 // hold the pairs, else MURBHIP_E_INVALID (-2000) with *count and out8 filled, like murbbind_pairs; murbhip's code
 int murbhost_sim_binaries(void *p, int *i, int *j, double *elems, unsigned long capacity, unsigned long *count, double *out8)

@@ -5,6 +5,7 @@
 
 #include "murbbind.h"
 #include "murbbound.h"
+#include "murbmst.h"
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
@@ -107,6 +108,25 @@ int SimulationNBodyHIP<T>::boundMembers(int maxIter, std::vector<unsigned char> 
     member.assign(n, 0);
     e.assign(n, 0.0);
     return murbbound_members(hipBodiesPtr->getContext(), nullptr, nullptr, maxIter, member.data(), e.data(), out16);
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::spanningTree(std::vector<int> &i, std::vector<int> &j, std::vector<float> &r2, std::vector<double> &length,
+                                        double *out8)
+{
+    const unsigned long n = this->getBodies()->getN(), capacity = n > 0 ? n - 1 : 0;   // a tree of n bodies has n - 1 edges
+    i.assign(capacity, 0);
+    j.assign(capacity, 0);
+    r2.assign(capacity, 0.f);
+    length.assign(capacity, 0.0);
+    const int rc = murbmst_of(hipBodiesPtr->getContext(), nullptr, capacity, i.data(), j.data(), r2.data(), length.data(), nullptr, out8);
+    if (rc != 0) return rc;
+    const unsigned long edges = (unsigned long)out8[1];
+    i.resize(edges);
+    j.resize(edges);
+    r2.resize(edges);
+    length.resize(edges);
+    return 0;
 }
 
 template <typename T>

@@ -61,6 +61,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // mass against the final members, out16 the summary.  A read-out like fieldAt; returns murbhip's code.
     int boundMembers(int maxIter, std::vector<unsigned char> &member, std::vector<double> &e, double *out16);
 
+    // Minimum spanning tree of all bodies as they are on the device (murbmst_of's rules, include/murbmst.h): the edges i < j
+    // ascending by the key (r2, i, j) with the sweep's r2 and the fp64 length of each, out8 the summary {members, edges,
+    // components, rounds, total, mean and longest length, 0}.  A read-out like fieldAt; returns murbhip's code.
+    int spanningTree(std::vector<int> &i, std::vector<int> &j, std::vector<float> &r2, std::vector<double> &length, double *out8);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

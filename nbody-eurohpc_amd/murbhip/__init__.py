@@ -118,6 +118,11 @@ def lib():
         L.murbpot_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [_ip, _bp, _fp]
         L.murbbound_members.argtypes = [C.c_void_p, _bp, _dp, C.c_int, _bp, _dp, _dp]
         L.murbbound_radii.argtypes = [C.c_ulong] + [_fp] * 4 + [_bp, _dp, C.c_int, _dp, _dp]
+        # include/murbmst.h
+        L.murbforeign_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _ip, _ip, _fp]
+        L.murbmst_of.argtypes = [C.c_void_p, _bp, C.c_ulong, _ip, _ip, _fp, _dp, _ip, _dp]
+        L.murbmst_round.argtypes = [C.c_ulong, _ip, _ip, _fp, _ip, _ip, _fp, C.c_ulong, _up]
+        L.murbmst_cut.argtypes = [C.c_ulong, C.c_ulong, _ip, _ip, _fp, C.c_float, _ip]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -171,6 +176,8 @@ BIND_CENSUS_KEYS = ("pairs", "energy_sum", "hardest_i", "hardest_j", "hardest_en
 BOUND_EXPORTS = "murbpot_of murbpot_at murbbound_members murbbound_radii".split()   # include/murbbound.h
 BOUND_KEYS = ("members", "mass", "rounds", "converged", "vx", "vy", "vz", "cx", "cy", "cz", "kinetic", "potential", "virial_ratio",
               "removed", "unbound_bodies")
+MST_EXPORTS = "murbforeign_of murbmst_of murbmst_round murbmst_cut".split()   # include/murbmst.h
+MST_KEYS = ("members", "edges", "components", "rounds", "total_length", "mean_length", "longest_length")
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -388,6 +395,40 @@ def fof_groups(offsets, idx):
         if np.array_equal(new, label):
             return label.astype(np.int32)
         label = new
+
+
+def mst_round(label, partner, r2):
+    """(label, i, j, r2, added): one Boruvka round over what Simulation.foreign_nearest(label) returns for all n bodies.  Per
+    component (label >= 0; < 0: outside) the minimum, by the key (r2, min(i, j), max(i, j)), over its bodies' (i, partner[i],
+    r2[i]); the chosen edges in key order with i < j, mutual choices once; every merged component relabelled to its smallest
+    body index.  Input that closes a cycle is not what foreign_nearest returns for these labels: MurbHipError, nothing changed
+    (host only; include/murbmst.h: murbmst_round)."""
+    lab = np.array(label, np.int32).reshape(-1)   # a copy: the call relabels in place
+    pa, ra = np.ascontiguousarray(partner, np.int32).reshape(-1), _f32(r2).reshape(-1)
+    n = lab.shape[0]
+    if pa.shape != (n,) or ra.shape != (n,):
+        raise ValueError("label, partner and r2 have one entry per body")
+    ip = C.POINTER(C.c_int)
+    i, j, er2 = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    edges = C.c_ulong(0)
+    _check(lib().murbmst_round(n, lab.ctypes.data_as(ip), pa.ctypes.data_as(ip), _ptr(ra), i.ctypes.data_as(ip), j.ctypes.data_as(ip),
+                               _ptr(er2), n, C.byref(edges)), "murbmst_round")
+    e = int(edges.value)
+    return lab, i[:e].copy(), j[:e].copy(), er2[:e].copy(), e
+
+
+def mst_groups(n, i, j, r2, thr):
+    """int32 group label of each of n bodies: the smallest body index of its component under the tree edges (i, j) with
+    r2 <= thr; bodies on no edge label themselves.  With thr = neighbour_threshold(b, soft) and the tree of all bodies these are
+    fof_groups()'s labels at linking length b (host only; include/murbmst.h: murbmst_cut)."""
+    ia, ja, ra = np.ascontiguousarray(i, np.int32).reshape(-1), np.ascontiguousarray(j, np.int32).reshape(-1), _f32(r2).reshape(-1)
+    if ia.shape != ja.shape or ia.shape != ra.shape:
+        raise ValueError("i, j and r2 have one entry per edge")
+    ip = C.POINTER(C.c_int)
+    label = np.zeros(int(n), np.int32)
+    _check(lib().murbmst_cut(int(n), ia.shape[0], ia.ctypes.data_as(ip), ja.ctypes.data_as(ip), _ptr(ra), float(np.float32(thr)),
+                             label.ctypes.data_as(ip)), "murbmst_cut")
+    return label
 
 
 def _centre_dict(out):
@@ -774,6 +815,66 @@ class Simulation:
                                        member.ctypes.data_as(C.POINTER(C.c_ubyte)), e.ctypes.data_as(dp), out16), "murbbound_members")
         return _bound_dict(member, e, out16[:])
 
+    # -- nearest body of another label, the minimum spanning tree (include/murbmst.h)
+    def foreign_nearest(self, labels, bodies=None):
+        """(partner int32, r2 float32) of the listed bodies (None: all, in order): the nearest body of ANOTHER label by (r2, index)
+        among the bodies with label >= 0; `labels` holds one int per body, < 0 puts a body outside (never a candidate; as a point
+        -1 / +inf); -1 / +inf where there is none (include/murbmst.h: murbforeign_of).  A read-out: synchronous, changes
+        nothing of the simulation."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if lab.shape != (self.n,):
+            raise ValueError("labels has one entry per body")
+        count, bp = self._knn_bodies(bodies)
+        partner, r2 = np.full(count, -1, np.int32), np.full(count, np.inf, np.float32)
+        ip = C.POINTER(C.c_int)
+        _check(lib().murbforeign_of(self._h, count, bp, lab.ctypes.data_as(ip), partner.ctypes.data_as(ip), _ptr(r2)), "murbforeign_of")
+        return partner, r2
+
+    def spanning_tree(self, member=None):
+        """dict of the minimum spanning forest of the bodies the mask `member` lets in (None: all) under the key (r2, min(i, j),
+        max(i, j)): edges i < j (int32), r2 (float32), length (float64, from the float32 coordinates) ascending by the key;
+        label (int32, n: the smallest member index of the body's component, -1 outside the mask); members, edges, components,
+        rounds, total_length, mean_length, longest_length (include/murbmst.h: murbmst_of).  The arrays are sized for
+        members - 1 edges, which always serves."""
+        mk, mp = _mask(member, self.n)
+        cap = max((self.n if mk is None else int(mk.sum())) - 1, 0)
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        i, j = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        r2, length = np.zeros(cap, np.float32), np.zeros(cap, np.float64)
+        label, out8 = np.zeros(self.n, np.int32), (C.c_double * 8)()
+        _check(lib().murbmst_of(self._h, mp, cap, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(r2), length.ctypes.data_as(dp),
+                                label.ctypes.data_as(ip), out8), "murbmst_of")
+        d = dict(zip(MST_KEYS, out8[:7]))
+        for key in ("members", "edges", "components", "rounds"):
+            d[key] = int(d[key])
+        e = d["edges"]
+        d.update({"i": i[:e], "j": j[:e], "r2": r2[:e], "length": length[:e], "label": label})
+        return d
+
+    def mass_segregation_ratio(self, n_mst, sets=50, seed=0, member=None):
+        """dict of Allison et al. 2009's mass segregation ratio of the members (None: all): ratio, the mean tree length of
+        `sets` random sets of n_mst members over the tree length of the n_mst most massive (by mass descending, index
+        ascending); sigma, the random lengths' standard deviation over the massive length; length_massive; lengths_random.
+        Each draw is numpy.random.default_rng(seed).choice(members, n_mst, replace=False), in sequence from one generator.
+        Composed from spanning_tree(member=...): sets + 1 trees of n_mst points per round each."""
+        mk, _ = _mask(member, self.n)
+        members = np.arange(self.n) if mk is None else np.flatnonzero(mk)
+        n_mst = int(n_mst)
+        if not 2 <= n_mst <= members.shape[0]:
+            raise ValueError("n_mst is at least 2 and at most the members")
+        m = self.masses()[members]
+        heavy = members[np.lexsort((members, -m.astype(np.float64)))[:n_mst]]
+
+        def tree_length(who):
+            mask = np.zeros(self.n, np.uint8)
+            mask[who] = 1
+            return self.spanning_tree(member=mask)["total_length"]
+
+        massive = tree_length(heavy)
+        rng = np.random.default_rng(seed)
+        lengths = np.array([tree_length(rng.choice(members, n_mst, replace=False)) for _ in range(int(sets))])
+        return {"ratio": lengths.mean() / massive, "sigma": lengths.std() / massive, "length_massive": massive, "lengths_random": lengths}
+
     # -- neighbours within a radius (include/murbnbr.h)
     def _nbr_radii(self, h, count):
         """(h array pointer or None, h_all) of a scalar or of one radius per point."""
@@ -1068,6 +1169,7 @@ def host_lib():
         H.murbhost_sim_neighbours_of.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong), C.POINTER(C.c_int), C.c_ulong]
         H.murbhost_sim_binaries.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.c_ulong, C.POINTER(C.c_ulong), _dp]
         H.murbhost_sim_bound_members.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp]
+        H.murbhost_sim_spanning_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, C.c_ulong, _dp]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1243,6 +1345,22 @@ class HostSim:
         _check(self.H.murbhost_sim_bound_members(self.h, int(max_iter), member.ctypes.data_as(C.POINTER(C.c_ubyte)),
                                                  e.ctypes.data_as(C.POINTER(C.c_double)), out16), "murbhost_sim_bound_members")
         return _bound_dict(member, e, out16[:])
+
+    def spanning_tree(self):
+        """SimulationNBodyHIP::spanningTree: Simulation.spanning_tree() of all the plugin's bodies as they are on the device
+        (without the labels)."""
+        cap = max(self.n - 1, 0)
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        i, j, r2, length = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.float64)
+        out8 = (C.c_double * 8)()
+        _check(self.H.murbhost_sim_spanning_tree(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(r2), length.ctypes.data_as(dp),
+                                                 cap, out8), "murbhost_sim_spanning_tree")
+        d = dict(zip(MST_KEYS, out8[:7]))
+        for key in ("members", "edges", "components", "rounds"):
+            d[key] = int(d[key])
+        e = d["edges"]
+        d.update({"i": i[:e], "j": j[:e], "r2": r2[:e], "length": length[:e]})
+        return d
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
