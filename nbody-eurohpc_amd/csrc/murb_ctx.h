@@ -19,6 +19,7 @@
 #include "murb_kernels_bind.h"    // likewise
 #include "murb_kernels_pot.h"     // likewise
 #include "murb_kernels_mst.h"     // likewise
+#include "murb_kernels_sep.h"     // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -198,6 +199,22 @@ struct Shard {
     int* mst_idx = nullptr;         // a launch's partners: mst_points entries ...
     float* mst_r2 = nullptr;        // ... and their r2
     size_t mst_points = 0;
+    // pair separations (include/murbsep.h): the packed points go through the field read-out's fld_pts like the knn read-out's; the
+    // uploaded planes, the mask, the masked records, rows and results are its own, allocated on first use and grown
+    float* sep_in = nullptr;        // a launch's uploaded points: 3 planes of floats and one of ints (the listed bodies)
+    size_t sep_ins = 0;             // floats it holds
+    unsigned char* sep_member = nullptr;   // the mask, one byte per body: sep_members bytes
+    size_t sep_members = 0;
+    float4* sep_rec = nullptr;      // the masked copy of the position records: sep_recs records
+    size_t sep_recs = 0;
+    float* sep_part = nullptr;      // the chunks' rows: sep_parts floats
+    size_t sep_parts = 0;
+    double* sep_sum = nullptr;      // a launch's sums: sep_sums doubles
+    size_t sep_sums = 0;
+    unsigned int* sep_rows = nullptr;        // the workgroups' counter rows of a launch: sep_row entries ...
+    size_t sep_row = 0;
+    unsigned long long* sep_total = nullptr; // ... and the call's 64-bit totals: sep_totals entries
+    size_t sep_totals = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -246,6 +263,7 @@ enum ProfKind {
     kProfBind,            // compute stream: a sweep launch of the bound-pair read-out (murbbind.h); never part of the force figures
     kProfPot,             // compute stream: a sweep launch of the potential read-out (murbbound.h); never part of the force figures
     kProfMst,             // compute stream: a sweep launch of the foreign-nearest read-out (murbmst.h); never part of the force figures
+    kProfSep,             // compute stream: a sweep launch of the pair-separation read-out (murbsep.h); never part of the force figures
     kProfKinds
 };
 

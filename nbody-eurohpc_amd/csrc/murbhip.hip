@@ -44,6 +44,7 @@
 #include "../../include/murbknn.h"
 #include "../../include/murbmst.h"
 #include "../../include/murbnbr.h"
+#include "../../include/murbsep.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
 #include "murb_ctx.h"
@@ -2284,6 +2285,127 @@ int mst_call(murbhip_ctx* c, const unsigned char* member, unsigned long capacity
     return 0;
 }
 
+// ---- pair separations (include/murbsep.h; kernels: murb_kernels_sep.h, the bins and the launch cut: murb_sep.h) ---------------
+// murbsep_of / murbsep_at once their arguments are checked.  pot_run's planning, grid and packed-point buffer; the launches are
+// cut by murb_sep_cut, so that no 32-bit counter of a workgroup can wrap.  p: the three position planes (murbsep_at) or all null
+// (of bodies: idx lists them, or null for all n in order).  bins == 0: the sum-only sweep.
+int sep_call(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const unsigned char* member,
+             double* sum, int lo_exp, int sub, int bins, unsigned long long* hist, unsigned long long* out4)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const unsigned long n = c->in.n;
+    const MurbFieldLayout l = murb_field_layout(n, c->field_chunks, c->field_batch);
+    const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
+    const unsigned long batch = murb_sep_cut(l, grid_full);
+    if (batch == 0) return MURBHIP_E_INVALID;   // one group of points against the longest chunk would pass 2^32 pairs
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(batch, whole_groups(count));
+    const int width = bins > 0 ? MURB_SEP_TABLE : 0;   // the table's slots: below | the bins | above, the rest above too
+    const size_t pairs = (size_t)l.tiles * MURB_TILE_PAIRS, records = (size_t)l.tiles * MURB_TILE_F4;
+    RC_TRY(ensure_field(sh, cap, 0));
+    RC_TRY(grow(sh, sh.sep_in, sh.sep_ins, 4 * cap));
+    RC_TRY(grow(sh, sh.sep_rec, sh.sep_recs, records));
+    RC_TRY(grow(sh, sh.sep_part, sh.sep_parts, cap * (size_t)l.chunks));
+    RC_TRY(grow(sh, sh.sep_sum, sh.sep_sums, cap));
+    if (width) {
+        RC_TRY(grow(sh, sh.sep_rows, sh.sep_row, (size_t)grid_full * MURB_SEP_TABLE));
+        RC_TRY(grow(sh, sh.sep_total, sh.sep_totals, (size_t)MURB_SEP_TABLE));
+        HIP_TRY(hipMemsetAsync(sh.sep_total, 0, (size_t)width * sizeof(unsigned long long), sh.compute));
+    }
+    unsigned long in_set = n;   // |S|
+    if (member) {
+        RC_TRY(grow(sh, sh.sep_member, sh.sep_members, (size_t)n));
+        HIP_TRY(hipMemcpy(sh.sep_member, member, n, hipMemcpyHostToDevice));
+        in_set = 0;
+        for (unsigned long i = 0; i < n; ++i) in_set += member[i] != 0;
+    }
+    hipLaunchKernelGGL(murb_sep_mask_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, sh.compute, (const float4*)sh.rec[c->cur],
+                       member ? (const unsigned char*)sh.sep_member : nullptr, sh.sep_rec, (int)n, (unsigned int)pairs);
+    RC_TRY(hip_rc(hipGetLastError()));
+    std::vector<float> host(of_bodies ? 0 : 3 * cap, 0.f);
+    std::vector<int> every;
+    unsigned long long not_counted = 0;   // entries the slots outside S and the filler points left in the table's last slot
+    for (unsigned long first = 0; first < count; first += batch) {
+        const unsigned long bn = std::min<unsigned long>(batch, count - first), padded = whole_groups(bn);
+        if (!of_bodies) {
+            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.sep_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
+        }
+        const int* list = idx ? idx + first : nullptr;
+        if (of_bodies && !idx) {   // all bodies in order
+            every.resize(bn);
+            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
+            list = every.data();
+        }
+        if (of_bodies) HIP_TRY(hipMemcpy(sh.sep_in + 3 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.sep_in;
+        pa.idx = of_bodies ? (const int*)(sh.sep_in + 3 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)padded;
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        MurbSepArgs ta{};
+        ta.rec = sh.sep_rec;
+        ta.pts = sh.fld_pts;
+        ta.part = sh.sep_part;
+        ta.rows = sh.sep_rows;
+        ta.groups = (int)(padded / MURB_FIELD_GROUP);
+        ta.chunks = l.chunks;   // the field read-out's cut: a sum depends on it
+        ta.tiles = l.tiles;
+        ta.count = (int)bn;
+        ta.stride = (unsigned int)padded;   // chunks * padded <= sep_parts
+        ta.sh = murb_sep_shift(sub);
+        ta.minus4 = -4 * (murb_sep_base(lo_exp, sub) - 1);
+        const long units = (long)ta.groups * ta.chunks;
+        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));   // grid * width <= sep_row
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfSep, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+        RC_TRY(rc);
+        if (width)
+            hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, true>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, ta);
+        else
+            hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, false>), dim3(grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, ta);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        const unsigned long threads = std::max<unsigned long>(bn, (unsigned long)width);
+        hipLaunchKernelGGL(murb_sep_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, sh.compute, (const float*)ta.part,
+                           sh.sep_sum, (int)bn, ta.chunks, ta.stride, (const unsigned int*)sh.sep_rows, sh.sep_total, width, (int)grid);
+        RC_TRY(hip_rc(hipGetLastError()));
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        if (sum) HIP_TRY(hipMemcpy(sum + first, sh.sep_sum, bn * sizeof(double), hipMemcpyDeviceToHost));
+        not_counted += (unsigned long long)padded * ((unsigned long long)l.tiles * MURB_TILE_BODIES) - (unsigned long long)bn * in_set;
+    }
+    if (!width) return 0;
+    std::vector<unsigned long long> total((size_t)width);
+    HIP_TRY(hipMemcpy(total.data(), sh.sep_total, (size_t)width * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long own = 0;   // listed bodies that are in S: each met itself at d2 == +0, below the lowest edge
+    if (of_bodies)
+        for (unsigned long i = 0; i < count; ++i) own += !member || member[idx ? idx[i] : (long)i] != 0;
+    for (int k = 0; k < bins; ++k) hist[k] = total[(size_t)k + 1];
+    out4[0] = (unsigned long long)count * in_set - own;
+    out4[1] = total[0] - own;
+    unsigned long long above = 0;
+    for (size_t k = (size_t)bins + 1; k < total.size(); ++k) above += total[k];
+    out4[2] = above - not_counted;
+    out4[3] = 0;
+    return 0;
+}
+
+// the checks murbsep_of and murbsep_at share: what is asked for, the histogram's parameters and where it goes
+inline bool sep_request_valid(const double* sum, int lo_exp, int sub, int bins, const unsigned long long* hist, const unsigned long long* out4)
+{
+    if (bins == 0) return sum != nullptr;
+    return hist && out4 && murb_sep_params_valid(lo_exp, sub, bins);
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2497,6 +2619,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.bnd_in, sh.bnd_part, sh.bnd_idx, sh.bnd_h, sh.bnd_elems, sh.bnd_flag, sh.bnd_sums);
         release(sh.pot_in, sh.pot_rec, sh.pot_member, sh.pot_part, sh.pot_phi, sh.pot_e, sh.pot_rows);
         release(sh.mst_label, sh.mst_rec, sh.mst_in, sh.mst_part, sh.mst_idx, sh.mst_r2);
+        release(sh.sep_in, sh.sep_member, sh.sep_rec, sh.sep_part, sh.sep_sum, sh.sep_rows, sh.sep_total);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -3123,6 +3246,51 @@ int murbbound_radii(unsigned long n, const float* qx, const float* qy, const flo
     for (int f = 0; f < nfrac; ++f)
         if (!(frac[f] > 0.0 && frac[f] <= 1.0)) return MURBHIP_E_INVALID;
     murb_bound_radii(n, qx, qy, qz, m, member, centre3, nfrac, frac, radii);
+    return 0;
+}
+
+// ---- include/murbsep.h
+int murbsep_of(murbhip_ctx* c, unsigned long count, const int* bodies, const unsigned char* member, double* sum, int lo_exp, int sub, int bins,
+               unsigned long long* hist, unsigned long long* out4)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!sep_request_valid(sum, lo_exp, sub, bins, hist, out4) || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    return sep_call(c, count, p, bodies, true, member, sum, lo_exp, sub, bins, hist, out4);
+}
+
+int murbsep_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const unsigned char* member,
+               double* sum, int lo_exp, int sub, int bins, unsigned long long* hist, unsigned long long* out4)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!sep_request_valid(sum, lo_exp, sub, bins, hist, out4) || !px || !py || !pz) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz})
+        for (unsigned long i = 0; i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    const float* const p[3] = {px, py, pz};
+    return sep_call(c, count, p, nullptr, false, member, sum, lo_exp, sub, bins, hist, out4);
+}
+
+int murbsep_bin(int lo_exp, int sub, int bins, float d2)
+{
+    if (!murb_sep_params_valid(lo_exp, sub, bins)) return MURBHIP_E_INVALID;
+    return murb_sep_bin(lo_exp, sub, bins, d2);
+}
+
+int murbsep_edges(int lo_exp, int sub, int bins, float* edge2, double* edge_r)
+{
+    if (!murb_sep_params_valid(lo_exp, sub, bins) || (!edge2 && !edge_r)) return MURBHIP_E_INVALID;
+    for (int k = 0; k <= bins; ++k) {
+        const float e = murb_sep_edge2(lo_exp, sub, k);
+        if (edge2) edge2[k] = e;
+        if (edge_r) edge_r[k] = std::sqrt((double)e);
+    }
     return 0;
 }
 
@@ -3958,11 +4126,11 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr, bind, pot, mst
+        //                                 tracer, knn, nbr, bind, pot, mst, sep
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
                                                       "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot",
-                                                      "mst"};
+                                                      "mst", "sep"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -274,6 +274,8 @@ int murbhost_sim_spanning_tree(void *p, int *i, int *j, float *r2, double *lengt
     if (length) std::copy(vl.begin(), vl.end(), length);
     return 0;
 }
+// SimulationNBodyHIP::meanSeparation; murbhip's code
+int murbhost_sim_mean_separation(void *p, double *mean) { return static_cast<Sim *>(p)->sim->meanSeparation(mean); }
 // SimulationNBodyHIP::binaries: *count and out8 always; i, j (capacity entries) and elems (6 * capacity) where they are given and
 // hold the pairs, else MURBHIP_E_INVALID (-2000) with *count and out8 filled, like murbbind_pairs; murbhip's code
 int murbhost_sim_binaries(void *p, int *i, int *j, double *elems, unsigned long capacity, unsigned long *count, double *out8)

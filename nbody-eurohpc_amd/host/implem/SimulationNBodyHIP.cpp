@@ -2,10 +2,13 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
+#include <vector>
 
 #include "murbbind.h"
 #include "murbbound.h"
 #include "murbmst.h"
+#include "murbsep.h"
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
@@ -126,6 +129,27 @@ int SimulationNBodyHIP<T>::spanningTree(std::vector<int> &i, std::vector<int> &j
     j.resize(edges);
     r2.resize(edges);
     length.resize(edges);
+    return 0;
+}
+
+// the sums in index order: this file is compiled with -ffast-math, which would otherwise let the compiler reassociate them
+__attribute__((optimize("no-fast-math"))) static double sumInOrder(const std::vector<double> &v)
+{
+    double total = 0.0;
+    for (const double x : v) total += x;
+    return total;
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::meanSeparation(double *mean)
+{
+    const unsigned long n = this->getBodies()->getN();
+    *mean = std::numeric_limits<double>::quiet_NaN();
+    if (n < 2) return 0;
+    std::vector<double> sum(n);
+    const int rc = murbsep_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, sum.data(), 0, 0, 0, nullptr, nullptr);
+    if (rc != 0) return rc;
+    *mean = sumInOrder(sum) / ((double)n * ((double)n - 1.0));
     return 0;
 }
 

@@ -66,6 +66,11 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // components, rounds, total, mean and longest length, 0}.  A read-out like fieldAt; returns murbhip's code.
     int spanningTree(std::vector<int> &i, std::vector<int> &j, std::vector<float> &r2, std::vector<double> &length, double *out8);
 
+    // Mean pair separation of all bodies as they are on the device (murbsep_of's sums, include/murbsep.h): every body's sum of
+    // distances to the others, added in index order in fp64, over n (n - 1); NaN for fewer than 2 bodies.  A read-out like
+    // fieldAt; returns murbhip's code.
+    int meanSeparation(double *mean);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

@@ -123,6 +123,12 @@ def lib():
         L.murbmst_of.argtypes = [C.c_void_p, _bp, C.c_ulong, _ip, _ip, _fp, _dp, _ip, _dp]
         L.murbmst_round.argtypes = [C.c_ulong, _ip, _ip, _fp, _ip, _ip, _fp, C.c_ulong, _up]
         L.murbmst_cut.argtypes = [C.c_ulong, C.c_ulong, _ip, _ip, _fp, C.c_float, _ip]
+        # include/murbsep.h
+        _qp = C.POINTER(C.c_ulonglong)
+        L.murbsep_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _bp, _dp, C.c_int, C.c_int, C.c_int, _qp, _qp]
+        L.murbsep_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 3 + [_bp, _dp, C.c_int, C.c_int, C.c_int, _qp, _qp]
+        L.murbsep_bin.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float]
+        L.murbsep_edges.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _dp]
         # include/murbtracer.h
         L.murbtracer_upload.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6
         L.murbtracer_download.argtypes = [C.c_void_p] + [_fp] * 6
@@ -178,6 +184,8 @@ BOUND_KEYS = ("members", "mass", "rounds", "converged", "vx", "vy", "vz", "cx", 
               "removed", "unbound_bodies")
 MST_EXPORTS = "murbforeign_of murbmst_of murbmst_round murbmst_cut".split()   # include/murbmst.h
 MST_KEYS = ("members", "edges", "components", "rounds", "total_length", "mean_length", "longest_length")
+SEP_EXPORTS = "murbsep_of murbsep_at murbsep_bin murbsep_edges".split()   # include/murbsep.h
+SEP_KEYS = ("pairs", "below", "above")
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -429,6 +437,34 @@ def mst_groups(n, i, j, r2, thr):
     _check(lib().murbmst_cut(int(n), ia.shape[0], ia.ctypes.data_as(ip), ja.ctypes.data_as(ip), _ptr(ra), float(np.float32(thr)),
                              label.ctypes.data_as(ip)), "murbmst_cut")
     return label
+
+
+def separation_bin(lo_exp, sub, bins, d2):
+    """The bin of the squared separation d2 (taken as float32) among `bins` bins from d2 = 2^lo_exp up, 2^sub per octave of d2:
+    -1 below, `bins` above (+inf and NaN too), else the bin; read off the float's bits, so a d2 on an edge belongs to the bin
+    above the edge (host only; include/murbsep.h: murbsep_bin)."""
+    k = lib().murbsep_bin(int(lo_exp), int(sub), int(bins), float(np.float32(d2)))
+    if k < -1:
+        raise MurbHipError(k, "murbsep_bin")
+    return k
+
+
+def separation_edges(lo_exp, sub, bins):
+    """(edge2 float32, edge_r float64), bins + 1 entries each: the bins' edges in d2, exact floats, and their fp64 roots (host
+    only; include/murbsep.h: murbsep_edges)."""
+    size = max(int(bins), 0) + 1   # bins < 1 is refused by the call
+    edge2, edge_r = np.zeros(size, np.float32), np.zeros(size, np.float64)
+    _check(lib().murbsep_edges(int(lo_exp), int(sub), int(bins), _ptr(edge2), edge_r.ctypes.data_as(C.POINTER(C.c_double))), "murbsep_edges")
+    return edge2, edge_r
+
+
+def shell_density(hist_row, edge_r):
+    """float64 number density per bin of a one-point separation_at (about the density centre, say): the counts hist_row over the
+    shell volumes 4/3 pi (edge_r[k + 1]^3 - edge_r[k]^3).  Host only."""
+    h, r = np.asarray(hist_row, np.float64).reshape(-1), np.asarray(edge_r, np.float64).reshape(-1)
+    if r.shape != (h.shape[0] + 1,):
+        raise ValueError("edge_r has one entry more than hist_row")
+    return h / (4.0 / 3.0 * np.pi * (r[1:] ** 3 - r[:-1] ** 3))
 
 
 def _centre_dict(out):
@@ -851,6 +887,75 @@ class Simulation:
         d.update({"i": i[:e], "j": j[:e], "r2": r2[:e], "length": length[:e], "label": label})
         return d
 
+    # -- pair separations (include/murbsep.h)
+    def _sep_call(self, name, head, count, member, bins):
+        _, mp = _mask(member, self.n)
+        lo_exp, sub, nb = (0, 0, 0) if bins is None else (int(v) for v in bins)
+        if bins is not None and nb < 1:
+            raise ValueError("bins is a (lo_exp, sub, bins) triple with at least one bin, or None")
+        qp = C.POINTER(C.c_ulonglong)
+        total = np.zeros(count, np.float64)
+        hist, out4 = np.zeros(nb, np.uint64), np.zeros(4, np.uint64)
+        _check(getattr(lib(), name)(*head, mp, total.ctypes.data_as(C.POINTER(C.c_double)), lo_exp, sub, nb,
+                                    hist.ctypes.data_as(qp) if nb else None, out4.ctypes.data_as(qp) if nb else None), name)
+        if bins is None:
+            return total, None, None
+        return total, hist, dict(zip(SEP_KEYS, (int(v) for v in out4[:3])))
+
+    def separation_of(self, bodies=None, member=None, bins=None):
+        """(sum, hist, out4) of the listed bodies (None: all, in order) against the bodies the mask `member` lets in (None: all).
+        sum: float64 per listed body, the sum of its fp32 distances (unsoftened) to those bodies; itself adds 0.  bins: None, or
+        a (lo_exp, sub, bins) triple: hist (uint64, bins) counts the call's ordered (listed body, body) pairs by the float bits of
+        d2, from d2 = 2^lo_exp up with 2^sub bins per octave (separation_edges gives the edges), and out4 is a dict of pairs,
+        below, above with below + hist.sum() + above == pairs; a listed body's own entry is left out.  Without bins hist and out4
+        are None (include/murbsep.h: murbsep_of).  A read-out: synchronous, changes nothing."""
+        count, bp = self._knn_bodies(bodies)
+        return self._sep_call("murbsep_of", (self._h, count, bp), count, member, bins)
+
+    def separation_at(self, points, member=None, bins=None):
+        """separation_of at `points` (3, count) of the caller's.  No body is skipped: a point on a body gets 0 from it and one
+        entry in below (include/murbsep.h: murbsep_at)."""
+        p = [_f32(x) for x in points]
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p):
+            raise ValueError("points are three arrays of one length")
+        return self._sep_call("murbsep_at", (self._h, count, *[_ptr(x) for x in p]), count, member, bins)
+
+    def mean_separation(self, member=None):
+        """The mean pair separation of the M members (None: all): the members' separation_of sums against the members, added in
+        index order in fp64, over M (M - 1).  NaN for fewer than 2 members."""
+        mk, _ = _mask(member, self.n)
+        members = np.arange(self.n, dtype=np.int32) if mk is None else np.flatnonzero(mk).astype(np.int32)
+        m = int(members.shape[0])
+        if m < 2:
+            return float("nan")
+        sums, _, _ = self.separation_of(None if mk is None else members, member=member)
+        total = 0.0
+        for v in sums:
+            total += float(v)
+        return total / (m * (m - 1.0))
+
+    def q_parameter(self, member=None):
+        """dict of Cartwright & Whitworth 2004's Q of the M members (None: all) in the 3-D convention: q = m_bar / s_bar with
+        R the largest fp64 distance of a member from the members' unweighted mean position (from the float32 coordinates),
+        s_bar = mean_separation / R, and m_bar = the spanning tree's mean edge length over (M^2 * 4/3 pi R^3)^(1/3) / (M - 1),
+        the 3-D analogue of the 2-D (M A)^(1/2) / (M - 1).  Also m_bar, s_bar, radius, members.  NaN for fewer than 2 members.
+        Composed from spanning_tree and mean_separation."""
+        mk, _ = _mask(member, self.n)
+        members = np.arange(self.n) if mk is None else np.flatnonzero(mk)
+        m = int(members.shape[0])
+        nan = float("nan")
+        if m < 2:
+            return {"q": nan, "m_bar": nan, "s_bar": nan, "radius": nan, "members": m}
+        st = self.state()
+        q = np.stack([st[k].astype(np.float64)[members] for k in ("qx", "qy", "qz")])
+        d = q - q.mean(axis=1, keepdims=True)
+        radius = float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]).max())
+        s_bar = self.mean_separation(member) / radius
+        volume = 4.0 / 3.0 * np.pi * radius ** 3
+        m_bar = self.spanning_tree(member)["mean_length"] / ((float(m) ** 2 * volume) ** (1.0 / 3.0) / (m - 1.0))
+        return {"q": m_bar / s_bar, "m_bar": m_bar, "s_bar": s_bar, "radius": radius, "members": m}
+
     def mass_segregation_ratio(self, n_mst, sets=50, seed=0, member=None):
         """dict of Allison et al. 2009's mass segregation ratio of the members (None: all): ratio, the mean tree length of
         `sets` random sets of n_mst members over the tree length of the n_mst most massive (by mass descending, index
@@ -1170,6 +1275,7 @@ def host_lib():
         H.murbhost_sim_binaries.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.c_ulong, C.POINTER(C.c_ulong), _dp]
         H.murbhost_sim_bound_members.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp]
         H.murbhost_sim_spanning_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, C.c_ulong, _dp]
+        H.murbhost_sim_mean_separation.argtypes = [C.c_void_p, _dp]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1361,6 +1467,12 @@ class HostSim:
         e = d["edges"]
         d.update({"i": i[:e], "j": j[:e], "r2": r2[:e], "length": length[:e]})
         return d
+
+    def mean_separation(self):
+        """SimulationNBodyHIP::meanSeparation: Simulation.mean_separation() of all the plugin's bodies as they are on the device."""
+        mean = C.c_double()
+        _check(self.H.murbhost_sim_mean_separation(self.h, C.byref(mean)), "murbhost_sim_mean_separation")
+        return mean.value
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
