@@ -20,6 +20,7 @@
 #include "murb_kernels_pot.h"     // likewise
 #include "murb_kernels_mst.h"     // likewise
 #include "murb_kernels_sep.h"     // likewise
+#include "murb_kernels_list.h"    // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -215,6 +216,15 @@ struct Shard {
     size_t sep_row = 0;
     unsigned long long* sep_total = nullptr; // ... and the call's 64-bit totals: sep_totals entries
     size_t sep_totals = 0;
+    // the field of listed bodies (include/murblist.h): murblist_of / murblist_at pack their points through the field read-out's
+    // fld_in / fld_pts and stage their entries in the neighbour read-out's list buffer (nbr_idx); murbsplit_of runs inside the
+    // neighbour read-out's fill pass, whose points occupy fld_pts, so its points have records of their own.  All three write fld_out
+    float4* lst_src = nullptr;      // the gather copy of the bodies, two records per body: lst_srcs records
+    size_t lst_srcs = 0;
+    unsigned int* lst_range = nullptr;   // a range's list starts, then its list lengths: lst_ranges entries
+    size_t lst_ranges = 0;
+    float4* lst_pts = nullptr;      // murbsplit_of: a range's packed points: lst_points records
+    size_t lst_points = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -264,6 +274,7 @@ enum ProfKind {
     kProfPot,             // compute stream: a sweep launch of the potential read-out (murbbound.h); never part of the force figures
     kProfMst,             // compute stream: a sweep launch of the foreign-nearest read-out (murbmst.h); never part of the force figures
     kProfSep,             // compute stream: a sweep launch of the pair-separation read-out (murbsep.h); never part of the force figures
+    kProfList,            // compute stream: a sweep launch of the listed-source read-out (murblist.h); never part of the force figures
     kProfKinds
 };
 

@@ -44,6 +44,7 @@
 #include "../../include/murbknn.h"
 #include "../../include/murbmst.h"
 #include "../../include/murbnbr.h"
+#include "../../include/murblist.h"
 #include "../../include/murbsep.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
@@ -1675,8 +1676,12 @@ int knn_centre(murbhip_ctx* c, int k, double* out8)
 // for, and they fit) a second pass that fills them.  p: the three position planes (murbnbr_at) or all null (of bodies: idx
 // lists them, or null for all n in order).  thr: a threshold per point.  offsets: count + 1 entries.  out_idx, out_r2: host
 // arrays of `capacity` entries, null where not asked for; both null: the count pass alone.
+// consume (murbsplit_of): called after every filled range [lo, hi) of the launch that starts at point `first`, with the launch's
+// point capacity, while the range's entries sit in the list buffer at offsets[first + e] - offsets[first + lo] and the launch's
+// bodies in fld_in's index plane; the lists then count as asked for and nothing of them is copied to the host.
+using NbrConsume = std::function<int(unsigned long first, unsigned long lo, unsigned long hi, size_t cap)>;
 int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const std::vector<float>& thr,
-            unsigned long* offsets, int* out_idx, float* out_r2, unsigned long capacity)
+            unsigned long* offsets, int* out_idx, float* out_r2, unsigned long capacity, const NbrConsume* consume = nullptr)
 {
     RC_TRY(murbhip_sync(c));
     Shard& sh = c->shards[0];
@@ -1684,7 +1689,7 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
     const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
     const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
     const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
-    const bool lists = out_idx || out_r2;
+    const bool lists = out_idx || out_r2 || consume;
     const unsigned long launches = murb_field_batches(l, count);
     RC_TRY(ensure_field(sh, cap, 0));
     // with lists every launch keeps its rows of prefix sums until the fill pass: launch b's rows start at b * batch * chunks
@@ -1801,6 +1806,7 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
             HIP_TRY(hipStreamSynchronize(sh.compute));
             if (out_idx) HIP_TRY(hipMemcpy(out_idx + offsets[first + lo], sh.nbr_idx, total * sizeof(int), hipMemcpyDeviceToHost));
             if (out_r2) HIP_TRY(hipMemcpy(out_r2 + offsets[first + lo], sh.nbr_r2, total * sizeof(float), hipMemcpyDeviceToHost));
+            if (consume) RC_TRY((*consume)(first, lo, hi, cap));
         }
     }
     return 0;
@@ -2406,6 +2412,145 @@ inline bool sep_request_valid(const double* sum, int lo_exp, int sub, int bins, 
     return hist && out4 && murb_sep_params_valid(lo_exp, sub, bins);
 }
 
+// ---- the field of listed bodies (include/murblist.h; kernels: murb_kernels_list.h, the checks: murb_list.h) ------------------
+constexpr int kListWaves = 4;   // one wave per point
+
+// The gather copy of the bodies, rewritten per call: read-outs are synchronous and the copy is 32 B x n.
+int list_pack(murbhip_ctx* c, Shard& sh)
+{
+    const size_t n = c->in.n;
+    RC_TRY(grow(sh, sh.lst_src, sh.lst_srcs, 2 * n));
+    MurbListPackArgs pa{};
+    pa.rec = sh.rec[c->cur];
+    pa.vel = sh.vel;
+    pa.src = sh.lst_src;
+    pa.count = (int)n;
+    hipLaunchKernelGGL(murb_list_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    return hip_rc(hipGetLastError());
+}
+
+// One range of `npts` points, packed at pts, whose entries sit in the list buffer (nbr_idx): range holds the points' list starts,
+// then their lengths.  Synchronous: on return the list buffer, lst_range and fld_out are free again.  out: the caller's planes,
+// null where not asked for; the range's first point is point `at` of the call.
+int list_sweep(murbhip_ctx* c, Shard& sh, const float4* pts, unsigned long npts, const std::vector<unsigned int>& range, float* const (&out)[7],
+               unsigned long at, std::vector<float>& host)
+{
+    RC_TRY(grow(sh, sh.lst_range, sh.lst_ranges, 2 * npts));
+    HIP_TRY(hipMemcpy(sh.lst_range, range.data(), 2 * npts * sizeof(unsigned int), hipMemcpyHostToDevice));
+    MurbListArgs la{};
+    la.src = sh.lst_src;
+    la.pts = pts;
+    la.begin = sh.lst_range;
+    la.len = sh.lst_range + npts;
+    la.idx = sh.nbr_idx;
+    la.out = sh.fld_out;   // 7 * npts <= 7 * fld_points
+    la.count = (int)npts;
+    la.out_stride = (unsigned int)npts;
+    la.soft2 = c->soft2;
+    int rc = 0;
+    const int sp = span_begin(c, sh, kProfList, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
+    RC_TRY(rc);
+    hipLaunchKernelGGL((murb_list_sweep_kernel<kListWaves>), dim3((unsigned)((npts + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
+                       sh.compute, la);
+    RC_TRY(span_end(sh, sp, sh.compute));
+    RC_TRY(hip_rc(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(sh.compute));
+    host.resize(7 * npts);
+    HIP_TRY(hipMemcpy(host.data(), sh.fld_out, 7 * npts * sizeof(float), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 7; ++k)
+        if (out[k]) std::memcpy(out[k] + at, host.data() + k * npts, npts * sizeof(float));
+    return 0;
+}
+
+// the starts and lengths of the lists of points [lo, hi) of a CSR pair, relative to the range's first entry
+void list_range(const unsigned long* offsets, unsigned long lo, unsigned long hi, std::vector<unsigned int>& range)
+{
+    const unsigned long npts = hi - lo;
+    range.resize(2 * npts);
+    for (unsigned long e = 0; e < npts; ++e) {
+        range[e] = (unsigned int)(offsets[lo + e] - offsets[lo]);
+        range[npts + e] = (unsigned int)(offsets[lo + e + 1] - offsets[lo + e]);
+    }
+}
+
+// the list buffer holds `total` entries of a range: nbr_run's rule (a single list longer than "list_entries" grows it)
+int list_buffer(Shard& sh, unsigned long entries, unsigned long total, unsigned long all)
+{
+    size_t have = sh.nbr_list;
+    const size_t want = std::max(have, (size_t)std::min<unsigned long>(std::max(entries, total), all));
+    RC_TRY(grow(sh, sh.nbr_idx, have, want));
+    return grow(sh, sh.nbr_r2, sh.nbr_list, want);
+}
+
+// What murblist_of and murblist_at share once their arguments are checked.  field_run's batching ("field_batch") and pack step;
+// inside a launch the points are cut into ranges whose entries fit the list buffer (murb_nbr_cut under "list_entries"), staged
+// there and swept.  p: the six input planes (murblist_at; p[3..5] null: at rest) or all null (murblist_of: idx are the bodies,
+// or null for all n in order).
+int list_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], const int* idx, bool of_bodies, const unsigned long* offsets,
+             const int* entries_in, float* const (&out)[7])
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
+    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
+    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    RC_TRY(ensure_field(sh, cap, 0));
+    RC_TRY(list_pack(c, sh));
+    const unsigned long entries = murb_nbr_entries(c->nbr_list_entries);
+    const bool has_vel = p[3] != nullptr;
+    std::vector<float> host(6 * cap, 0.f), results;
+    std::vector<int> all;
+    std::vector<unsigned int> range;
+    for (unsigned long first = 0; first < count; first += l.batch) {
+        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
+        if (offsets[first + bn] == offsets[first]) {   // empty lists alone: +0 seven times
+            for (int k = 0; k < 7; ++k)
+                if (out[k]) std::fill(out[k] + first, out[k] + first + bn, 0.f);
+            continue;
+        }
+        if (!of_bodies) {
+            const int planes = has_vel ? 6 : 3;
+            for (int k = 0; k < planes; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), planes * cap * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            const int* list = idx ? idx + first : nullptr;
+            if (!list) {   // all bodies in order
+                all.resize(bn);
+                for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
+                list = all.data();
+            }
+            HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        }
+        MurbFieldPackArgs pa{};
+        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.idx = of_bodies ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.fld_pts;
+        pa.count = (int)bn;
+        pa.padded = (int)bn;   // a wave takes one point: no group to fill up
+        pa.in_stride = (unsigned int)cap;
+        pa.has_vel = has_vel ? 1 : 0;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        RC_TRY(hip_rc(hipGetLastError()));
+        for (unsigned long lo = 0, hi; lo < bn; lo = hi) {
+            hi = murb_nbr_cut(bn, offsets + first, lo, entries);
+            const unsigned long total = offsets[first + hi] - offsets[first + lo];
+            if (total == 0) {
+                for (int k = 0; k < 7; ++k)
+                    if (out[k]) std::fill(out[k] + first + lo, out[k] + first + hi, 0.f);
+                continue;
+            }
+            RC_TRY(list_buffer(sh, entries, total, offsets[count]));
+            HIP_TRY(hipMemcpy(sh.nbr_idx, entries_in + offsets[first + lo], total * sizeof(int), hipMemcpyHostToDevice));
+            list_range(offsets + first, lo, hi, range);
+            RC_TRY(list_sweep(c, sh, sh.fld_pts + 2 * lo, hi - lo, range, out, first + lo, results));
+        }
+    }
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2620,6 +2765,7 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.pot_in, sh.pot_rec, sh.pot_member, sh.pot_part, sh.pot_phi, sh.pot_e, sh.pot_rows);
         release(sh.mst_label, sh.mst_rec, sh.mst_in, sh.mst_part, sh.mst_idx, sh.mst_r2);
         release(sh.sep_in, sh.sep_member, sh.sep_rec, sh.sep_part, sh.sep_sum, sh.sep_rows, sh.sep_total);
+        release(sh.lst_src, sh.lst_range, sh.lst_pts);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -3415,6 +3561,83 @@ int murbnbr_cut(unsigned long count, const unsigned long* offsets, unsigned long
     return 0;
 }
 
+// ---- include/murblist.h
+int murblist_of(murbhip_ctx* c, unsigned long count, const int* bodies, const unsigned long* offsets, const int* idx, float* ax, float* ay,
+                float* az, float* jx, float* jy, float* jz, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if ((!bodies && count != c->in.n) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!murb_list_valid(count, offsets, idx, c->in.n)) return MURBHIP_E_INVALID;
+    const float* const p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
+    return list_run(c, count, p, bodies, true, offsets, idx, out);
+}
+
+int murblist_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const float* pvx, const float* pvy,
+                const float* pvz, const unsigned long* offsets, const int* idx, float* ax, float* ay, float* az, float* jx, float* jy,
+                float* jz, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz}) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    for (const float* q : {px, py, pz, pvx, pvy, pvz})
+        for (unsigned long i = 0; q && i < count; ++i)
+            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    if (!murb_list_valid(count, offsets, idx, c->in.n)) return MURBHIP_E_INVALID;
+    const float* const p[6] = {px, py, pz, pvx, pvy, pvz};
+    float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
+    return list_run(c, count, p, nullptr, false, offsets, idx, out);
+}
+
+int murbsplit_of(murbhip_ctx* c, unsigned long count, const int* bodies, const float* h, float h_all, unsigned long* counts, float* ax,
+                 float* ay, float* az, float* jx, float* jy, float* jz, float* phi)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (count == 0) return 0;
+    RC_TRY(field_state(c));
+    if ((!bodies && count != c->in.n) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
+    for (unsigned long i = 0; bodies && i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    std::vector<float> thr;
+    if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    RC_TRY(list_pack(c, sh));
+    float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
+    for (float* plane : out)   // the ranges without an entry are never swept: +0
+        if (plane) std::fill(plane, plane + count, 0.f);
+    std::vector<unsigned long> offsets(count + 1, 0ul);
+    std::vector<unsigned int> range;
+    std::vector<float> results;
+    // a filled range of the neighbour read-out, consumed where it is: its points packed with their velocities into records of
+    // this read-out's own (the fill pass keeps the launch's points in fld_pts), its entries read from the list buffer
+    const NbrConsume consume = [&](unsigned long first, unsigned long lo, unsigned long hi, size_t cap) -> int {
+        const unsigned long npts = hi - lo;
+        RC_TRY(grow(sh, sh.lst_pts, sh.lst_points, 2 * npts));
+        MurbFieldPackArgs pa{};
+        pa.idx = (const int*)(sh.fld_in + 6 * cap) + lo;   // the launch's bodies, as nbr_run staged them
+        pa.rec = sh.rec[c->cur];
+        pa.vel = sh.vel;
+        pa.pts = sh.lst_pts;
+        pa.count = (int)npts;
+        pa.padded = (int)npts;
+        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        RC_TRY(hip_rc(hipGetLastError()));
+        list_range(offsets.data() + first, lo, hi, range);
+        return list_sweep(c, sh, sh.lst_pts, npts, range, out, first + lo, results);
+    };
+    const float* const p[3] = {nullptr, nullptr, nullptr};
+    RC_TRY(nbr_run(c, count, p, bodies, true, thr, offsets.data(), nullptr, nullptr, ~0ul, &consume));
+    for (unsigned long i = 0; counts && i < count; ++i) counts[i] = offsets[i + 1] - offsets[i];
+    return 0;
+}
+
 // ---- include/murbtracer.h
 int murbtracer_validate(unsigned long count, const float* qx, const float* qy, const float* qz, const float* vx, const float* vy,
                         const float* vz)
@@ -4126,11 +4349,11 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr, bind, pot, mst, sep
+        //                                 tracer, knn, nbr, bind, pot, mst, sep, list
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
                                                       "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot",
-                                                      "mst", "sep"};
+                                                      "mst", "sep", "list"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -276,6 +276,20 @@ int murbhost_sim_spanning_tree(void *p, int *i, int *j, float *r2, double *lengt
 }
 // SimulationNBodyHIP::meanSeparation; murbhip's code
 int murbhost_sim_mean_separation(void *p, double *mean) { return static_cast<Sim *>(p)->sim->meanSeparation(mean); }
+// SimulationNBodyHIP::forceSplit: counts (n entries) and irregular, total, regular (7 n floats each: the planes ax ay az jx jy jz phi)
+// where they are given; murbhip's code
+int murbhost_sim_force_split(void *p, float h, unsigned long *counts, float *irregular, float *total, float *regular)
+{
+    std::vector<unsigned long> vc;
+    std::vector<float> vi, vt, vr;
+    const int rc = static_cast<Sim *>(p)->sim->forceSplit(h, vc, vi, vt, vr);
+    if (rc != 0) return rc;
+    if (counts) std::copy(vc.begin(), vc.end(), counts);
+    if (irregular) std::copy(vi.begin(), vi.end(), irregular);
+    if (total) std::copy(vt.begin(), vt.end(), total);
+    if (regular) std::copy(vr.begin(), vr.end(), regular);
+    return 0;
+}
 // SimulationNBodyHIP::binaries: *count and out8 always; i, j (capacity entries) and elems (6 * capacity) where they are given and
 // hold the pairs, else MURBHIP_E_INVALID (-2000) with *count and out8 filled, like murbbind_pairs; murbhip's code
 int murbhost_sim_binaries(void *p, int *i, int *j, double *elems, unsigned long capacity, unsigned long *count, double *out8)

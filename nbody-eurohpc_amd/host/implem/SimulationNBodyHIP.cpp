@@ -12,6 +12,7 @@
 #include "murbfield.h"
 #include "murbhip.h"
 #include "murbknn.h"
+#include "murblist.h"
 #include "murbnbr.h"
 #include "murbtidal.h"
 #include "murbtracer.h"
@@ -150,6 +151,28 @@ int SimulationNBodyHIP<T>::meanSeparation(double *mean)
     const int rc = murbsep_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, sum.data(), 0, 0, 0, nullptr, nullptr);
     if (rc != 0) return rc;
     *mean = sumInOrder(sum) / ((double)n * ((double)n - 1.0));
+    return 0;
+}
+
+template <typename T>
+int SimulationNBodyHIP<T>::forceSplit(float h, std::vector<unsigned long> &counts, std::vector<float> &irregular, std::vector<float> &total,
+                                      std::vector<float> &regular)
+{
+    const unsigned long n = this->getBodies()->getN();
+    counts.assign(n, 0ul);
+    irregular.assign(7 * n, 0.f);
+    total.assign(7 * n, 0.f);
+    regular.assign(7 * n, 0.f);
+    if (n == 0) return 0;
+    float *const i = irregular.data(), *const t = total.data();
+    int rc = murbsplit_of(hipBodiesPtr->getContext(), n, nullptr, nullptr, h, counts.data(), i, i + n, i + 2 * n, i + 3 * n, i + 4 * n,
+                          i + 5 * n, i + 6 * n);
+    if (rc != 0) return rc;
+    std::vector<int> all(n);
+    for (unsigned long b = 0; b < n; ++b) all[b] = (int)b;
+    rc = murbfield_of(hipBodiesPtr->getContext(), n, all.data(), t, t + n, t + 2 * n, t + 3 * n, t + 4 * n, t + 5 * n, t + 6 * n);
+    if (rc != 0) return rc;
+    for (unsigned long e = 0; e < 7 * n; ++e) regular[e] = (float)((double)total[e] - (double)irregular[e]);
     return 0;
 }
 

@@ -71,6 +71,13 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     // fieldAt; returns murbhip's code.
     int meanSeparation(double *mean);
 
+    // The neighbour split of every body's force as the bodies are on the device (murbsplit_of's rules, include/murblist.h): counts
+    // gets the n neighbour counts within h; irregular, total and regular 7 n floats each, the planes ax ay az jx jy jz phi one
+    // after the other: the force of the neighbours alone, murbfield_of's of all other bodies, and total - irregular formed in
+    // double and rounded once.  A read-out like fieldAt; returns murbhip's code.
+    int forceSplit(float h, std::vector<unsigned long> &counts, std::vector<float> &irregular, std::vector<float> &total,
+                   std::vector<float> &regular);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

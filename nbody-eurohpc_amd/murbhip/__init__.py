@@ -106,6 +106,10 @@ def lib():
         L.murbnbr_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
         L.murbnbr_threshold.argtypes = [C.c_float, C.c_float, _fp]
         L.murbnbr_cut.argtypes = [C.c_ulong, _up, C.c_ulong, C.c_ulong, _up]
+        # include/murblist.h
+        L.murblist_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _up, _ip] + [_fp] * 7
+        L.murblist_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [_up, _ip] + [_fp] * 7
+        L.murbsplit_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _fp, C.c_float, _up] + [_fp] * 7
         # include/murbbind.h
         _dp = C.POINTER(C.c_double)
         L.murbbind_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _ip, _fp]
@@ -186,6 +190,7 @@ MST_EXPORTS = "murbforeign_of murbmst_of murbmst_round murbmst_cut".split()   # 
 MST_KEYS = ("members", "edges", "components", "rounds", "total_length", "mean_length", "longest_length")
 SEP_EXPORTS = "murbsep_of murbsep_at murbsep_bin murbsep_edges".split()   # include/murbsep.h
 SEP_KEYS = ("pairs", "below", "above")
+LIST_EXPORTS = "murblist_of murblist_at murbsplit_of".split()   # include/murblist.h
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -403,6 +408,47 @@ def fof_groups(offsets, idx):
         if np.array_equal(new, label):
             return label.astype(np.int32)
         label = new
+
+
+def _csr(offsets, idx, count):
+    """(offsets uint64, idx int32) of a CSR pair for `count` points, contiguous; ValueError where the shapes disagree."""
+    o = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+    j = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    if o.shape != (count + 1,):
+        raise ValueError("offsets holds one entry per point and one more")
+    if j.shape[0] != int(o[-1]):
+        raise ValueError("idx holds offsets[-1] entries")
+    return o, j
+
+
+def complement_lists(n, bodies, offsets, idx):
+    """(offsets uint64, idx int32): for every listed body p every OTHER body of the n that is not in its list
+    idx[offsets[p]:offsets[p + 1]], in ascending index, the body itself left out.  Host only, numpy.  The sources of the regular
+    force of an Ahmad-Cohen split, for Simulation.list_field_of: irregular (the list) + regular (this) = every other body once."""
+    n = int(n)
+    b = np.asarray(bodies, np.int64).reshape(-1)
+    if b.size and (b.min() < 0 or b.max() >= n):
+        raise ValueError("a body index outside [0, n)")
+    o, j = _csr(offsets, idx, b.shape[0])
+    if j.size and (j.min() < 0 or j.max() >= n):
+        raise ValueError("a list entry outside [0, n)")
+    if o[0] != 0 or np.any(np.diff(o.astype(np.int64)) < 0):
+        raise ValueError("offsets start at 0 and do not decrease")
+    out_o = np.zeros(b.shape[0] + 1, np.uint64)
+    parts = []
+    for p in range(b.shape[0]):
+        keep = np.ones(n, bool)
+        keep[j[int(o[p]):int(o[p + 1])]] = False
+        keep[b[p]] = False
+        parts.append(np.flatnonzero(keep).astype(np.int32))
+        out_o[p + 1] = out_o[p] + np.uint64(parts[-1].shape[0])
+    return out_o, (np.concatenate(parts) if parts else np.zeros(0, np.int32))
+
+
+def split_regular(total, irregular):
+    """field_of's dict of the regular force: total - irregular per key, formed in fp64 and rounded once to float32 (host only)."""
+    return {k: (np.asarray(total[k], np.float32).astype(np.float64) - np.asarray(irregular[k], np.float32).astype(np.float64)).astype(np.float32)
+            for k in Simulation._FIELD_KEYS}
 
 
 def mst_round(label, partner, r2):
@@ -1040,6 +1086,55 @@ class Simulation:
         _check(lib().murbnbr_get_option(self._h, key.encode(), C.byref(f)), f"murbnbr_get_option({key})")
         return f.value
 
+    # -- the field of listed bodies and the neighbour split (include/murblist.h)
+    def list_field_of(self, bodies, offsets, idx):
+        """field_of's dict from LISTED source bodies alone: body bodies[p] (None: all, in order) feels the bodies
+        idx[offsets[p]:offsets[p + 1]], exactly as given: no entry is skipped, the body itself counts where it is listed, a
+        duplicate counts twice, and the order of the entries decides the order of the fp32 sum (include/murblist.h:
+        murblist_of).  O(list length) per point.  A read-out: synchronous, changes nothing of the simulation."""
+        count, bp = self._knn_bodies(bodies)
+        o, j = _csr(offsets, idx, count)
+        out = {k: np.zeros(count, np.float32) for k in self._FIELD_KEYS}
+        _check(lib().murblist_of(self._h, count, bp, o.ctypes.data_as(C.POINTER(C.c_ulong)), j.ctypes.data_as(C.POINTER(C.c_int)),
+                                 *[_ptr(out[k]) for k in self._FIELD_KEYS]), "murblist_of")
+        return out
+
+    def list_field_at(self, points, velocities, offsets, idx):
+        """list_field_of at `points` (3, count) of the caller's, moving with `velocities` (3, count; None = at rest)
+        (include/murblist.h: murblist_at)."""
+        p = [_f32(x) for x in points]
+        v = [_f32(x) for x in velocities] if velocities is not None else None
+        count = p[0].shape[0]
+        if len(p) != 3 or any(x.shape != (count,) for x in p + (v or [])) or (v is not None and len(v) != 3):
+            raise ValueError("points and velocities are three arrays of one length each")
+        o, j = _csr(offsets, idx, count)
+        out = {k: np.zeros(count, np.float32) for k in self._FIELD_KEYS}
+        _check(lib().murblist_at(self._h, count, *[_ptr(x) for x in p], *([_ptr(x) for x in v] if v else [None] * 3),
+                                 o.ctypes.data_as(C.POINTER(C.c_ulong)), j.ctypes.data_as(C.POINTER(C.c_int)),
+                                 *[_ptr(out[k]) for k in self._FIELD_KEYS]), "murblist_at")
+        return out
+
+    def irregular_field_of(self, bodies=None, h=0.0):
+        """(counts uint64, dict): the field the neighbours within h (a scalar, or one radius per listed body) make at the listed
+        bodies (None: all, in order): list_field_of on neighbours_of's lists, bit for bit, with the lists produced and consumed
+        on the device (include/murblist.h: murbsplit_of)."""
+        count, bp = self._knn_bodies(bodies)
+        keep, hp, h_all = self._nbr_radii(h, count)
+        counts = np.zeros(count, np.uint64)
+        out = {k: np.zeros(count, np.float32) for k in self._FIELD_KEYS}
+        _check(lib().murbsplit_of(self._h, count, bp, hp, h_all, counts.ctypes.data_as(C.POINTER(C.c_ulong)),
+                                  *[_ptr(out[k]) for k in self._FIELD_KEYS]), "murbsplit_of")
+        return counts, out
+
+    def force_split(self, h, bodies=None):
+        """dict of the Ahmad-Cohen split of the listed bodies' (None: all) force at neighbour radius h: counts (uint64, the
+        neighbours), irregular (the neighbours' field, murbsplit_of), total (field_of: all other bodies) and regular =
+        total - irregular, formed in fp64 on the host and rounded once; the three are field_of's dicts."""
+        who = np.arange(self.n, dtype=np.int32) if bodies is None else np.ascontiguousarray(bodies, np.int32).reshape(-1)
+        counts, irregular = self.irregular_field_of(bodies, h)
+        total = self.field_of(who)
+        return {"counts": counts, "irregular": irregular, "total": total, "regular": split_regular(total, irregular)}
+
     # -- massless tracers (include/murbtracer.h)
     def upload_tracers(self, q, v=None):
         """`q` (3, count) positions and `v` (3, count; None = at rest) velocities of massless test particles at the bodies'
@@ -1276,6 +1371,7 @@ def host_lib():
         H.murbhost_sim_bound_members.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), _dp, _dp]
         H.murbhost_sim_spanning_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, C.c_ulong, _dp]
         H.murbhost_sim_mean_separation.argtypes = [C.c_void_p, _dp]
+        H.murbhost_sim_force_split.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong)] + [_fp] * 3
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1473,6 +1569,16 @@ class HostSim:
         mean = C.c_double()
         _check(self.H.murbhost_sim_mean_separation(self.h, C.byref(mean)), "murbhost_sim_mean_separation")
         return mean.value
+
+    def force_split(self, h):
+        """SimulationNBodyHIP::forceSplit: Simulation.force_split(h) of all the plugin's bodies as they are on the device."""
+        counts = np.zeros(self.n, np.uint64)
+        planes = [np.zeros((7, self.n), np.float32) for _ in range(3)]
+        _check(self.H.murbhost_sim_force_split(self.h, float(np.float32(h)), counts.ctypes.data_as(C.POINTER(C.c_ulong)),
+                                               *[_ptr(a) for a in planes]), "murbhost_sim_force_split")
+        keys = Simulation._FIELD_KEYS
+        irregular, total, regular = ({k: a[i] for i, k in enumerate(keys)} for a in planes)
+        return {"counts": counts, "irregular": irregular, "total": total, "regular": regular}
 
     def encounters(self):
         """integrator 3 / 4: dict of the substep that ended the last iteration by an encounter (Simulation.encounters' keys;
