@@ -21,6 +21,7 @@
 #include "murb_kernels_mst.h"     // likewise
 #include "murb_kernels_sep.h"     // likewise
 #include "murb_kernels_list.h"    // likewise
+#include "murb_kernels_ac.h"      // likewise
 #include "murb_rccl.h"
 
 namespace {
@@ -225,6 +226,28 @@ struct Shard {
     size_t lst_ranges = 0;
     float4* lst_pts = nullptr;      // murbsplit_of: a range's packed points: lst_points records
     size_t lst_points = 0;
+    // the Ahmad-Cohen scheme (include/murbac.h): everything it keeps between steps and everything its steps write is its own, so
+    // that the read-outs above (synchronous, on buffers of theirs) stay observers; of the Hermite integrator it uses the predicted
+    // records, the partial rows and the remembered (a0, j0)
+    float4* ac_src = nullptr;       // the predicted bodies in gather form, two records per body: ac_srcs records
+    size_t ac_srcs = 0;
+    float* ac_in = nullptr;         // the rebuild's points as murb_nbr_pack_kernel reads them: n thresholds, then the n bodies: ac_ins floats
+    size_t ac_ins = 0;
+    float4* ac_pts = nullptr;       // ... packed, whole groups: ac_ptss records
+    size_t ac_ptss = 0;
+    unsigned int* ac_part = nullptr;   // the chunks' counts, then their prefix sums per point: ac_parts entries
+    size_t ac_parts = 0;
+    unsigned int* ac_begin[2] = {nullptr, nullptr};   // the two list buffers alternate (old and new lists exist together): per body
+    unsigned int* ac_len[2] = {nullptr, nullptr};     // where its list starts and its length: ac_points entries each ...
+    size_t ac_points[2] = {0, 0};
+    int* ac_idx[2] = {nullptr, nullptr};              // ... and the entries: ac_cap entries
+    size_t ac_cap[2] = {0, 0};
+    float* ac_r2 = nullptr;         // the fill sweep's r2, written and never read: ac_r2s floats
+    size_t ac_r2s = 0;
+    float* ac_out = nullptr;        // two list sweeps' results, seven planes of n each: ac_outs floats
+    size_t ac_outs = 0;
+    float* ac_force = nullptr;      // (aI, jI): 6 planes of n, then (aR, jR, a2R, a3R): 12 planes: ac_forces floats
+    size_t ac_forces = 0;
     unsigned long sym_launches = 0; // pair-symmetric launches of any form since "profile" was last set (force, potential sweep)
     size_t bytes = 0;
 };
@@ -275,6 +298,8 @@ enum ProfKind {
     kProfMst,             // compute stream: a sweep launch of the foreign-nearest read-out (murbmst.h); never part of the force figures
     kProfSep,             // compute stream: a sweep launch of the pair-separation read-out (murbsep.h); never part of the force figures
     kProfList,            // compute stream: a sweep launch of the listed-source read-out (murblist.h); never part of the force figures
+    kProfAcPredict,       // compute stream: the predictor launch of an irregular step of the Ahmad-Cohen scheme (murbac.h)
+    kProfAcCorrect,       // compute stream: the corrector launch of an irregular step, or the last launch of a regular one (murbac.h)
     kProfKinds
 };
 
@@ -327,6 +352,14 @@ struct murbhip_ctx {
     bool trc_current = false;       // their (a0, j0) are those of the tracers' and the bodies' current state
     long tracer_chunks = 0;         // "tracer_chunks", "tracer_batch": the field options' meaning (murb_field.h)
     long tracer_batch = 0;
+    // the Ahmad-Cohen scheme (include/murbac.h)
+    bool ac_live = false;           // murbac_begin has run and nothing has changed the bodies another way since
+    int ac_nirr = 0, ac_m = 0;      // regular steps are every ac_nirr-th; ac_m steps since the last one
+    int ac_buf = 0;                 // which of the two list buffers holds the resident lists
+    unsigned long ac_steps = 0, ac_regular = 0;
+    double ac_time = 0.0;           // the fp64 sum of the steps' dt since murbac_begin
+    std::vector<unsigned long> ac_offsets;   // the resident lists' offsets: n + 1 entries
+    unsigned long ac_longest = 0, ac_empty = 0;
     int tracer_dt = 0;              // "tracer_dt": 1 = the tracers' Aarseth steps enter murbhip_evolve's step-size minimum
     bool lf_half = false;     // leapfrog: device velocities lag the positions by half a step of lf_last_dt
     // acceleration cache: murbhip_compute_acc / a leapfrog read-out evaluated the forces at the CURRENT positions

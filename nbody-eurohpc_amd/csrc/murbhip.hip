@@ -45,6 +45,7 @@
 #include "../../include/murbmst.h"
 #include "../../include/murbnbr.h"
 #include "../../include/murblist.h"
+#include "../../include/murbac.h"
 #include "../../include/murbsep.h"
 #include "../../include/murbtracer.h"
 #include "murb_init.h"
@@ -747,6 +748,7 @@ void invalidate_cached_forces(murbhip_ctx* c)
     c->blk_open = false;        // murbhip_evolve_block: an open block is closed, the bodies' levels are dropped
     c->blk_have_levels = 0;
     c->trc_current = false;     // the tracers' (a0, j0) were made against the old bodies (murbtracer.h)
+    c->ac_live = false;         // an Ahmad-Cohen scheme ends with whatever steps the bodies another way (murbac.h)
     ++c->state_serial;
 }
 
@@ -2551,6 +2553,271 @@ int list_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], co
     return 0;
 }
 
+// ---- the Ahmad-Cohen neighbour scheme (include/murbac.h; kernels: murb_kernels_ac.h, the polynomial: murb_ac.h) ---------------
+// Hermite steps on the compute stream whose full sweep happens on every n_irr-th step only.  Lists, split forces and every
+// buffer a step writes are the scheme's own (Shard::ac_*); of the Hermite integrator it uses the predicted records, the partial
+// rows and the remembered (a0, j0).  The rebuild is the neighbour read-out's kernels (pack, count, rows, fill) as they are, over
+// all bodies in ONE launch each and pointed at the records it is given; its one host round trip reads the counts.
+inline int ac_requirements(const murbhip_ctx* c)
+{
+    const bool ok = c->uploaded && c->integrator == 2 && c->in.world == 1 && c->shards.size() == 1 && !c->force_exchange && !c->blk_open &&
+                    !c->lf_half && !c->tracers && !c->nearest && !c->contact && !c->potential;
+    return ok ? 0 : MURBHIP_E_STATE;
+}
+
+inline size_t ac_padded(const murbhip_ctx* c) { return (c->in.n + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; }
+
+// the buffers whose size the body count fixes; the caller has waited for enqueued work
+int ac_ensure(murbhip_ctx* c, Shard& sh)
+{
+    const size_t n = c->in.n, padded = ac_padded(c);
+    RC_TRY(grow(sh, sh.ac_src, sh.ac_srcs, 2 * n));
+    RC_TRY(grow(sh, sh.ac_in, sh.ac_ins, 2 * n));
+    RC_TRY(grow(sh, sh.ac_pts, sh.ac_ptss, 2 * padded));
+    RC_TRY(grow(sh, sh.ac_out, sh.ac_outs, 14 * n));
+    RC_TRY(grow(sh, sh.ac_force, sh.ac_forces, 18 * n));
+    for (int b = 0; b < 2; ++b) {
+        size_t have = sh.ac_points[b];
+        RC_TRY(grow(sh, sh.ac_begin[b], have, padded));
+        RC_TRY(grow(sh, sh.ac_len[b], sh.ac_points[b], padded));
+    }
+    return 0;
+}
+
+// the gather copy of the state (rec, vel)
+int ac_pack(murbhip_ctx* c, Shard& sh, const float4* rec, const float4* vel)
+{
+    MurbListPackArgs pa{};
+    pa.rec = rec;
+    pa.vel = vel;
+    pa.src = sh.ac_src;
+    pa.count = (int)c->in.n;
+    hipLaunchKernelGGL(murb_list_pack_kernel, dim3((unsigned)((c->in.n + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    return hip_rc(hipGetLastError());
+}
+
+// every body's list field over the lists of buffer `buf`, at its own gather records; asynchronous
+int ac_sweep(murbhip_ctx* c, Shard& sh, int buf, float* out)
+{
+    MurbAcSweepArgs a{};
+    a.src = sh.ac_src;
+    a.begin = sh.ac_begin[buf];
+    a.len = sh.ac_len[buf];
+    a.idx = sh.ac_idx[buf];
+    a.out = out;
+    a.count = (int)c->in.n;
+    a.out_stride = (unsigned int)c->in.n;
+    a.soft2 = c->soft2;
+    int rc = 0;
+    const int sp = span_begin(c, sh, kProfList, sh.compute, &rc);   // "profile" 2: a list span
+    RC_TRY(rc);
+    hipLaunchKernelGGL((murb_ac_sweep_kernel<kListWaves>), dim3((unsigned)((c->in.n + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
+                       sh.compute, a);
+    RC_TRY(span_end(sh, sp, sh.compute));
+    return hip_rc(hipGetLastError());
+}
+
+// The lists of all bodies at the positions `rec`, into list buffer `buf`: begin, length and entries on the device, the offsets
+// and their statistics on the host.  Waits for the stream once, after the count pass.
+int ac_rebuild(murbhip_ctx* c, Shard& sh, const float4* rec, int buf)
+{
+    const size_t n = c->in.n, padded = ac_padded(c);
+    const MurbFieldLayout l = murb_field_layout(n, c->field_chunks, 0);
+    const long grid_full = block_grid(c) / 5 * 4;   // nbr_run's: 4 workgroups per CU
+    MurbNbrPackArgs pa{};
+    pa.thr = sh.ac_in;
+    pa.idx = (const int*)(sh.ac_in + n);
+    pa.rec = rec;
+    pa.pts = sh.ac_pts;
+    pa.count = (int)n;
+    pa.padded = (int)padded;
+    pa.in_stride = (unsigned int)n;
+    MurbNbrArgs na{};
+    na.rec = rec;
+    na.pts = sh.ac_pts;
+    na.groups = (int)(padded / MURB_FIELD_GROUP);
+    na.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + na.groups - 1) / na.groups));   // a list does not depend on the cut
+    na.tiles_each = l.tiles / na.chunks;
+    na.tiles_more = l.tiles % na.chunks;
+    na.count = (int)n;
+    na.stride = (unsigned int)padded;
+    na.soft2 = c->soft2;
+    if ((size_t)na.chunks * padded > sh.ac_parts) {   // "field_chunks" grew: the last rebuild's fill may still read the rows
+        HIP_TRY(hipStreamSynchronize(sh.compute));
+        RC_TRY(grow(sh, sh.ac_part, sh.ac_parts, (size_t)na.chunks * padded));
+    }
+    na.part = sh.ac_part;
+    const unsigned grid = (unsigned)std::max(1l, std::min<long>((long)na.groups * na.chunks, grid_full));
+    const auto sweep = [&](const MurbNbrArgs& a, bool fill) -> int {
+        int rc = 0;
+        const int sp = span_begin(c, sh, kProfNbr, sh.compute, &rc);
+        RC_TRY(rc);
+        if (fill)
+            hipLaunchKernelGGL((murb_nbr_fill_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute, a);
+        else
+            hipLaunchKernelGGL((murb_nbr_count_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute, a);
+        RC_TRY(span_end(sh, sp, sh.compute));
+        return hip_rc(hipGetLastError());
+    };
+    hipLaunchKernelGGL(murb_nbr_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(sweep(na, false));
+    hipLaunchKernelGGL(murb_nbr_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sh.compute, na.part, sh.ac_len[buf], (int)n,
+                       na.chunks, na.stride);
+    RC_TRY(hip_rc(hipGetLastError()));
+    std::vector<unsigned int> counts(n), base(padded, MURB_NBR_NO_BASE);
+    HIP_TRY(hipMemcpyAsync(counts.data(), sh.ac_len[buf], n * sizeof(unsigned int), hipMemcpyDeviceToHost, sh.compute));
+    HIP_TRY(hipStreamSynchronize(sh.compute));   // the one host round trip of a regular step; nothing is in flight behind it
+    std::vector<unsigned long> offsets(n + 1, 0ul);
+    unsigned long longest = 0, empty = 0;
+    for (size_t i = 0; i < n; ++i) {
+        offsets[i + 1] = offsets[i] + counts[i];
+        longest = std::max<unsigned long>(longest, counts[i]);
+        empty += counts[i] == 0u;
+    }
+    const unsigned long total = offsets[n];
+    if (total > 0x7ffffffful) return MURBHIP_E_INVALID;   // the sweeps' places are 32-bit
+    for (size_t i = 0; i < n; ++i) base[i] = (unsigned int)offsets[i];
+    const size_t want = std::max<size_t>(total, 1);
+    RC_TRY(grow(sh, sh.ac_idx[buf], sh.ac_cap[buf], want));
+    RC_TRY(grow(sh, sh.ac_r2, sh.ac_r2s, want));
+    HIP_TRY(hipMemcpy(sh.ac_begin[buf], base.data(), padded * sizeof(unsigned int), hipMemcpyHostToDevice));
+    if (total > 0) {
+        MurbNbrArgs fa = na;
+        fa.base = sh.ac_begin[buf];
+        fa.out_idx = sh.ac_idx[buf];
+        fa.out_r2 = sh.ac_r2;
+        fa.capacity = (unsigned int)std::min<size_t>(sh.ac_cap[buf], sh.ac_r2s);   // >= total: no place lies beyond it
+        RC_TRY(sweep(fa, true));
+    }
+    c->ac_offsets.swap(offsets);
+    c->ac_longest = longest;
+    c->ac_empty = empty;
+    return 0;
+}
+
+MurbAcArgs ac_args(const murbhip_ctx* c, const Shard& sh, int parts, float dt, int elapsed)
+{
+    MurbAcArgs a{};
+    a.h = hermite_args(c, sh, parts, dt, 1);
+    a.h.rec_out = sh.rec[c->cur ^ 1];
+    a.f_cur = sh.ac_out;
+    a.f_new = sh.ac_out + 7 * c->in.n;
+    a.irr = sh.ac_force;
+    a.reg = sh.ac_force + 6 * c->in.n;
+    a.n = (unsigned int)c->in.n;
+    a.elapsed = elapsed;
+    return a;
+}
+
+// what a step of either kind leaves behind: the Hermite step's bookkeeping, with the scheme still live
+void ac_stepped(murbhip_ctx* c, float dt)
+{
+    c->cur ^= 1;
+    invalidate_cached_forces(c);
+    c->herm_current = true;   // (a1, j1) of this step are the next step's (a0, j0)
+    c->herm_in_acc_out = true;
+    c->ac_live = true;
+    ++c->ac_steps;
+    c->ac_time += (double)dt;
+}
+
+// The scheme is over; an extrapolated total is no Hermite evaluation and is not kept as one.  Every call that ends a live
+// scheme without replacing the bodies comes through here: murbac_end, a failed step, and the calls that step the bodies another
+// way (the others go through invalidate_cached_forces, which drops the Hermite memory anyway).
+void ac_finish(murbhip_ctx* c)
+{
+    if (c->ac_live && c->ac_m != 0) { c->herm_current = false; c->herm_proposal = false; }
+    c->ac_live = false;
+}
+
+int ac_irregular_step(murbhip_ctx* c, Shard& sh, int parts, float dt)
+{
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
+    MurbAcPredictArgs pa{};
+    pa.rec = sh.rec[c->cur];
+    pa.vel = sh.vel;
+    pa.a0 = sh.herm_a0;
+    pa.j0 = sh.herm_j0;
+    pa.src = sh.ac_src;
+    pa.count = (int)c->in.n;
+    pa.stride = (unsigned int)c->in.slots;
+    pa.dt = dt;
+    int rc = 0;
+    int sp = span_begin(c, sh, kProfAcPredict, sh.compute, &rc);   // "profile" 2: the two small launches have span kinds of their own
+    RC_TRY(rc);
+    hipLaunchKernelGGL(murb_ac_predict_kernel, dim3((unsigned)((c->in.n + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    RC_TRY(span_end(sh, sp, sh.compute));
+    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(ac_sweep(c, sh, c->ac_buf, sh.ac_out));
+    const MurbAcArgs a = ac_args(c, sh, parts, dt, c->ac_m + 1);
+    sp = span_begin(c, sh, kProfAcCorrect, sh.compute, &rc);
+    RC_TRY(rc);
+    hipLaunchKernelGGL(murb_ac_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    RC_TRY(span_end(sh, sp, sh.compute));
+    RC_TRY(hip_rc(hipGetLastError()));
+    ac_stepped(c, dt);
+    ++c->ac_m;
+    return 0;
+}
+
+int ac_regular_step(murbhip_ctx* c, Shard& sh, int parts, float dt)
+{
+    const unsigned pairs = (unsigned)(c->in.slots / 2);
+    MurbHermiteArgs p = hermite_args(c, sh, parts, dt, 1);
+    p.rec_out = sh.herm_rec;
+    p.vel_out = sh.herm_vel;
+    hipLaunchKernelGGL(murb_hermite_predict_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, p);
+    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(ac_pack(c, sh, sh.herm_rec, sh.herm_vel));
+    RC_TRY(ac_sweep(c, sh, c->ac_buf, sh.ac_out));                          // (aIo, jIo): the old lists
+    RC_TRY(enqueue_hermite_sweep(c, sh, sh.herm_rec, sh.herm_vel, parts));    // the rows of (a1, j1)
+    RC_TRY(ac_rebuild(c, sh, sh.herm_rec, c->ac_buf ^ 1));                  // nothing of the bodies has changed where this fails
+    RC_TRY(ac_sweep(c, sh, c->ac_buf ^ 1, sh.ac_out + 7 * c->in.n));        // (aIn, jIn): the new lists
+    const MurbAcArgs a = ac_args(c, sh, parts, dt, c->ac_nirr);
+    int rc = 0;
+    const int sp = span_begin(c, sh, kProfAcCorrect, sh.compute, &rc);
+    RC_TRY(rc);
+    hipLaunchKernelGGL(murb_ac_regular_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    RC_TRY(span_end(sh, sp, sh.compute));
+    RC_TRY(hip_rc(hipGetLastError()));
+    ac_stepped(c, dt);
+    c->ac_buf ^= 1;
+    c->ac_m = 0;
+    ++c->ac_regular;
+    return 0;
+}
+
+int ac_begin(murbhip_ctx* c, const std::vector<float>& thr, int n_irr)
+{
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    ac_finish(c);
+    const size_t n = c->in.n;
+    const int parts = hermite_parts(c->in);
+    RC_TRY(ac_ensure(c, sh));
+    std::vector<int> all(n);
+    for (size_t i = 0; i < n; ++i) all[i] = (int)i;
+    HIP_TRY(hipMemcpy(sh.ac_in, thr.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sh.ac_in + n, all.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    RC_TRY(enqueue_hermite(c, 0.f, 0));   // (a0, j0): murbhip_compute_acc_jerk's
+    RC_TRY(ac_pack(c, sh, sh.rec[c->cur], sh.vel));
+    RC_TRY(ac_rebuild(c, sh, sh.rec[c->cur], 0));
+    RC_TRY(ac_sweep(c, sh, 0, sh.ac_out + 7 * n));
+    MurbAcArgs a = ac_args(c, sh, parts, 0.f, n_irr);
+    a.begin = 1;
+    hipLaunchKernelGGL(murb_ac_regular_kernel, dim3((unsigned)((c->in.slots / 2 + 255) / 256)), dim3(256), 0, sh.compute, a);
+    RC_TRY(hip_rc(hipGetLastError()));
+    c->ac_live = true;
+    c->ac_nirr = n_irr;
+    c->ac_m = 0;
+    c->ac_buf = 0;
+    c->ac_steps = c->ac_regular = 0;
+    c->ac_time = 0.0;
+    return 0;
+}
+
 // all of a group's pointers, or none of them
 inline bool all_or_none(std::initializer_list<const void*> group)
 {
@@ -2766,6 +3033,8 @@ int murbhip_destroy(murbhip_ctx* c)
         release(sh.mst_label, sh.mst_rec, sh.mst_in, sh.mst_part, sh.mst_idx, sh.mst_r2);
         release(sh.sep_in, sh.sep_member, sh.sep_rec, sh.sep_part, sh.sep_sum, sh.sep_rows, sh.sep_total);
         release(sh.lst_src, sh.lst_range, sh.lst_pts);
+        release(sh.ac_src, sh.ac_in, sh.ac_pts, sh.ac_part, sh.ac_r2, sh.ac_out, sh.ac_force);
+        release(sh.ac_begin[0], sh.ac_begin[1], sh.ac_len[0], sh.ac_len[1], sh.ac_idx[0], sh.ac_idx[1]);
         if (sh.pot_sums_host) (void)hipHostFree(sh.pot_sums_host);
         if (sh.blk_ctl_host) (void)hipHostFree(sh.blk_ctl_host);
         release(sh.sym_items, sh.sym_send, sh.sym_recv, sh.sym_p2p, sh.sym_tri_acc, sh.sym_acc64);
@@ -3638,6 +3907,92 @@ int murbsplit_of(murbhip_ctx* c, unsigned long count, const int* bodies, const f
     return 0;
 }
 
+// ---- include/murbac.h
+int murbac_begin(murbhip_ctx* c, const float* h, float h_all, int n_irr)
+{
+    if (!c || !murb_ac_nirr_valid(n_irr)) return MURBHIP_E_INVALID;
+    std::vector<float> thr;
+    if (!nbr_thresholds(c, c->in.n, h, h_all, thr)) return MURBHIP_E_INVALID;
+    RC_TRY(ac_requirements(c));
+    const int rc = ac_begin(c, thr, n_irr);
+    if (rc) c->ac_live = false;
+    return rc;
+}
+
+int murbac_steps(murbhip_ctx* c, float dt, int steps)
+{
+    if (!c || !std::isfinite(dt) || !(dt > 0.f) || steps < 0) return MURBHIP_E_INVALID;
+    RC_TRY(ac_requirements(c));
+    if (!c->ac_live) return MURBHIP_E_STATE;
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const int parts = hermite_parts(c->in);
+    if (steps > 0) RC_TRY(ensure_hermite(c, sh, parts));
+    for (int i = 0; i < steps; ++i) {
+        const int rc = c->ac_m + 1 < c->ac_nirr ? ac_irregular_step(c, sh, parts, dt) : ac_regular_step(c, sh, parts, dt);
+        if (rc) {   // the bodies stand at the end of the last completed step
+            ac_finish(c);
+            return rc;
+        }
+    }
+    return 0;
+}
+
+int murbac_end(murbhip_ctx* c)
+{
+    if (!c) return MURBHIP_E_INVALID;
+    ac_finish(c);
+    return 0;
+}
+
+int murbac_state(murbhip_ctx* c, double out[16])
+{
+    if (!c || !out) return MURBHIP_E_INVALID;
+    std::fill(out, out + 16, 0.0);
+    if (!c->ac_live) return 0;
+    const double total = (double)c->ac_offsets[c->in.n];
+    const double values[9] = {(double)c->ac_nirr, (double)c->ac_m, (double)c->ac_steps, (double)c->ac_regular, total, (double)c->ac_longest,
+                              (double)c->ac_empty, total / (double)c->in.n, c->ac_time};
+    std::copy(values, values + 9, out);
+    return 0;
+}
+
+int murbac_lists(murbhip_ctx* c, unsigned long* offsets, int* idx, unsigned long capacity)
+{
+    if (!c || !offsets) return MURBHIP_E_INVALID;
+    if (!c->ac_live) return MURBHIP_E_STATE;
+    std::copy(c->ac_offsets.begin(), c->ac_offsets.end(), offsets);
+    if (!idx && capacity == 0) return 0;
+    const unsigned long total = c->ac_offsets[c->in.n];
+    if (!idx || total > capacity) return MURBHIP_E_INVALID;   // idx untouched: the caller sizes it from the offsets
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    if (total) HIP_TRY(hipMemcpy(idx, sh.ac_idx[c->ac_buf], total * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int murbac_forces(murbhip_ctx* c, float* irr[6], float* reg[6], float* reg2[3], float* reg3[3])
+{
+    if (!c) return MURBHIP_E_INVALID;
+    if (!c->ac_live) return MURBHIP_E_STATE;
+    const std::pair<float* const*, int> groups[4] = {{irr, 6}, {reg, 6}, {reg2, 3}, {reg3, 3}};
+    for (const auto& g : groups)
+        for (int k = 0; g.first && k < g.second; ++k)
+            if (!g.first[k]) return MURBHIP_E_INVALID;
+    RC_TRY(murbhip_sync(c));
+    Shard& sh = c->shards[0];
+    HIP_TRY(hipSetDevice(sh.device));
+    const size_t n = c->in.n;
+    size_t plane = 0;   // ac_force: aI jI | aR jR | a2R | a3R, three planes each
+    for (const auto& g : groups) {
+        for (int k = 0; g.first && k < g.second; ++k)
+            HIP_TRY(hipMemcpy(g.first[k], sh.ac_force + (plane + k) * n, n * sizeof(float), hipMemcpyDeviceToHost));
+        plane += g.second;
+    }
+    return 0;
+}
+
 // ---- include/murbtracer.h
 int murbtracer_validate(unsigned long count, const float* qx, const float* qy, const float* qz, const float* vx, const float* vy,
                         const float* vz)
@@ -3785,6 +4140,7 @@ int murbhip_evolve(murbhip_ctx* c, double duration, double eta, double eta_start
         !(dt_max > 0.f) || !(dt_min >= 0.f) || dt_min > dt_max || max_steps == 0)
         return MURBHIP_E_INVALID;
     if (!c->uploaded || c->integrator != 2 || c->blk_open) return MURBHIP_E_STATE;
+    ac_finish(c);                         // murbac.h: these steps end a live scheme, and never start from its extrapolated total
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
     Shard& sh = c->shards[0];
     RC_TRY(enqueue_tracer_evaluation(c, sh));   // murbtracer.h: beside the bodies' starting evaluation, or alone
@@ -3882,6 +4238,7 @@ int murbhip_evolve_block(murbhip_ctx* c, float dt_max, unsigned long blocks, dou
     if (!c->uploaded || c->integrator != 2 || c->tracers) return MURBHIP_E_STATE;   // tracers take no block steps (murbtracer.h)
     if (c->blk_open && (dt_max != c->blk_dt_max || kmax != c->blk_kmax)) return MURBHIP_E_STATE;   // the open block is another grid's
     const bool resume = c->blk_open;
+    ac_finish(c);                         // murbac.h: as in murbhip_evolve
     RC_TRY(enqueue_hermite(c, 0.f, 0));   // refuses several shards; leaves (a0, j0) of the current state remembered
     Shard& sh = c->shards[0];
     RC_TRY(ensure_block(c, sh));
@@ -3972,6 +4329,7 @@ int murbhip_block_set_levels(murbhip_ctx* c, const int* levels, int kmax)
     HIP_TRY(hipStreamSynchronize(sh.compute));
     c->blk_have_levels = 2;
     c->blk_kmax = kmax;
+    ac_finish(c);   // murbac.h: the next steps are block steps
     return 0;
 }
 
@@ -4001,6 +4359,7 @@ int murbhip_steps(murbhip_ctx* c, float dt, int iterations)
 {
     if (!c || iterations < 0) return MURBHIP_E_INVALID;
     if (!c->uploaded || c->blk_open) return MURBHIP_E_STATE;   // an open block (murbhip_evolve_block): the bodies sit at different times
+    if (iterations > 0) ac_finish(c);   // murbac.h: these steps end a live scheme, and never start from its extrapolated total
     for (int i = 0; i < iterations; ++i) {
         if (c->integrator == 2) { RC_TRY(enqueue_hermite(c, dt, 1)); continue; }
         RC_TRY(enqueue_iteration(c, dt, 1));
@@ -4349,11 +4708,11 @@ int murbhip_get_info(murbhip_ctx* c, const char* key, double* value)
         // Timing spans of the profiled steps ("profile"), over all shards of this process:
         //   force_*                       every force launch (one GPU: the launch; exchange pipeline: T1, R and T2 together)
         //   span_<kind>_ms_avg / _count   kind in tri1, rect, tri2, reduce_scatter, all_gather, wait_gather, wait_reduce, step, field, tidal,
-        //                                 tracer, knn, nbr, bind, pot, mst, sep, list
+        //                                 tracer, knn, nbr, bind, pot, mst, sep, list, ac_predict, ac_correct
         //   compute_wait_ms_per_step      (wait_gather + wait_reduce) per profiled step: what the exchange costs the compute stream
         static const char* const names[kProfKinds] = {"force", "tri1", "rect", "tri2", "reduce_scatter", "all_gather", "wait_gather",
                                                       "wait_reduce", "step", "field", "tidal", "tracer", "knn", "nbr", "bind", "pot",
-                                                      "mst", "sep", "list"};
+                                                      "mst", "sep", "list", "ac_predict", "ac_correct"};
         RC_TRY(murbhip_sync(c));
         double total[kProfKinds] = {0};
         size_t count[kProfKinds] = {0};

@@ -75,7 +75,8 @@ void *murbhost_sim_create(unsigned long n, const char *scheme, float soft, float
     return h;
 }
 // --im hip+tracking (leapfrog = 0) / hip+leapfrog (1) / hip+hermite (2): the value is murbhip's option "integrator";
-// hip+hermite+adaptive (3): option 2 driven by murbhip_evolve; hip+hermite+block (4): by murbhip_evolve_block
+// hip+hermite+adaptive (3): option 2 driven by murbhip_evolve; hip+hermite+block (4): by murbhip_evolve_block; hip+hermite+ac (5): by
+// murbac_steps
 void *murbhost_tracking_create(unsigned long n, const char *scheme, float soft, float dt, int leapfrog, int ndev,
                                const int *devices, int exchange)
 {
@@ -130,6 +131,15 @@ int murbhost_sim_substeps(void *p, double *out3)
     out3[2] = t->getLargestDt();
     return 0;
 }
+// hip+hermite+ac (5): SimulationNBodyHIPTracking::setNeighbourScheme.  0, or -1 where it does not apply.
+int murbhost_sim_set_ac(void *p, float rnb, int nirr)
+{
+    auto *t = dynamic_cast<SimulationNBodyHIPTracking<float, double> *>(static_cast<Sim *>(p)->sim);
+    return t && t->setNeighbourScheme(rnb, nirr) ? 0 : -1;
+}
+// SimulationNBodyHIP::acBegin / acSteps on any simulation: murbhip's code
+int murbhost_sim_ac_begin(void *p, float h, int nirr) { return static_cast<Sim *>(p)->sim->acBegin(h, nirr); }
+int murbhost_sim_ac_steps(void *p, float dt, int steps) { return static_cast<Sim *>(p)->sim->acSteps(dt, steps); }
 // hip+hermite+block: accuracy parameter and deepest level, before the first iteration.  0, or -1 for another simulation.
 int murbhost_sim_set_block(void *p, double eta, int kmax)
 {

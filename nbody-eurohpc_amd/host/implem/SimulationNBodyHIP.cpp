@@ -10,6 +10,7 @@
 #include "murbmst.h"
 #include "murbsep.h"
 #include "murbfield.h"
+#include "murbac.h"
 #include "murbhip.h"
 #include "murbknn.h"
 #include "murblist.h"
@@ -152,6 +153,17 @@ int SimulationNBodyHIP<T>::meanSeparation(double *mean)
     if (rc != 0) return rc;
     *mean = sumInOrder(sum) / ((double)n * ((double)n - 1.0));
     return 0;
+}
+
+template <typename T> int SimulationNBodyHIP<T>::acBegin(float h, int nIrr)
+{
+    return murbac_begin(hipBodiesPtr->getContext(), nullptr, h, nIrr);
+}
+
+template <typename T> int SimulationNBodyHIP<T>::acSteps(float dt, int steps)
+{
+    hipBodiesPtr->invalidateDataSoA();
+    return murbac_steps(hipBodiesPtr->getContext(), dt, steps);
 }
 
 template <typename T>

@@ -78,6 +78,12 @@ template <typename T> class SimulationNBodyHIP : public SimulationNBodyInterface
     int forceSplit(float h, std::vector<unsigned long> &counts, std::vector<float> &irregular, std::vector<float> &total,
                    std::vector<float> &regular);
 
+    // The Ahmad-Cohen neighbour scheme on the bodies as they are on the device (murbac_begin's and murbac_steps' arguments and rules,
+    // include/murbac.h; needs the Hermite plugins): acBegin starts it with the common neighbour radius h and a full sweep on every
+    // nIrr-th step, acSteps takes `steps` steps of dt (enqueue only, like computeOneIteration).  Both return murbhip's code.
+    int acBegin(float h, int nIrr);
+    int acSteps(float dt, int steps);
+
     // Massless tracers carried by the Hermite steps on the device (murbtracer_upload's arguments and rules: velocities all three
     // null = at rest, count 0 clears; needs the Hermite plugins, `hip+hermite` or `hip+hermite+adaptive`).  getTracers: the
     // resident tracers' state into arrays of as many entries as getTracerCount gives (null pointers are skipped).  All three return

@@ -11,11 +11,11 @@ SimulationNBodyHIPTracking<T, Q>::SimulationNBodyHIPTracking(const BodiesAllocat
                                                              const int integrator, const std::vector<int> &devices,
                                                              int exchange)
     : SimulationNBodyHIP<T>(allocator, soft, devices, exchange), history{history}, adaptive{integrator == 3 || integrator == 4},
-      blockSteps{integrator == 4}, hermite{integrator >= 2 && integrator <= 4}
+      blockSteps{integrator == 4}, hermite{integrator >= 2 && integrator <= 5}, neighbourScheme{integrator == 5}
 {
     if (!this->history) this->history = std::make_shared<SimulationHistory<Q>>();
     if (integrator)
-        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", adaptive ? 2 : integrator),
+        murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "integrator", adaptive || neighbourScheme ? 2 : integrator),
                      "murbhip_set_option(integrator)");
 }
 
@@ -65,9 +65,17 @@ template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setCont
     return true;
 }
 
+template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setNeighbourScheme(const T radius, const int nIrr)
+{
+    if (!neighbourScheme || acBegun || !(radius >= 0) || !std::isfinite((double)radius) || nIrr < 1 || nIrr > 4096) return false;
+    acRadius = radius;
+    acNirr = nIrr;
+    return true;
+}
+
 template <typename T, typename Q> bool SimulationNBodyHIPTracking<T, Q>::setPotential(const bool on)
 {
-    if (!hermite || (on && (encounterRadius > 0 || contactStop))) return false;
+    if (!hermite || neighbourScheme || (on && (encounterRadius > 0 || contactStop))) return false;
     murbhipCheck(murbhip_set_option(this->hipBodiesPtr->getContext(), "potential", on ? 1 : 0), "murbhip_set_option(potential)");
     potentialOn = on;
     return true;
@@ -133,6 +141,10 @@ template <typename T, typename Q> void SimulationNBodyHIPTracking<T, Q>::compute
         substeps += (unsigned long)out[1];
         if (encounterRadius > 0) readEncounters();
         if (contactStop) readContacts();
+    } else if (neighbourScheme) {   // one step of dt of the neighbour scheme, begun at the first iteration
+        if (!acBegun) murbhipCheck(this->acBegin((float)acRadius, acNirr), "murbac_begin");
+        acBegun = true;
+        murbhipCheck(this->acSteps((float)this->dt, 1), "murbac_steps");
     } else SimulationNBodyHIP<T>::computeOneIteration();
     currentIteration++;
 }

@@ -32,7 +32,11 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     int currentIteration = 0;
     bool adaptive = false;            // integrator 3: "integrator" 2 driven by murbhip_evolve; 4: by murbhip_evolve_block
     bool blockSteps = false;          // integrator 4
-    bool hermite = false;             // integrators 2, 3 and 4: the acceleration + jerk sweeps
+    bool hermite = false;             // integrators 2 to 5: the acceleration + jerk sweeps
+    bool neighbourScheme = false;     // integrator 5: "integrator" 2 driven by murbac_steps (include/murbac.h)
+    bool acBegun = false;             // ... whose scheme the first iteration begins
+    T acRadius = 0;                   // ... with this common neighbour radius
+    int acNirr = 8;                   // ... and a full sweep on every acNirr-th iteration
     bool potentialOn = false;         // ... keep every body's potential beside them (option "potential")
     int kmax = 12;                    // its deepest level (--kmax): steps down to dt 2^-kmax
     unsigned long bodySteps = 0, clampedSteps = 0;   // integrator 4: bodies advanced, and steps the cap was too coarse for
@@ -97,6 +101,10 @@ template <typename T, typename Q = double> class SimulationNBodyHIPTracking : pu
     // (include/murbhip.h has the definition).  Excludes an encounter radius and the contact stop.  false for the other
     // integrators and beside either of the two.
     bool setPotential(const bool on);
+    // hip+hermite+ac (integrator 5): the common neighbour radius and the regular steps' spacing, before the first iteration.
+    // false for the other integrators, after the first iteration, for a radius negative or not finite, for nIrr outside [1, 4096].
+    bool setNeighbourScheme(const T radius, const int nIrr);
+    bool hasNeighbourScheme() const { return neighbourScheme; }
     bool hasPotential() const { return potentialOn; }
     // hip+tracking+density: the history's density_center columns hold the density centre over every body's 6 nearest
     // (densityCentre(6)) instead of the centre of mass.  Every integrator.

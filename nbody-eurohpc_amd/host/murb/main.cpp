@@ -47,6 +47,8 @@ int Kmax = 12;              // --kmax: hip+hermite+block, the deepest level (ste
 float Renc = 0.f;           // --renc: hip+hermite+adaptive / hip+hermite+block, encounter radius (0 = no encounter stop)
 bool Collide = false;       // --collide: hip+hermite+adaptive / hip+hermite+block, stop when two bodies touch (radii times --rscale)
 float Rscale = 1.f;         // --rscale
+float Rnb = 0.f;            // --rnb: hip+hermite+ac, the common neighbour radius
+int Nirr = 8;               // --nirr: hip+hermite+ac, a full sweep on every Nirr-th iteration
 std::shared_ptr<SimulationHistory<double>> History;
 
 // One row per command-line option: tag (as Arguments_reader wants it: "-im" is typed "--im"), name of
@@ -85,6 +87,8 @@ static std::vector<Option> optionTable()
          "\t\t\t                      step criterion asks for (--eta)\n"
          "\t\t\t - \"hip+hermite+block\"  hip+hermite with individual block time steps: every iteration is one block of\n"
          "\t\t\t                      --dt seconds, every body in steps of its own size dt 2^-k, k <= --kmax (--eta)\n"
+         "\t\t\t - \"hip+hermite+ac\"  hip+hermite with an Ahmad-Cohen neighbour scheme: a full sweep on every --nirr-th\n"
+         "\t\t\t                      iteration, the neighbours within --rnb alone on the others\n"
          "\t\t\t ----"},
         {"-soft", "softeningFactor", false, "softening factor."},
         {"s", "bodies scheme", false, "bodies scheme (initial conditions can be \"galaxy\" or \"random\")."},
@@ -98,6 +102,8 @@ static std::vector<Option> optionTable()
         {"-renc", "length", false, "hip+hermite+adaptive / hip+hermite+block: stop when two bodies come within this distance."},
         {"-collide", "", false, "hip+hermite+adaptive / hip+hermite+block: stop when two bodies touch (sum of their radii)."},
         {"-rscale", "factor", false, "--collide: the bodies' radii are multiplied by this factor (default is 1)."},
+        {"-rnb", "length", false, "hip+hermite+ac: neighbour radius (default is 0: no neighbours)."},
+        {"-nirr", "iterations", false, "hip+hermite+ac: a full sweep on every nirr-th iteration, 1 to 4096 (default is 8)."},
     };
 }
 
@@ -162,6 +168,24 @@ static void argsReader(int argc, char **argv)
             exit(-1);
         }
     }
+    if (given("-rnb")) {
+        Rnb = stof(reader.get_argument("-rnb"));
+        if (!(Rnb >= 0.f) || !std::isfinite(Rnb)) {
+            std::cout << "The neighbour radius --rnb must be finite and not negative... exiting." << std::endl;
+            exit(-1);
+        }
+    }
+    if (given("-nirr")) {
+        Nirr = stoi(reader.get_argument("-nirr"));
+        if (Nirr < 1 || Nirr > 4096) {
+            std::cout << "--nirr must be between 1 and 4096... exiting." << std::endl;
+            exit(-1);
+        }
+    }
+    if ((given("-rnb") || given("-nirr")) && ImplTag != "hip+hermite+ac") {
+        std::cout << "--rnb and --nirr need hip+hermite+ac... exiting." << std::endl;
+        exit(-1);
+    }
     if (Collide && Renc > 0.f) {
         std::cout << "--collide cannot be combined with --renc... exiting." << std::endl;
         exit(-1);
@@ -207,10 +231,10 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
                                          use <= visible ? 1 : 0);
     }
     if (ImplTag == "hip+tracking" || ImplTag == "hip+leapfrog" || ImplTag == "hip+hermite" || ImplTag == "hip+hermite+adaptive" ||
-        ImplTag == "hip+hermite+block" || ImplTag == "hip+tracking+density") {
+        ImplTag == "hip+hermite+block" || ImplTag == "hip+hermite+ac" || ImplTag == "hip+tracking+density") {
         // shaped like main.cpp:245-261
         const std::map<std::string, int> integrator = {{"hip+tracking", 0}, {"hip+leapfrog", 1}, {"hip+hermite", 2},
-                                                       {"hip+hermite+adaptive", 3}, {"hip+hermite+block", 4},
+                                                       {"hip+hermite+adaptive", 3}, {"hip+hermite+block", 4}, {"hip+hermite+ac", 5},
                                                        {"hip+tracking+density", 0}};
         HIPBodiesAllocator<T> hipAllocator(NBodies, BodiesScheme);
         History = std::make_shared<SimulationHistory<double>>((int)NIterations);
@@ -218,6 +242,10 @@ template <typename T> static SimulationNBodyHIP<T> *createImplem()
         tracking->setEta(Eta);
         tracking->setKmax(Kmax);
         tracking->setDensityCentre(ImplTag == "hip+tracking+density");
+        if (ImplTag == "hip+hermite+ac" && !tracking->setNeighbourScheme(Rnb, Nirr)) {
+            std::cout << "--rnb must be finite and not negative and --nirr between 1 and 4096... exiting." << std::endl;
+            exit(-1);
+        }
         if (Renc > 0.f && !tracking->setEncounterRadius(Renc)) {
             std::cout << "--renc needs hip+hermite+adaptive or hip+hermite+block... exiting." << std::endl;
             exit(-1);

@@ -110,6 +110,14 @@ def lib():
         L.murblist_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _up, _ip] + [_fp] * 7
         L.murblist_at.argtypes = [C.c_void_p, C.c_ulong] + [_fp] * 6 + [_up, _ip] + [_fp] * 7
         L.murbsplit_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _fp, C.c_float, _up] + [_fp] * 7
+        # include/murbac.h
+        _fpp = C.POINTER(_fp)
+        L.murbac_begin.argtypes = [C.c_void_p, _fp, C.c_float, C.c_int]
+        L.murbac_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
+        L.murbac_end.argtypes = [C.c_void_p]
+        L.murbac_state.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.murbac_lists.argtypes = [C.c_void_p, _up, _ip, C.c_ulong]
+        L.murbac_forces.argtypes = [C.c_void_p, _fpp, _fpp, _fpp, _fpp]
         # include/murbbind.h
         _dp = C.POINTER(C.c_double)
         L.murbbind_of.argtypes = [C.c_void_p, C.c_ulong, _ip, _ip, _fp]
@@ -191,6 +199,9 @@ MST_KEYS = ("members", "edges", "components", "rounds", "total_length", "mean_le
 SEP_EXPORTS = "murbsep_of murbsep_at murbsep_bin murbsep_edges".split()   # include/murbsep.h
 SEP_KEYS = ("pairs", "below", "above")
 LIST_EXPORTS = "murblist_of murblist_at murbsplit_of".split()   # include/murblist.h
+AC_EXPORTS = "murbac_begin murbac_steps murbac_end murbac_state murbac_lists murbac_forces".split()   # include/murbac.h
+AC_STATE_KEYS = ("n_irr", "m", "steps", "regular_steps", "entries", "longest", "empty", "mean", "time")
+AC_NIRR_MAX = 4096
 CENTRE_KEYS = ("x", "r_core", "rho_core", "rho_sum", "used", "left_out")
 
 
@@ -535,6 +546,7 @@ class Simulation:
 
     def __init__(self, n, soft=2e8, g=G, device=0, devices=None, exchange="copy", rank=None, world=None, uid=None):
         self.n = int(n)
+        self.soft = float(np.float32(soft))
         self._h = C.c_void_p()
         L = lib()
         if devices is not None:
@@ -1135,6 +1147,76 @@ class Simulation:
         total = self.field_of(who)
         return {"counts": counts, "irregular": irregular, "total": total, "regular": split_regular(total, irregular)}
 
+    # -- the Ahmad-Cohen neighbour scheme (include/murbac.h)
+    def ac_begin(self, h, n_irr):
+        """Start an Ahmad-Cohen scheme at the current state: neighbour radius h (a scalar, or one radius per body), a full sweep
+        on every n_irr-th step of ac_steps() (include/murbac.h: murbac_begin; "integrator" must be 2)."""
+        keep, hp, h_all = self._nbr_radii(h, self.n)
+        _check(lib().murbac_begin(self._h, hp, h_all, int(n_irr)), "murbac_begin")
+
+    def ac_steps(self, dt, steps):
+        """`steps` Hermite steps of size dt of the live scheme (murbac_steps; enqueue only, sync() waits)."""
+        _check(lib().murbac_steps(self._h, dt, int(steps)), "murbac_steps")
+
+    def ac_end(self):
+        _check(lib().murbac_end(self._h), "murbac_end")
+
+    def ac_state(self):
+        """dict of the live scheme: n_irr, m (steps since the last regular one), steps, regular_steps, entries, longest, empty
+        (ints), mean (entries per list) and time (the fp64 sum of the steps' dt since ac_begin); all 0 without one."""
+        out = (C.c_double * 16)()
+        _check(lib().murbac_state(self._h, out), "murbac_state")
+        d = {k: int(out[e]) for e, k in enumerate(AC_STATE_KEYS[:7])}
+        d["mean"], d["time"] = out[7], out[8]
+        return d
+
+    def ac_lists(self):
+        """(offsets (n + 1) uint64, idx int32): the scheme's resident lists in CSR form (murbac_lists); syncs."""
+        up = C.POINTER(C.c_ulong)
+        offsets = np.zeros(self.n + 1, np.uint64)
+        _check(lib().murbac_lists(self._h, offsets.ctypes.data_as(up), None, 0), "murbac_lists")
+        total = int(offsets[self.n])
+        idx = np.zeros(total, np.int32)
+        if total:
+            _check(lib().murbac_lists(self._h, offsets.ctypes.data_as(up), idx.ctypes.data_as(C.POINTER(C.c_int)), total), "murbac_lists")
+        return offsets, idx
+
+    def ac_forces(self):
+        """dict of (3, n) float32 arrays of the live scheme (murbac_forces; syncs): aI, jI at the current time; aR, jR, a2R, a3R
+        at the time of the last regular step."""
+        planes = np.zeros((18, self.n), np.float32)
+        groups = []
+        for first, count in ((0, 6), (6, 6), (12, 3), (15, 3)):
+            groups.append((_fp * count)(*[_ptr(planes[first + k]) for k in range(count)]))
+        _check(lib().murbac_forces(self._h, *groups), "murbac_forces")
+        return {k: planes[3 * e:3 * e + 3] for e, k in enumerate(("aI", "jI", "aR", "jR", "a2R", "a3R"))}
+
+    def ac_radii(self, k):
+        """float32 radii, one per body, for ac_begin(): the distance to the body's k-th nearest neighbour (knn_of's k-th column),
+        nudged up ulp by ulp until neighbour_threshold() takes that neighbour in, so that body i's list has at least k entries."""
+        k = int(k)
+        if not 1 <= k <= self.n - 1:
+            raise ValueError("k is at least 1 and at most n - 1")
+        soft2 = np.float32(self.soft) * np.float32(self.soft)
+        if k > KNN_KMAX:   # beyond knn_of's columns: the KNN_KMAX-th distance scaled as for a uniform density, then grown by the counts
+            h = (self.ac_radii(KNN_KMAX).astype(np.float64) * (k / KNN_KMAX) ** (1.0 / 3.0)).astype(np.float32)
+            for _ in range(200):
+                short = np.diff(self.neighbours_of(None, h, lists=False)[0].astype(np.int64)) < k
+                if not short.any():
+                    return h
+                h[short] *= np.float32(1.1)
+            raise RuntimeError("ac_radii did not reach k entries per list")
+        r2 = self.knn_of(None, k)[1][:, k - 1]
+        h = np.sqrt(np.maximum(r2.astype(np.float64) - float(soft2), 0.0)).astype(np.float32)
+        for _ in range(64):
+            thr = (h.astype(np.float64) * h.astype(np.float64) + np.float64(soft2)).astype(np.float32)   # neighbour_threshold's formula
+            short = thr < r2
+            if not short.any():
+                break
+            h[short] = np.nextafter(h[short], np.float32(np.inf))
+        assert all(neighbour_threshold(h[i], self.soft) >= r2[i] for i in np.argsort(h)[[0, -1]])
+        return h
+
     # -- massless tracers (include/murbtracer.h)
     def upload_tracers(self, q, v=None):
         """`q` (3, count) positions and `v` (3, count; None = at rest) velocities of massless test particles at the bodies'
@@ -1372,6 +1454,9 @@ def host_lib():
         H.murbhost_sim_spanning_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, C.c_ulong, _dp]
         H.murbhost_sim_mean_separation.argtypes = [C.c_void_p, _dp]
         H.murbhost_sim_force_split.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_ulong)] + [_fp] * 3
+        H.murbhost_sim_set_ac.argtypes = [C.c_void_p, C.c_float, C.c_int]
+        H.murbhost_sim_ac_begin.argtypes = [C.c_void_p, C.c_float, C.c_int]
+        H.murbhost_sim_ac_steps.argtypes = [C.c_void_p, C.c_float, C.c_int]
         H.murbhost_sim_set_tracers.argtypes =[C.c_void_p, C.c_ulong] + [_fp] * 6
         H.murbhost_sim_get_tracers.argtypes = [C.c_void_p, C.POINTER(C.c_ulong)] + [_fp] * 6
         H.murbhost_sim_contacts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_ulong,
@@ -1415,8 +1500,10 @@ class HostSim:
 
     def __init__(self, n, scheme="galaxy", soft=2e8, dt=3600.0, devices=(0,), exchange="rccl", tracking=False,
                  leapfrog=False, integrator=None, eta=0.02, kmax=12, encounter=0.0, contact=False, rscale=1.0, potential=False,
-                 tracers=None, density_centre=False):
-        """density_centre=True (with tracking=True or an integrator): `--im hip+tracking+density`, the history's density_center
+                 tracers=None, density_centre=False, rnb=0.0, nirr=8):
+        """integrator=5: `--im hip+hermite+ac`, option 2 driven by murbac_steps (include/murbac.h): an iteration is one step of
+        dt of the Ahmad-Cohen scheme with the common neighbour radius rnb and a full sweep on every nirr-th iteration.
+        density_centre=True (with tracking=True or an integrator): `--im hip+tracking+density`, the history's density_center
         columns hold density_centre()'s x instead of the centre of mass.
         tracking=True: SimulationNBodyHIPTracking (`--im hip+tracking`; with leapfrog=True `hip+leapfrog`; integrator=
         0, 1 or 2 names the murbhip option "integrator" directly: 2 is `hip+hermite`; 3 is `hip+hermite+adaptive`, option 2
@@ -1454,6 +1541,9 @@ class HostSim:
         self.n = int(self.H.murbhost_sim_n(self.h))
         if integrator == 4:
             self.H.murbhost_sim_set_block(self.h, eta, kmax)
+        if integrator == 5:
+            if self.H.murbhost_sim_set_ac(self.h, rnb, int(nirr)) != 0:
+                raise ValueError("rnb= is finite and not negative, nirr= in [1, 4096]")
         if encounter:
             if self.H.murbhost_sim_set_encounter(self.h, encounter) != 0:
                 raise ValueError("encounter= needs integrator 3 or 4")
@@ -1607,6 +1697,14 @@ class HostSim:
             self.H.murbhost_sim_contacts(self.h, i.ctypes.data_as(ip), j.ctypes.data_as(ip), _ptr(gap2), kept, C.byref(count),
                                          C.byref(time))
         return {"i": i, "j": j, "gap2": gap2, "count": int(count.value), "time": time.value}
+
+    def ac_begin(self, h, n_irr):
+        """SimulationNBodyHIP::acBegin: Simulation.ac_begin with a common radius on the plugin's bodies (needs a Hermite plugin)."""
+        _check(self.H.murbhost_sim_ac_begin(self.h, float(np.float32(h)), int(n_irr)), "murbhost_sim_ac_begin")
+
+    def ac_steps(self, dt, steps):
+        """SimulationNBodyHIP::acSteps: Simulation.ac_steps on the plugin's bodies."""
+        _check(self.H.murbhost_sim_ac_steps(self.h, dt, int(steps)), "murbhost_sim_ac_steps")
 
     def block_counts(self):
         """integrator=4: (block steps so far, body-steps, clamped steps); None for the other plugins."""
