@@ -1,6 +1,7 @@
-// Planning of the field read-out (murbfield_at / murbfield_of; include/murbfield.h has the definition): how the j tiles
-// are cut into chunks and a call's points into launches.  Pure host code that g++ compiles too, so that
-// tests/test_field_host.py checks it through murbfield_layout without a device.
+// Planning of the field read-out (murbfield_at / murbfield_of; include/murbfield.h has the definition) and of every read-out
+// that sweeps packed points the same way: how the j tiles are cut into chunks, a call's points into launches, and one launch
+// into workgroups.  Pure host code that g++ compiles too, so that tests/test_field_host.py checks it through murbfield_layout
+// and a stand-alone program without a device.
 //
 // The rule that matters: the chunk count is a function of the BODY count and of "field_chunks" alone.  A point's partial sums
 // are cut by the chunks, so its bits would otherwise depend on how many points the caller happened to ask for.
@@ -51,6 +52,44 @@ inline MurbFieldLayout murb_field_layout(unsigned long n, long chunks_option, lo
 inline unsigned long murb_field_batches(const MurbFieldLayout& l, unsigned long count)
 {
     return (count + l.batch - 1) / l.batch;
+}
+
+// points rounded up to whole groups of MURB_FIELD_GROUP: the packed records a sweep reads (the filler points are computed and
+// never read back)
+inline unsigned long murb_field_padded(unsigned long points)
+{
+    return (points + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP;
+}
+
+// workgroups of a launch of groups x chunks (group, chunk) units on a chip that holds grid_full of them: workgroup b walks the
+// units b, b + grid, ...
+inline long murb_field_grid(long groups, long chunks, long grid_full)
+{
+    return std::max(1l, std::min(groups * chunks, grid_full));
+}
+
+// How one launch of `padded` points (whole groups, at least one) is cut.
+struct MurbFieldCut {
+    int groups;        // groups of points
+    int chunks;        // j chunks of this launch
+    int tiles_each;    // chunk c holds tiles_each tiles, the first tiles_more chunks one more ...
+    int tiles_more;    // ... for the sweeps that cut by these two rather than by tiles * c / chunks
+    long grid;         // workgroups
+};
+
+// fill_grid false: the layout's chunk count whatever the launch holds, for a result that depends on the cut (a sum: the rule at
+// the top).  fill_grid true: the layout's chunk count is the MOST the launch is cut into, for a result that does not (a list, a
+// count, a minimum).  Every chunk pays its start again, so a launch whose groups fill the chip on their own is not cut at all,
+// and one with fewer groups into as many chunks as fill it.
+inline MurbFieldCut murb_field_cut(const MurbFieldLayout& l, unsigned long padded, long grid_full, bool fill_grid)
+{
+    MurbFieldCut k{};
+    k.groups = (int)(padded / MURB_FIELD_GROUP);
+    k.chunks = fill_grid ? (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + k.groups - 1) / k.groups)) : l.chunks;
+    k.tiles_each = l.tiles / k.chunks;   // chunks <= tiles: every chunk holds a tile
+    k.tiles_more = l.tiles % k.chunks;
+    k.grid = murb_field_grid(k.groups, k.chunks, grid_full);
+    return k;
 }
 
 #endif

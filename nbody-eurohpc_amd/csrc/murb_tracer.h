@@ -35,10 +35,4 @@ inline bool murb_tracer_option_valid(const char* key, long value)
     return false;
 }
 
-// tracers rounded up to whole groups of MURB_FIELD_GROUP: the packed records the sweep reads
-inline unsigned long murb_tracer_padded(unsigned long count)
-{
-    return (count + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP;
-}
-
 #endif

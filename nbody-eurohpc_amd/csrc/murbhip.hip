@@ -160,6 +160,18 @@ int timed_wait(murbhip_ctx* c, Shard& sh, int kind, hipStream_t stream, hipEvent
     HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
     return span_end(sh, sp, stream);
 }
+// One launch on the compute stream as a span of its own kind ("profile" 2: the launch alone), then the launch's error.  `launch`
+// enqueues and returns nothing; timed false: no span (the control-block forms of an adaptive step record none).
+template <typename Enqueue>
+int timed_launch(murbhip_ctx* c, Shard& sh, int kind, Enqueue&& launch, bool timed = true)
+{
+    int rc = 0;
+    const int sp = timed ? span_begin(c, sh, kind, sh.compute, &rc) : -1;
+    RC_TRY(rc);
+    launch();
+    RC_TRY(span_end(sh, sp, sh.compute));
+    return hip_rc(hipGetLastError());
+}
 
 int build_sym_schedule(murbhip_ctx* c, Shard& sh, const Plan& p);
 // The one-sided kernels' partial-sum rows: kMaxParts rows of float4 per local slot, zeroed once (rows a launch does
@@ -895,28 +907,143 @@ int enqueue_hermite_sweep(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
     constexpr int group = kHermiteWaves * kHermiteR;
     const dim3 grid((unsigned)((sh.count + group - 1) / group), (unsigned)parts, 1);   // whole i groups: the extra slots hold mass 0
     void* args[] = {&a, &ctl};   // a kernel takes as many as it has, and of `a` what its parameter's type holds
-    int rc = 0;
-    const int sp = ctl ? -1 : span_begin(c, sh, kProfForce, sh.compute, &rc);
-    RC_TRY(rc);
-    (void)hipLaunchKernel(fixed_sweep_kernel(sweep_side(c), ctl != nullptr), grid, dim3(kHermiteWaves * 64), args, 0, sh.compute);
-    RC_TRY(hip_rc(hipGetLastError()));
-    if (ctl) return 0;
-    RC_TRY(span_end(sh, sp, sh.compute));
-    note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
+    RC_TRY(timed_launch(c, sh, kProfForce, [&] {
+        (void)hipLaunchKernel(fixed_sweep_kernel(sweep_side(c), ctl != nullptr), grid, dim3(kHermiteWaves * 64), args, 0, sh.compute);
+    }, ctl == nullptr));
+    if (!ctl) note_interactions(c, sh, (double)sh.count * (double)c->in.slots);
     return 0;
+}
+
+// ---- a call's points, launch by launch: what the point read-outs and the tracers share (the planning: murb_field.h) -----------
+// Workgroups the chip holds at once: of the active sweep (32 KiB of LDS each: 5 per CU) ...
+inline int block_grid(const murbhip_ctx* c) { return 5 * std::max(c->in.cu_count, 1); }
+// ... and of a sweep that runs 4 waves per SIMD, 4 resident workgroups per CU: every sweep over packed points, and the active sweep
+// with a side product.  murb_field_cut's grid_full.
+inline long sweep_grid(const murbhip_ctx* c) { return block_grid(c) / 5 * 4; }
+
+// The plan of every such call.  Its points go to the device in launches of at most `batch` points, synchronously on the compute
+// stream.  A launch's points [first, first + bn) are staged (stage_points), packed into records in whole groups of
+// MURB_FIELD_GROUP (`padded` of them: the filler records are swept and never read back), swept by a grid that murb_field_cut
+// sizes, and their partial rows folded by the read-out's rows kernel; only the last launch is ragged.  Every buffer of a launch
+// is sized by `cap`, the largest launch's points in whole groups, so a plane of staged input or of results starts at k * cap.
+struct Launch {
+    unsigned long first, bn, padded;
+};
+// for (const Launch ln : Launches{count, batch})
+struct Launches {
+    unsigned long count, batch;
+    struct Iterator {
+        unsigned long count, batch, first;
+        Launch operator*() const
+        {
+            const unsigned long bn = std::min(batch, count - first);
+            return Launch{first, bn, murb_field_padded(bn)};
+        }
+        void operator++() { first += batch; }
+        bool operator!=(const Iterator&) const { return first < count; }
+    };
+    Iterator begin() const { return Iterator{count, batch, 0ul}; }
+    Iterator end() const { return Iterator{count, batch, count}; }
+};
+
+struct PointCall {
+    Shard* sh = nullptr;
+    MurbFieldLayout l{};
+    unsigned long count = 0, batch = 0;
+    size_t cap = 0;
+    long grid_full = 0;
+    std::vector<float> host;   // host_planes planes of `cap` floats, zeroed: a launch's input on its way up, and the caller's to use after
+    std::vector<int> order;    // "all bodies in order" of one launch
+    Launches launches() const { return Launches{count, batch}; }
+};
+
+// The plan of a call of `count` points under layout `l`, in launches of `batch` points.  prepare: wait for enqueued work and select
+// the device first; false where the caller has, and has enqueued what the sweep reads since.
+int point_call(murbhip_ctx* c, bool prepare, const MurbFieldLayout& l, unsigned long batch, unsigned long count, size_t host_planes,
+               PointCall& pc)
+{
+    pc.sh = &c->shards[0];
+    if (prepare) {
+        RC_TRY(murbhip_sync(c));
+        HIP_TRY(hipSetDevice(pc.sh->device));
+    }
+    pc.l = l;
+    pc.count = count;
+    pc.batch = batch;
+    pc.cap = std::min<unsigned long>(batch, murb_field_padded(count));
+    pc.grid_full = sweep_grid(c);
+    pc.host.assign(host_planes * pc.cap, 0.f);
+    return 0;
+}
+inline MurbFieldLayout field_layout(const murbhip_ctx* c) { return murb_field_layout(c->in.n, c->field_chunks, c->field_batch); }
+// ... under "field_chunks" / "field_batch", as every read-out but the pair separations' cuts its calls
+int field_call(murbhip_ctx* c, bool prepare, unsigned long count, size_t host_planes, PointCall& pc)
+{
+    const MurbFieldLayout l = field_layout(c);
+    return point_call(c, prepare, l, l.batch, count, host_planes, pc);
+}
+
+// A launch's input on the device: `in` the float planes at stride cap (null: the points are bodies), `idx` an int per point (the
+// bodies, or the body each point skips; null: none).
+struct StagedPoints {
+    const float* in;
+    const int* idx;
+};
+constexpr int kFieldIntPlane = 6;   // of fld_in's 7 planes: six of floats, then the ints
+
+// Brings launch `ln` of the call to `dev`, a buffer of the caller's with int_plane + 1 planes or more.  of_bodies false: the
+// `nplanes` host planes (a null one stays zero) go to planes [0, nplanes) in one copy, and idx, where set, holds a skip per point.
+// of_bodies true: idx lists the bodies, null standing for all bodies in order (point i is body i).  The ints go to plane
+// int_plane, and stay there until the next launch is staged: murbsplit_of's hook reads the launch's bodies from it.
+int stage_points(PointCall& pc, const Launch& ln, const float* const* planes, int nplanes, const int* idx, bool of_bodies, float* dev,
+                 int int_plane, StagedPoints& st)
+{
+    const size_t cap = pc.cap;
+    if (!of_bodies) {
+        for (int k = 0; k < nplanes; ++k)
+            if (planes[k]) std::memcpy(pc.host.data() + k * cap, planes[k] + ln.first, ln.bn * sizeof(float));
+        HIP_TRY(hipMemcpy(dev, pc.host.data(), nplanes * cap * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const int* list = idx ? idx + ln.first : nullptr;
+    if (of_bodies && !idx) {
+        pc.order.resize(ln.bn);
+        for (unsigned long e = 0; e < ln.bn; ++e) pc.order[e] = (int)(ln.first + e);
+        list = pc.order.data();
+    }
+    int* const dev_idx = (int*)(dev + int_plane * cap);
+    if (list) HIP_TRY(hipMemcpy(dev_idx, list, ln.bn * sizeof(int), hipMemcpyHostToDevice));
+    st.in = of_bodies ? nullptr : dev;
+    st.idx = list ? dev_idx : nullptr;
+    return 0;
+}
+
+// `count` staged points as `padded` packed records at pts (murb_field_pack_kernel: position, velocity where has_vel, the int)
+int pack_points(murbhip_ctx* c, Shard& sh, const StagedPoints& st, float4* pts, unsigned long count, unsigned long padded, size_t in_stride,
+                bool has_vel)
+{
+    MurbFieldPackArgs pa{};
+    pa.in = st.in;
+    pa.idx = st.idx;
+    pa.rec = sh.rec[c->cur];
+    pa.vel = sh.vel;
+    pa.pts = pts;
+    pa.count = (int)count;
+    pa.padded = (int)padded;
+    pa.in_stride = (unsigned int)in_stride;
+    pa.has_vel = has_vel ? 1 : 0;
+    hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    return hip_rc(hipGetLastError());
 }
 
 // ---- massless tracers (include/murbtracer.h; kernels: murb_kernels_tracer.h, host logic: murb_tracer.h) ----------------------
 // Resident beside the bodies on the one shard, carried by the Hermite steps on the compute stream, enqueue-only.  Everything
 // they write is their own; of the context they read the records and velocities a sweep is made at, and soft2.
-inline int block_grid(const murbhip_ctx* c);   // below: workgroups the chip holds at once
-
 inline MurbFieldLayout tracer_layout(const murbhip_ctx* c) { return murb_field_layout(c->in.n, c->tracer_chunks, c->tracer_batch); }
 
 // room for `count` tracers; the caller has waited for enqueued work where buffers are replaced
 int ensure_tracers(Shard& sh, unsigned long count)
 {
-    const size_t cap = murb_tracer_padded(count);
+    const size_t cap = murb_field_padded(count);
     if (cap <= sh.trc_cap) return 0;
     shard_free(sh, sh.trc_state, 18 * sh.trc_cap * sizeof(float));
     shard_free(sh, sh.trc_pts, 2 * sh.trc_cap * sizeof(float4));
@@ -931,7 +1058,7 @@ int ensure_tracers(Shard& sh, unsigned long count)
 int ensure_tracer_rows(murbhip_ctx* c, Shard& sh)
 {
     const MurbFieldLayout l = tracer_layout(c);
-    const size_t rows = std::min<size_t>(l.batch, murb_tracer_padded(c->tracers)) * (size_t)l.chunks;
+    const size_t rows = std::min<size_t>(l.batch, murb_field_padded(c->tracers)) * (size_t)l.chunks;
     if (rows <= sh.trc_rows) return 0;
     HIP_TRY(hipStreamSynchronize(sh.compute));   // an enqueued rows kernel may still read the old ones
     shard_free(sh, sh.trc_part, 2 * sh.trc_rows * sizeof(float4));
@@ -953,7 +1080,7 @@ MurbTracerArgs tracer_args(const murbhip_ctx* c, const Shard& sh, float dt, int 
     a.j1 = sh.trc_state + 15 * cap;
     a.pts = sh.trc_pts;
     a.count = (int)c->tracers;
-    a.padded = (int)murb_tracer_padded(c->tracers);
+    a.padded = (int)murb_field_padded(c->tracers);
     a.stride = (unsigned int)cap;
     a.dt = dt;
     a.predict = predict;
@@ -979,29 +1106,25 @@ int enqueue_tracer_sweeps(murbhip_ctx* c, Shard& sh, const float4* rec, const fl
     const MurbTracerArgs a = tracer_args(c, sh, 0.f, 0);
     float* const out_a = evaluation ? a.a0 : a.a1;
     float* const out_j = evaluation ? a.j0 : a.j1;
-    for (unsigned long first = 0; first < c->tracers; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, c->tracers - first), padded = murb_tracer_padded(bn);
+    const long grid_full = sweep_grid(c);
+    for (const Launch ln : Launches{c->tracers, l.batch}) {
+        const MurbFieldCut cut = murb_field_cut(l, ln.padded, grid_full, false);   // a sum: the layout's chunks whatever the launch holds
         MurbTracerSweepArgs s{};
         s.rec = rec;
         s.vel = vel;
-        s.pts = sh.trc_pts + 2 * first;   // first + padded <= trc_cap: only the last launch is ragged
+        s.pts = sh.trc_pts + 2 * ln.first;   // first + padded <= trc_cap: only the last launch is ragged
         s.part_a = sh.trc_part;
         s.part_j = sh.trc_part + sh.trc_rows;
-        s.groups = (int)(padded / MURB_FIELD_GROUP);
-        s.chunks = l.chunks;
+        s.groups = cut.groups;
+        s.chunks = cut.chunks;
         s.tiles = l.tiles;
-        s.stride = (unsigned int)padded;   // chunks * padded <= trc_rows
+        s.stride = (unsigned int)ln.padded;   // chunks * padded <= trc_rows
         s.soft2 = c->soft2;
-        const long units = (long)s.groups * s.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // the field sweep's: 4 workgroups per CU
-        int rc = 0;
-        const int sp = ctl ? -1 : span_begin(c, sh, kProfTracer, sh.compute, &rc);   // "profile" 2: a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_tracer_sweep_kernel<4, 4, 2>), dim3(grid), dim3(256), 0, sh.compute, s, ctl);
-        RC_TRY(hip_rc(hipGetLastError()));
-        RC_TRY(span_end(sh, sp, sh.compute));
-        hipLaunchKernelGGL(murb_tracer_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const float4*)s.part_a,
-                           (const float4*)s.part_j, out_a + first, out_j + first, (int)bn, s.chunks, s.stride, a.stride, ctl);
+        RC_TRY(timed_launch(c, sh, kProfTracer, [&] {
+            hipLaunchKernelGGL((murb_tracer_sweep_kernel<4, 4, 2>), dim3((unsigned)cut.grid), dim3(256), 0, sh.compute, s, ctl);
+        }, ctl == nullptr));
+        hipLaunchKernelGGL(murb_tracer_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute, (const float4*)s.part_a,
+                           (const float4*)s.part_j, out_a + ln.first, out_j + ln.first, (int)ln.bn, s.chunks, s.stride, a.stride, ctl);
         RC_TRY(hip_rc(hipGetLastError()));
     }
     return 0;
@@ -1109,9 +1232,7 @@ int enqueue_hermite_adaptive(murbhip_ctx* c, Shard& sh, int parts)
 constexpr int kBlockBatch = 64;        // block steps enqueued between two looks at the control block
 constexpr int kBlockMaxUnits = 65536;  // "block_units"
 
-// Workgroups of the active sweep: what the chip holds at once (32 KiB of LDS each: 5 per CU).  The default "block_units"
-// is the same number, one unit per resident workgroup.
-inline int block_grid(const murbhip_ctx* c) { return 5 * std::max(c->in.cu_count, 1); }
+// The default "block_units": one unit per workgroup of the active sweep that the chip holds at once (block_grid).
 inline int block_units(const murbhip_ctx* c) { return c->block_units > 0 ? c->block_units : block_grid(c); }
 
 int ensure_block(murbhip_ctx* c, Shard& sh)
@@ -1169,7 +1290,7 @@ int enqueue_block_step(murbhip_ctx* c, Shard& sh, const MurbBlockArgs& a)
     const MurbSide side = sweep_side(c);
     MurbBlockNNSweepArgs na{};   // the plain sweep takes its base
     na.rec_pred = a.rec_pred; na.vel_pred = a.vel_pred; na.soft2 = a.soft2; na.count = a.count;
-    na.grid = side == MurbSide::None ? block_grid(c) : block_grid(c) / 5 * 4;   // with a side product 4 waves per SIMD: 4 resident workgroups per CU
+    na.grid = side == MurbSide::None ? block_grid(c) : (int)sweep_grid(c);
     na.ctl = sh.blk_ctl;
     const MurbBlockCtl* ctl = sh.blk_ctl;
     void* args[] = {&na, &ctl};   // an error of this launch shows in hipGetLastError below, like the others'
@@ -1405,127 +1526,86 @@ int ensure_field(Shard& sh, size_t points, size_t rows)
 
 // What both entry points share once their arguments are checked.  p: the six input planes (murbfield_at; p[3..5] null:
 // at rest) or all null (murbfield_of: idx are the bodies); out: ax ay az jx jy jz phi, null where not asked for.
-int field_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], const int* idx, bool of_bodies, float* const (&out)[7])
+int field_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, float* const (&out)[7])
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
-    RC_TRY(ensure_field(sh, cap, cap * (size_t)l.chunks));
-    const bool has_vel = p[3] != nullptr;
-    std::vector<float> host(7 * cap, 0.f);
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            const int planes = has_vel ? 6 : 3;
-            for (int k = 0; k < planes; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), planes * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (idx) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, idx + first, bn * sizeof(int), hipMemcpyHostToDevice));
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.fld_in;
-        pa.idx = idx ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = has_vel ? 1 : 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 7, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
+    RC_TRY(ensure_field(sh, cap, cap * (size_t)pc.l.chunks));
+    const bool has_vel = p && p[3];
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, has_vel ? 6 : 3, idx, of_bodies, sh.fld_in, kFieldIntPlane, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, ln.bn, ln.padded, cap, has_vel));
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, false);
         MurbFieldArgs fa{};
         fa.rec = sh.rec[c->cur];
         fa.vel = sh.vel;
         fa.pts = sh.fld_pts;
         fa.part_a = sh.fld_part;
         fa.part_j = sh.fld_part + sh.fld_rows;
-        fa.groups = (int)(padded / MURB_FIELD_GROUP);
-        fa.chunks = l.chunks;
-        fa.tiles = l.tiles;
-        fa.stride = (unsigned int)padded;   // chunks * padded <= fld_rows
+        fa.groups = cut.groups;
+        fa.chunks = cut.chunks;
+        fa.tiles = pc.l.tiles;
+        fa.stride = (unsigned int)ln.padded;   // chunks * padded <= fld_rows
         fa.soft2 = c->soft2;
-        const long units = (long)fa.groups * fa.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // 4 waves per SIMD: 4 workgroups per CU
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfField, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_force_field_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                           sh.compute, fa);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        hipLaunchKernelGGL(murb_field_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute,
-                           (const float4*)fa.part_a, (const float4*)fa.part_j, sh.fld_out, (int)bn, fa.chunks, fa.stride, (unsigned int)cap);
+        RC_TRY(timed_launch(c, sh, kProfField, [&] {
+            hipLaunchKernelGGL((murb_force_field_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)cut.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, fa);
+        }));
+        hipLaunchKernelGGL(murb_field_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)fa.part_a, (const float4*)fa.part_j, sh.fld_out, (int)ln.bn, fa.chunks, fa.stride, (unsigned int)cap);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
         int lo = 7, hi = 0;   // the planes the caller asked for: one copy from the first to the last of them
         for (int k = 0; k < 7; ++k)
             if (out[k]) { lo = std::min(lo, k); hi = k + 1; }
-        if (lo < hi) HIP_TRY(hipMemcpy(host.data() + lo * cap, sh.fld_out + lo * cap, (size_t)(hi - lo) * cap * sizeof(float), hipMemcpyDeviceToHost));
+        float* const host = pc.host.data();
+        if (lo < hi) HIP_TRY(hipMemcpy(host + lo * cap, sh.fld_out + lo * cap, (size_t)(hi - lo) * cap * sizeof(float), hipMemcpyDeviceToHost));
         for (int k = 0; k < 7; ++k)
-            if (out[k]) std::memcpy(out[k] + first, host.data() + k * cap, bn * sizeof(float));
+            if (out[k]) std::memcpy(out[k] + ln.first, host + k * cap, ln.bn * sizeof(float));
     }
     return 0;
 }
 
 // ---- tidal read-out (murbtidal_at / murbtidal_of; kernels: murb_kernels_tidal.h) -----------------------------------
-// field_run with another sweep: the same planning (murb_field_layout under "field_chunks" / "field_batch"), the same batching,
-// the same grid, and the field read-out's own buffers (both calls are synchronous on the compute stream, so neither sees the
-// other's rows).  p: the three position planes (murbtidal_at) or all null (murbtidal_of: idx are the bodies); out: txx tyy
-// tzz txy txz tyz, all set or all null.
-int tidal_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, float* const (&out)[6])
+// Under "field_chunks" / "field_batch" and in the field read-out's own buffers (both calls are synchronous on the compute stream,
+// so neither sees the other's rows).  p: the three position planes (murbtidal_at) or all null (murbtidal_of: idx are the
+// bodies); out: txx tyy tzz txy txz tyz, all set or all null.
+int tidal_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, float* const (&out)[6])
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
-    RC_TRY(ensure_field(sh, cap, cap * (size_t)l.chunks));
-    std::vector<float> host(6 * cap, 0.f);
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (idx) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, idx + first, bn * sizeof(int), hipMemcpyHostToDevice));
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.fld_in;
-        pa.idx = idx ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 6, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
+    RC_TRY(ensure_field(sh, cap, cap * (size_t)pc.l.chunks));
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, 3, idx, of_bodies, sh.fld_in, kFieldIntPlane, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, ln.bn, ln.padded, cap, false));
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, false);
         MurbTidalArgs ta{};
         ta.rec = sh.rec[c->cur];
         ta.pts = sh.fld_pts;
         ta.part_a = sh.fld_part;
         ta.part_b = sh.fld_part + sh.fld_rows;
-        ta.groups = (int)(padded / MURB_FIELD_GROUP);
-        ta.chunks = l.chunks;
-        ta.tiles = l.tiles;
-        ta.stride = (unsigned int)padded;   // chunks * padded <= fld_rows
+        ta.groups = cut.groups;
+        ta.chunks = cut.chunks;
+        ta.tiles = pc.l.tiles;
+        ta.stride = (unsigned int)ln.padded;   // chunks * padded <= fld_rows
         ta.soft2 = c->soft2;
-        const long units = (long)ta.groups * ta.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // field_run's: 4 workgroups per CU
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfTidal, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_tidal_sweep_kernel<kHermiteR, kHermiteWaves, kTidalStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                           sh.compute, ta);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        hipLaunchKernelGGL(murb_tidal_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute,
-                           (const float4*)ta.part_a, (const float4*)ta.part_b, sh.fld_out, (int)bn, ta.chunks, ta.stride, (unsigned int)cap);
+        RC_TRY(timed_launch(c, sh, kProfTidal, [&] {
+            hipLaunchKernelGGL((murb_tidal_sweep_kernel<kHermiteR, kHermiteWaves, kTidalStage>), dim3((unsigned)cut.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, ta);
+        }));
+        hipLaunchKernelGGL(murb_tidal_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)ta.part_a, (const float4*)ta.part_b, sh.fld_out, (int)ln.bn, ta.chunks, ta.stride, (unsigned int)cap);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
         if (!out[0]) continue;
-        HIP_TRY(hipMemcpy(host.data(), sh.fld_out, 6 * cap * sizeof(float), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 6; ++k) std::memcpy(out[k] + first, host.data() + k * cap, bn * sizeof(float));
+        HIP_TRY(hipMemcpy(pc.host.data(), sh.fld_out, 6 * cap * sizeof(float), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; ++k) std::memcpy(out[k] + ln.first, pc.host.data() + k * cap, ln.bn * sizeof(float));
     }
     return 0;
 }
@@ -1544,23 +1624,21 @@ int grow(Shard& sh, T*& p, size_t& have, size_t want)
     return 0;
 }
 
-// field_run with a list in the place of the sums: the same planning (murb_field_layout under "field_chunks" / "field_batch"),
-// the same batching and grid, the field read-out's point buffers, lists and rows of its own.  p: the three position planes
-// (murbknn_at) or all null (of bodies: idx lists them, or null for all n in order).  out_idx, out_r2, out_rho: host arrays, null
-// where not asked for; rho_all: the densities stay on the device, knn_rho[body] (murbdensity_centre; all bodies in order).
-int knn_run(murbhip_ctx* c, int k, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, int* out_idx,
-            float* out_r2, float* out_rho, bool rho_all)
+// A list of the k nearest bodies per point in the place of a sum, in the field read-out's point buffers, with lists and rows of
+// its own.  p: the three position planes (murbknn_at) or null (of bodies: idx lists them, or null for all n in order).  out_idx,
+// out_r2, out_rho: host arrays, null where not asked for; rho_all: the densities stay on the device, knn_rho[body]
+// (murbdensity_centre; all bodies in order).
+int knn_run(murbhip_ctx* c, int k, unsigned long count, const float* const* p, const int* idx, bool of_bodies, int* out_idx, float* out_r2,
+            float* out_rho, bool rho_all)
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 3, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     const bool want_rho = out_rho || rho_all;
     RC_TRY(ensure_field(sh, cap, 0));
     {   // r2 and indices grow together: each pair shares one size
-        const size_t part = cap * (size_t)l.chunks * (size_t)k, list = cap * (size_t)k;
+        const size_t part = cap * (size_t)pc.l.chunks * (size_t)k, list = cap * (size_t)k;
         size_t part_r2 = sh.knn_part, list_r2 = sh.knn_list;
         RC_TRY(grow(sh, sh.knn_part_r2, part_r2, part));
         RC_TRY(grow(sh, sh.knn_part_idx, sh.knn_part, part));
@@ -1568,68 +1646,40 @@ int knn_run(murbhip_ctx* c, int k, unsigned long count, const float* const (&p)[
         RC_TRY(grow(sh, sh.knn_list_idx, sh.knn_list, list));
         if (want_rho) RC_TRY(grow(sh, sh.knn_rho, sh.knn_rhos, rho_all ? std::max<size_t>(count, cap) : cap));
     }
-    std::vector<float> host(3 * cap, 0.f);
-    std::vector<int> all;
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            for (int e = 0; e < 3; ++e) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const int* list = idx ? idx + first : nullptr;
-        if (of_bodies && !idx) {   // all bodies in order
-            all.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
-            list = all.data();
-        }
-        if (list) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.fld_in;
-        pa.idx = list ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, 3, idx, of_bodies, sh.fld_in, kFieldIntPlane, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, ln.bn, ln.padded, cap, false));
+        // a list does not depend on the cut, and every chunk starts its lists empty and pays the slow path's first trips again
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, true);
         MurbKnnArgs ka{};
         ka.rec = sh.rec[c->cur];
         ka.pts = sh.fld_pts;
         ka.part_r2 = sh.knn_part_r2;
         ka.part_idx = sh.knn_part_idx;
-        ka.groups = (int)(padded / MURB_FIELD_GROUP);
-        // The layout's chunk count is the MOST a launch is cut into.  A list, unlike a sum, does not depend on the cut, and
-        // every chunk starts its lists empty and pays the slow path's first trips again: a launch whose groups fill the grid
-        // on their own is not cut at all, one with fewer into as many chunks as fill it.
-        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
-        ka.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + ka.groups - 1) / ka.groups));
-        ka.tiles = l.tiles;
+        ka.groups = cut.groups;
+        ka.chunks = cut.chunks;
+        ka.tiles = pc.l.tiles;
         ka.count = (int)c->in.n;
         ka.k = k;
-        ka.stride = (unsigned int)padded;   // chunks * padded * k <= knn_part
+        ka.stride = (unsigned int)ln.padded;   // chunks * padded * k <= knn_part
         ka.soft2 = c->soft2;
-        const long units = (long)ka.groups * ka.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfKnn, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_knn_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                           sh.compute, ka);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        const dim3 per_point((unsigned)((bn + 255) / 256));
+        RC_TRY(timed_launch(c, sh, kProfKnn, [&] {
+            hipLaunchKernelGGL((murb_knn_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3((unsigned)cut.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, ka);
+        }));
+        const dim3 per_point((unsigned)((ln.bn + 255) / 256));
         hipLaunchKernelGGL(murb_knn_rows_kernel, per_point, dim3(256), 0, sh.compute, (const float*)ka.part_r2,
-                           (const int*)ka.part_idx, sh.knn_list_idx, sh.knn_list_r2, (int)bn, ka.chunks, ka.stride, k);
-        float* const rho = want_rho ? sh.knn_rho + (rho_all ? first : 0ul) : nullptr;
+                           (const int*)ka.part_idx, sh.knn_list_idx, sh.knn_list_r2, (int)ln.bn, ka.chunks, ka.stride, k);
+        float* const rho = want_rho ? sh.knn_rho + (rho_all ? ln.first : 0ul) : nullptr;
         if (rho)
             hipLaunchKernelGGL(murb_knn_density_kernel, per_point, dim3(256), 0, sh.compute, (const int*)sh.knn_list_idx,
-                               (const float*)sh.knn_list_r2, (const float*)sh.mass, rho, (int)bn, k, c->soft2);
+                               (const float*)sh.knn_list_r2, (const float*)sh.mass, rho, (int)ln.bn, k, c->soft2);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first * k, sh.knn_list_idx, bn * k * sizeof(int), hipMemcpyDeviceToHost));
-        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + first * k, sh.knn_list_r2, bn * k * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_rho) HIP_TRY(hipMemcpy(out_rho + first, rho, bn * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + ln.first * k, sh.knn_list_idx, ln.bn * k * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + ln.first * k, sh.knn_list_r2, ln.bn * k * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rho) HIP_TRY(hipMemcpy(out_rho + ln.first, rho, ln.bn * sizeof(float), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -1637,9 +1687,8 @@ int knn_run(murbhip_ctx* c, int k, unsigned long count, const float* const (&p)[
 // The density of every body, then the centre: two launches of block sums, their rows added on the host in index order.
 int knn_centre(murbhip_ctx* c, int k, double* out8)
 {
-    const float* const none[3] = {nullptr, nullptr, nullptr};
     const unsigned long n = c->in.n;
-    RC_TRY(knn_run(c, k, n, none, nullptr, true, nullptr, nullptr, nullptr, true));
+    RC_TRY(knn_run(c, k, n, nullptr, nullptr, true, nullptr, nullptr, nullptr, true));
     Shard& sh = c->shards[0];
     const size_t blocks = (n + 255) / 256;
     RC_TRY(grow(sh, sh.knn_sums, sh.knn_blocks, blocks * MURB_KNN_CENTRE_VALUES));
@@ -1674,23 +1723,46 @@ int knn_centre(murbhip_ctx* c, int k, double* out8)
 }
 
 // ---- neighbours within a radius (include/murbnbr.h; kernels: murb_kernels_nbr.h, the cut: murb_nbr.h) -----------------
-// knn_run's planning, batching, grid and point buffers with a count per point in the place of the list, then (lists asked
-// for, and they fit) a second pass that fills them.  p: the three position planes (murbnbr_at) or all null (of bodies: idx
-// lists them, or null for all n in order).  thr: a threshold per point.  offsets: count + 1 entries.  out_idx, out_r2: host
-// arrays of `capacity` entries, null where not asked for; both null: the count pass alone.
+// A count per point, then (lists asked for, and they fit) a second pass that fills them, in the field read-out's point buffers.
+// p: the three position planes (murbnbr_at) or null (of bodies: idx lists them, or null for all n in order).  thr: a threshold
+// per point.  offsets: count + 1 entries.  out_idx, out_r2: host arrays of `capacity` entries, null where not asked for; both
+// null: the count pass alone.
 // consume (murbsplit_of): called after every filled range [lo, hi) of the launch that starts at point `first`, with the launch's
 // point capacity, while the range's entries sit in the list buffer at offsets[first + e] - offsets[first + lo] and the launch's
-// bodies in fld_in's index plane; the lists then count as asked for and nothing of them is copied to the host.
+// bodies where stage_points left them; the lists then count as asked for and nothing of them is copied to the host.
 using NbrConsume = std::function<int(unsigned long first, unsigned long lo, unsigned long hi, size_t cap)>;
-int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const std::vector<float>& thr,
+
+// the list buffer (nbr_idx, nbr_r2) holds the `total` entries of a range: "list_entries" entries, or a single list that is longer,
+// and never more than the call's `all`
+int list_buffer(Shard& sh, unsigned long entries, unsigned long total, unsigned long all)
+{
+    size_t have = sh.nbr_list;
+    const size_t want = std::max(have, (size_t)std::min<unsigned long>(std::max(entries, total), all));
+    RC_TRY(grow(sh, sh.nbr_idx, have, want));
+    return grow(sh, sh.nbr_r2, sh.nbr_list, want);
+}
+
+// one sweep of the neighbour kernels, counting or filling, as a span
+int nbr_sweep(murbhip_ctx* c, Shard& sh, const MurbNbrArgs& na, long grid, bool fill)
+{
+    return timed_launch(c, sh, kProfNbr, [&] {
+        if (fill)
+            hipLaunchKernelGGL((murb_nbr_fill_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3((unsigned)grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, na);
+        else
+            hipLaunchKernelGGL((murb_nbr_count_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3((unsigned)grid), dim3(kHermiteWaves * 64), 0,
+                               sh.compute, na);
+    });
+}
+
+int nbr_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, const std::vector<float>& thr,
             unsigned long* offsets, int* out_idx, float* out_r2, unsigned long capacity, const NbrConsume* consume = nullptr)
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 4, pc));
+    Shard& sh = *pc.sh;
+    const MurbFieldLayout& l = pc.l;
+    const size_t cap = pc.cap;
     const bool lists = out_idx || out_r2 || consume;
     const unsigned long launches = murb_field_batches(l, count);
     RC_TRY(ensure_field(sh, cap, 0));
@@ -1701,73 +1773,51 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
         RC_TRY(grow(sh, sh.nbr_counts, points, cap));
         RC_TRY(grow(sh, sh.nbr_base, sh.nbr_points, cap));
     }
-    const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
-    std::vector<float> host(4 * cap, 0.f);
-    std::vector<int> all;
     std::vector<unsigned int> counts(cap), base(cap);
+    const float* const planes[4] = {p ? p[0] : nullptr, p ? p[1] : nullptr, p ? p[2] : nullptr, thr.data()};   // the thresholds: a fourth plane
 
-    // uploads and packs the points [first, first + bn) of the call; the sweeps' arguments but for the fill's own
-    const auto stage = [&](unsigned long first, unsigned long bn, MurbNbrArgs& na) -> int {
-        const unsigned long padded = whole_groups(bn);
-        if (!of_bodies)
-            for (int e = 0; e < 3; ++e) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
-        std::memcpy(host.data() + 3 * cap, thr.data() + first, bn * sizeof(float));
-        if (of_bodies) HIP_TRY(hipMemcpy(sh.fld_in + 3 * cap, host.data() + 3 * cap, cap * sizeof(float), hipMemcpyHostToDevice));
-        else HIP_TRY(hipMemcpy(sh.fld_in, host.data(), 4 * cap * sizeof(float), hipMemcpyHostToDevice));
-        const int* list = idx ? idx + first : nullptr;
-        if (of_bodies && !idx) {   // all bodies in order
-            all.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
-            list = all.data();
+    // stages and packs launch `ln`; the sweeps' arguments but for the fill's own
+    const auto stage = [&](const Launch& ln, MurbNbrArgs& na, long& grid) -> int {
+        if (of_bodies) {   // no plane goes up with the bodies: the thresholds alone, to their plane
+            std::memcpy(pc.host.data() + 3 * cap, thr.data() + ln.first, ln.bn * sizeof(float));
+            HIP_TRY(hipMemcpy(sh.fld_in + 3 * cap, pc.host.data() + 3 * cap, cap * sizeof(float), hipMemcpyHostToDevice));
         }
-        if (list) HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, planes, 4, idx, of_bodies, sh.fld_in, kFieldIntPlane, st));
         MurbNbrPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.fld_in;
+        pa.in = st.in;
         pa.thr = sh.fld_in + 3 * cap;
-        pa.idx = list ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
+        pa.idx = st.idx;
         pa.rec = sh.rec[c->cur];
         pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
+        pa.count = (int)ln.bn;
+        pa.padded = (int)ln.padded;
         pa.in_stride = (unsigned int)cap;
-        hipLaunchKernelGGL(murb_nbr_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        hipLaunchKernelGGL(murb_nbr_pack_kernel, dim3((unsigned)((ln.padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        const MurbFieldCut cut = murb_field_cut(l, ln.padded, pc.grid_full, true);   // a count does not depend on the cut
         na = MurbNbrArgs{};
         na.rec = sh.rec[c->cur];
         na.pts = sh.fld_pts;
-        na.part = sh.nbr_part + (lists ? first * (size_t)l.chunks : 0ul);   // first is a multiple of the batch
+        na.part = sh.nbr_part + (lists ? ln.first * (size_t)l.chunks : 0ul);   // first is a multiple of the batch
         na.group_first = 0;
-        na.groups = (int)(padded / MURB_FIELD_GROUP);
-        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a count does not depend on the cut
-        na.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + na.groups - 1) / na.groups));
-        na.tiles_each = l.tiles / na.chunks;   // chunks <= tiles: at least one tile each
-        na.tiles_more = l.tiles % na.chunks;
+        na.groups = cut.groups;
+        na.chunks = cut.chunks;
+        na.tiles_each = cut.tiles_each;
+        na.tiles_more = cut.tiles_more;
         na.count = (int)c->in.n;
-        na.stride = (unsigned int)padded;   // chunks * padded <= the launch's rows
+        na.stride = (unsigned int)ln.padded;   // chunks * padded <= the launch's rows
         na.soft2 = c->soft2;
+        grid = cut.grid;
         return 0;
-    };
-    const auto sweep = [&](const MurbNbrArgs& na, bool fill) -> int {
-        const long units = (long)na.groups * na.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfNbr, sh.compute, &rc);   // "profile" 2: the sweeps alone, a span kind of their own
-        RC_TRY(rc);
-        if (fill)
-            hipLaunchKernelGGL((murb_nbr_fill_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                               sh.compute, na);
-        else
-            hipLaunchKernelGGL((murb_nbr_count_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                               sh.compute, na);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        return hip_rc(hipGetLastError());
     };
 
     offsets[0] = 0;
     MurbNbrArgs na{};
-    for (unsigned long first = 0; first < count; first += l.batch) {   // the count pass
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
-        RC_TRY(stage(first, bn, na));
-        RC_TRY(sweep(na, false));
+    long grid = 0;
+    for (const Launch ln : pc.launches()) {   // the count pass
+        const unsigned long first = ln.first, bn = ln.bn;
+        RC_TRY(stage(ln, na, grid));
+        RC_TRY(nbr_sweep(c, sh, na, grid, false));
         hipLaunchKernelGGL(murb_nbr_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, na.part, sh.nbr_counts,
                            (int)bn, na.chunks, na.stride);
         RC_TRY(hip_rc(hipGetLastError()));
@@ -1779,20 +1829,15 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
     if (offsets[count] > capacity) return MURBHIP_E_INVALID;   // idx and r2 untouched: the caller sizes them from the offsets
 
     const unsigned long entries = murb_nbr_entries(c->nbr_list_entries);
-    for (unsigned long first = 0; first < count; first += l.batch) {   // the fill pass
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
+    for (const Launch ln : pc.launches()) {   // the fill pass
+        const unsigned long first = ln.first, bn = ln.bn;
         if (offsets[first + bn] == offsets[first]) continue;
-        if (launches > 1) RC_TRY(stage(first, bn, na));   // one launch: its points are still packed
+        if (launches > 1) RC_TRY(stage(ln, na, grid));   // one launch: its points are still packed
         for (unsigned long lo = 0, hi; lo < bn; lo = hi) {   // ranges of the launch's points whose lists fit the buffer
             hi = murb_nbr_cut(bn, offsets + first, lo, entries);
             const unsigned long total = offsets[first + hi] - offsets[first + lo];
             if (total == 0) continue;
-            {   // a single list longer than "list_entries" grows the buffer to that list
-                size_t have = sh.nbr_list;
-                const size_t want = std::max(have, (size_t)std::min<unsigned long>(std::max(entries, total), offsets[count]));
-                RC_TRY(grow(sh, sh.nbr_idx, have, want));
-                RC_TRY(grow(sh, sh.nbr_r2, sh.nbr_list, want));
-            }
+            RC_TRY(list_buffer(sh, entries, total, offsets[count]));
             const unsigned long g0 = lo / MURB_FIELD_GROUP, g1 = (hi + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP;
             for (unsigned long e = g0 * MURB_FIELD_GROUP; e < g1 * MURB_FIELD_GROUP; ++e)
                 base[e - g0 * MURB_FIELD_GROUP] = e >= lo && e < hi ? (unsigned int)(offsets[first + e] - offsets[first + lo]) : MURB_NBR_NO_BASE;
@@ -1803,8 +1848,8 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
             fa.out_r2 = sh.nbr_r2;
             fa.capacity = (unsigned int)sh.nbr_list;   // >= total: no place of the range lies beyond it
             fa.group_first = (int)g0;
-            fa.groups = (int)(g1 - g0);
-            RC_TRY(sweep(fa, true));
+            fa.groups = (int)(g1 - g0);   // the range's groups under the launch's cut
+            RC_TRY(nbr_sweep(c, sh, fa, murb_field_grid(fa.groups, fa.chunks, pc.grid_full), true));
             HIP_TRY(hipStreamSynchronize(sh.compute));
             if (out_idx) HIP_TRY(hipMemcpy(out_idx + offsets[first + lo], sh.nbr_idx, total * sizeof(int), hipMemcpyDeviceToHost));
             if (out_r2) HIP_TRY(hipMemcpy(out_r2 + offsets[first + lo], sh.nbr_r2, total * sizeof(float), hipMemcpyDeviceToHost));
@@ -1815,86 +1860,65 @@ int nbr_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], con
 }
 
 // ---- bound pairs (include/murbbind.h; kernels: murb_kernels_bind.h, the elements: murb_bind.h) ----------------------------
-// knn_run's planning, batching, grid and packed-point buffer with one (partner, h) per point in the place of the list.
-// p: the seven input planes px py pz pvx pvy pvz gm (murbbind_at; p[3..5] null: at rest, p[6] null: massless) or all null (of
-// bodies: idx lists them, or null for all n in order).  out_idx, out_h: host arrays, null where not asked for; all: the
-// results stay on the device, bnd_idx / bnd_h [body] (murbbind_pairs; all bodies in order).
-int bind_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[7], const int* idx, bool of_bodies, int* out_idx, float* out_h,
-             bool all)
+// One (partner, h) per point: the most bound partner, a minimum.  The field read-out's packed-point buffer; input, rows and
+// results of its own.  p: the seven input planes px py pz pvx pvy pvz gm (murbbind_at; p[3..5] null: at rest, p[6] null:
+// massless) or null (of bodies: idx lists them, or null for all n in order).  out_idx, out_h: host arrays, null where not asked
+// for; all: the results stay on the device, bnd_idx / bnd_h [body] (murbbind_pairs; all bodies in order).
+int bind_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, int* out_idx, float* out_h, bool all)
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 7, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     RC_TRY(ensure_field(sh, cap, 0));
     {   // partners and h grow together: they share one size
         size_t h_points = sh.bnd_points;
         RC_TRY(grow(sh, sh.bnd_in, sh.bnd_ins, 8 * cap));
-        RC_TRY(grow(sh, sh.bnd_part, sh.bnd_parts, cap * (size_t)l.chunks));
+        RC_TRY(grow(sh, sh.bnd_part, sh.bnd_parts, cap * (size_t)pc.l.chunks));
         RC_TRY(grow(sh, sh.bnd_h, h_points, all ? std::max<size_t>(count, cap) : cap));
         RC_TRY(grow(sh, sh.bnd_idx, sh.bnd_points, all ? std::max<size_t>(count, cap) : cap));
     }
-    const bool has_vel = p[3] != nullptr, has_gm = p[6] != nullptr;
-    std::vector<float> host(7 * cap, 0.f);
-    std::vector<int> every;
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            for (int e = 0; e < 7; ++e)
-                if (p[e]) std::memcpy(host.data() + e * cap, p[e] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.bnd_in, host.data(), 7 * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const int* list = idx ? idx + first : nullptr;
-        if (of_bodies && !idx) {   // all bodies in order
-            every.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
-            list = every.data();
-        }
-        if (list) HIP_TRY(hipMemcpy(sh.bnd_in + 7 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
+    const bool has_vel = p && p[3], has_gm = p && p[6];
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, 7, idx, of_bodies, sh.bnd_in, 7, st));
         MurbBindPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.bnd_in;
-        pa.idx = list ? (const int*)(sh.bnd_in + 7 * cap) : nullptr;
+        pa.in = st.in;
+        pa.idx = st.idx;
         pa.rec = sh.rec[c->cur];
         pa.vel = sh.vel;
         pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
+        pa.count = (int)ln.bn;
+        pa.padded = (int)ln.padded;
         pa.in_stride = (unsigned int)cap;
         pa.has_vel = has_vel ? 1 : 0;
         pa.has_gm = has_gm ? 1 : 0;
-        hipLaunchKernelGGL(murb_bind_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        hipLaunchKernelGGL(murb_bind_pack_kernel, dim3((unsigned)((ln.padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, true);   // a minimum does not depend on the cut
         MurbBindArgs ba{};
         ba.rec = sh.rec[c->cur];
         ba.vel = sh.vel;
         ba.pts = sh.fld_pts;
         ba.part = sh.bnd_part;
-        ba.groups = (int)(padded / MURB_FIELD_GROUP);
-        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a minimum does not depend on the cut
-        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
-        ba.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + ba.groups - 1) / ba.groups));
-        ba.tiles_each = l.tiles / ba.chunks;   // chunks <= tiles: every chunk holds a tile
-        ba.tiles_more = l.tiles % ba.chunks;
+        ba.groups = cut.groups;
+        ba.chunks = cut.chunks;
+        ba.tiles_each = cut.tiles_each;
+        ba.tiles_more = cut.tiles_more;
         ba.count = (int)c->in.n;
-        ba.stride = (unsigned int)padded;   // chunks * padded <= bnd_parts
+        ba.stride = (unsigned int)ln.padded;   // chunks * padded <= bnd_parts
         ba.soft2 = c->soft2;
-        const long units = (long)ba.groups * ba.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfBind, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_bind_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                           sh.compute, ba);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        int* const res_idx = sh.bnd_idx + (all ? first : 0ul);
-        float* const res_h = sh.bnd_h + (all ? first : 0ul);
-        hipLaunchKernelGGL(murb_bind_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)ba.part,
-                           res_idx, res_h, (int)bn, ba.chunks, ba.stride);
+        RC_TRY(timed_launch(c, sh, kProfBind, [&] {
+            hipLaunchKernelGGL((murb_bind_sweep_kernel<kHermiteR, kHermiteWaves, kHermiteStage>), dim3((unsigned)cut.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, ba);
+        }));
+        int* const res_idx = sh.bnd_idx + (all ? ln.first : 0ul);
+        float* const res_h = sh.bnd_h + (all ? ln.first : 0ul);
+        hipLaunchKernelGGL(murb_bind_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)ba.part,
+                           res_idx, res_h, (int)ln.bn, ba.chunks, ba.stride);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first, res_idx, bn * sizeof(int), hipMemcpyDeviceToHost));
-        if (out_h) HIP_TRY(hipMemcpy(out_h + first, res_h, bn * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + ln.first, res_idx, ln.bn * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_h) HIP_TRY(hipMemcpy(out_h + ln.first, res_h, ln.bn * sizeof(float), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -1903,9 +1927,8 @@ int bind_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[7], co
 // here in index order, and the census.  pi, pj, elems: all set (capacity pairs each) or all null.
 int bind_pairs(murbhip_ctx* c, int* pi, int* pj, double* elems, unsigned long capacity, unsigned long* count, double* out8)
 {
-    const float* const none[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const unsigned long n = c->in.n;
-    RC_TRY(bind_run(c, n, none, nullptr, true, nullptr, nullptr, true));
+    RC_TRY(bind_run(c, n, nullptr, nullptr, true, nullptr, nullptr, true));
     Shard& sh = c->shards[0];
     const size_t blocks = (n + 255) / 256;
     RC_TRY(grow(sh, sh.bnd_flag, sh.bnd_flags, (size_t)n));
@@ -1969,76 +1992,50 @@ int pot_upload_mask(murbhip_ctx* c, Shard& sh, const unsigned char* member)
     return 0;
 }
 
-// knn_run's planning, batching, grid and packed-point buffer with one float per point in the place of the list.  p: the three
-// position planes (murbpot_at) or all null (of bodies: idx lists them, or null for all n in order).  masked: the j side is the
-// masked copy (pot_mask has run on the compute stream).  out: a host array, or null; all: the results stay on the device,
-// pot_phi[body] (murbbound_members; all bodies in order).
-int pot_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, bool masked, float* out,
-            bool all)
+// One potential per point, a sum, in the field read-out's packed-point buffer; input, rows and results of its own.  The caller
+// has prepared the stream.  p: the three position planes (murbpot_at) or null (of bodies: idx lists them, or null for all n in
+// order).  masked: the j side is the masked copy (pot_mask has run on the compute stream).  out: a host array, or null; all: the
+// results stay on the device, pot_phi[body] (murbbound_members; all bodies in order).
+int pot_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, bool masked, float* out, bool all)
 {
-    Shard& sh = c->shards[0];
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, false, count, 3, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     RC_TRY(ensure_field(sh, cap, 0));
     RC_TRY(grow(sh, sh.pot_in, sh.pot_ins, 4 * cap));
-    RC_TRY(grow(sh, sh.pot_part, sh.pot_parts, cap * (size_t)l.chunks));
+    RC_TRY(grow(sh, sh.pot_part, sh.pot_parts, cap * (size_t)pc.l.chunks));
     RC_TRY(grow(sh, sh.pot_phi, sh.pot_phis, all ? std::max<size_t>(count, cap) : cap));
-    std::vector<float> host(3 * cap, 0.f);
-    std::vector<int> every;
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.pot_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const int* list = idx ? idx + first : nullptr;
-        if (of_bodies && !idx) {   // all bodies in order
-            every.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
-            list = every.data();
-        }
-        if (list) HIP_TRY(hipMemcpy(sh.pot_in + 3 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.pot_in;
-        pa.idx = list ? (const int*)(sh.pot_in + 3 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, 3, idx, of_bodies, sh.pot_in, 3, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, ln.bn, ln.padded, cap, false));
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, false);   // a sum depends on the cut
         MurbPotArgs ta{};
         ta.rec = masked ? sh.pot_rec : sh.rec[c->cur];
         ta.pts = sh.fld_pts;
         ta.part = sh.pot_part;
-        ta.groups = (int)(padded / MURB_FIELD_GROUP);
-        ta.chunks = l.chunks;   // the field read-out's cut: a sum depends on it
-        ta.tiles = l.tiles;
-        ta.stride = (unsigned int)padded;   // chunks * padded <= pot_parts
+        ta.groups = cut.groups;
+        ta.chunks = cut.chunks;
+        ta.tiles = pc.l.tiles;
+        ta.stride = (unsigned int)ln.padded;   // chunks * padded <= pot_parts
         ta.soft2 = c->soft2;
-        const long units = (long)ta.groups * ta.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, block_grid(c) / 5 * 4));   // field_run's: 4 workgroups per CU
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfPot, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_pot_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute,
-                           ta);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        float* const res = sh.pot_phi + (all ? first : 0ul);
-        hipLaunchKernelGGL(murb_pot_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const float*)ta.part, res,
-                           (int)bn, ta.chunks, ta.stride);
+        RC_TRY(timed_launch(c, sh, kProfPot, [&] {
+            hipLaunchKernelGGL((murb_pot_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3((unsigned)cut.grid), dim3(kHermiteWaves * 64),
+                               0, sh.compute, ta);
+        }));
+        float* const res = sh.pot_phi + (all ? ln.first : 0ul);
+        hipLaunchKernelGGL(murb_pot_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute, (const float*)ta.part, res,
+                           (int)ln.bn, ta.chunks, ta.stride);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        if (out) HIP_TRY(hipMemcpy(out + first, res, bn * sizeof(float), hipMemcpyDeviceToHost));
+        if (out) HIP_TRY(hipMemcpy(out + ln.first, res, ln.bn * sizeof(float), hipMemcpyDeviceToHost));
     }
     return 0;
 }
 
 // murbpot_of / murbpot_at once their arguments are checked
-int pot_call(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const unsigned char* member,
+int pot_call(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, const unsigned char* member,
              float* phi)
 {
     RC_TRY(murbhip_sync(c));
@@ -2061,7 +2058,6 @@ int bound_members(murbhip_ctx* c, const unsigned char* start, const double* fram
     HIP_TRY(hipSetDevice(sh.device));
     const unsigned long n = c->in.n;
     const size_t blocks = (n + 255) / 256;
-    const float* const none[3] = {nullptr, nullptr, nullptr};
     RC_TRY(grow(sh, sh.pot_e, sh.pot_es, (size_t)n));
     RC_TRY(grow(sh, sh.pot_rows, sh.pot_row, blocks * (MURB_BOUND_SUMS + 1)));
     {
@@ -2095,7 +2091,7 @@ int bound_members(murbhip_ctx* c, const unsigned char* start, const double* fram
     };
     const auto evaluate = [&](bool update) -> int {
         RC_TRY(pot_mask(c, sh));
-        RC_TRY(pot_run(c, n, none, nullptr, true, true, nullptr, true));
+        RC_TRY(pot_run(c, n, nullptr, nullptr, true, true, nullptr, true));
         hipLaunchKernelGGL(murb_bound_energy_kernel, dim3((unsigned)blocks), dim3(256), 0, sh.compute, (const float4*)sh.vel,
                            (const float*)sh.pot_phi, sh.pot_member, sh.pot_e, removed_dev, (int)n, update ? 1 : 0, V[0], V[1], V[2]);
         return hip_rc(hipGetLastError());
@@ -2148,60 +2144,49 @@ int foreign_labels(murbhip_ctx* c, Shard& sh, const int* label)
     return hip_rc(hipGetLastError());
 }
 
-// knn_run's planning, batching, grid and packed-point buffer with one (partner, r2) per point in the place of the list.  The
-// points are listed bodies (idx, or null for all n in order); foreign_labels has run on the compute stream.
+// One (partner, r2) per point: the nearest body of another label, a minimum.  The field read-out's packed-point buffer; bodies,
+// rows and results of its own.  The caller has prepared the stream, and foreign_labels has run on it.  The points are listed
+// bodies (idx, or null for all n in order).
 int foreign_run(murbhip_ctx* c, unsigned long count, const int* idx, int* out_idx, float* out_r2)
 {
-    Shard& sh = c->shards[0];
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, false, count, 0, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     RC_TRY(ensure_field(sh, cap, 0));
     {   // partners and r2 grow together: they share one size
         size_t r2_points = sh.mst_points;
         RC_TRY(grow(sh, sh.mst_in, sh.mst_ins, cap));
-        RC_TRY(grow(sh, sh.mst_part, sh.mst_parts, cap * (size_t)l.chunks));
+        RC_TRY(grow(sh, sh.mst_part, sh.mst_parts, cap * (size_t)pc.l.chunks));
         RC_TRY(grow(sh, sh.mst_r2, r2_points, cap));
         RC_TRY(grow(sh, sh.mst_idx, sh.mst_points, cap));
     }
-    std::vector<int> every;
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first), padded = whole_groups(bn);
-        const int* list = idx ? idx + first : nullptr;
-        if (!idx) {   // all bodies in order
-            every.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
-            list = every.data();
-        }
-        HIP_TRY(hipMemcpy(sh.mst_in, list, bn * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(murb_foreign_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute,
-                           (const float4*)sh.rec[c->cur], (const int*)sh.mst_label, (const int*)sh.mst_in, sh.fld_pts, (int)bn, (int)padded);
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;   // mst_in is the one plane, of ints
+        RC_TRY(stage_points(pc, ln, nullptr, 0, idx, true, (float*)sh.mst_in, 0, st));
+        hipLaunchKernelGGL(murb_foreign_pack_kernel, dim3((unsigned)((ln.padded + 255) / 256)), dim3(256), 0, sh.compute,
+                           (const float4*)sh.rec[c->cur], (const int*)sh.mst_label, st.idx, sh.fld_pts, (int)ln.bn, (int)ln.padded);
+        const MurbFieldCut cut = murb_field_cut(pc.l, ln.padded, pc.grid_full, true);   // a minimum does not depend on the cut
         MurbForeignArgs fa{};
         fa.rec = sh.mst_rec;
         fa.pts = sh.fld_pts;
         fa.part = sh.mst_part;
-        fa.groups = (int)(padded / MURB_FIELD_GROUP);
-        // like knn_run: the layout's chunk count is the MOST a launch is cut into; a minimum does not depend on the cut
-        const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
-        fa.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + fa.groups - 1) / fa.groups));
-        fa.tiles_each = l.tiles / fa.chunks;   // chunks <= tiles: every chunk holds a tile
-        fa.tiles_more = l.tiles % fa.chunks;
-        fa.stride = (unsigned int)padded;   // chunks * padded <= mst_parts
+        fa.groups = cut.groups;
+        fa.chunks = cut.chunks;
+        fa.tiles_each = cut.tiles_each;
+        fa.tiles_more = cut.tiles_more;
+        fa.stride = (unsigned int)ln.padded;   // chunks * padded <= mst_parts
         fa.soft2 = c->soft2;
-        const long units = (long)fa.groups * fa.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfMst, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        hipLaunchKernelGGL((murb_foreign_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                           sh.compute, fa);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        hipLaunchKernelGGL(murb_foreign_rows_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)fa.part,
-                           (const float4*)sh.fld_pts, sh.mst_idx, sh.mst_r2, (int)bn, fa.chunks, fa.stride);
+        RC_TRY(timed_launch(c, sh, kProfMst, [&] {
+            hipLaunchKernelGGL((murb_foreign_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3((unsigned)cut.grid),
+                               dim3(kHermiteWaves * 64), 0, sh.compute, fa);
+        }));
+        hipLaunchKernelGGL(murb_foreign_rows_kernel, dim3((unsigned)((ln.bn + 255) / 256)), dim3(256), 0, sh.compute, (const uint2*)fa.part,
+                           (const float4*)sh.fld_pts, sh.mst_idx, sh.mst_r2, (int)ln.bn, fa.chunks, fa.stride);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        if (out_idx) HIP_TRY(hipMemcpy(out_idx + first, sh.mst_idx, bn * sizeof(int), hipMemcpyDeviceToHost));
-        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + first, sh.mst_r2, bn * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_idx) HIP_TRY(hipMemcpy(out_idx + ln.first, sh.mst_idx, ln.bn * sizeof(int), hipMemcpyDeviceToHost));
+        if (out_r2) HIP_TRY(hipMemcpy(out_r2 + ln.first, sh.mst_r2, ln.bn * sizeof(float), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -2294,22 +2279,20 @@ int mst_call(murbhip_ctx* c, const unsigned char* member, unsigned long capacity
 }
 
 // ---- pair separations (include/murbsep.h; kernels: murb_kernels_sep.h, the bins and the launch cut: murb_sep.h) ---------------
-// murbsep_of / murbsep_at once their arguments are checked.  pot_run's planning, grid and packed-point buffer; the launches are
-// cut by murb_sep_cut, so that no 32-bit counter of a workgroup can wrap.  p: the three position planes (murbsep_at) or all null
-// (of bodies: idx lists them, or null for all n in order).  bins == 0: the sum-only sweep.
-int sep_call(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], const int* idx, bool of_bodies, const unsigned char* member,
+// murbsep_of / murbsep_at once their arguments are checked.  A sum per point and, with bins, a histogram, in the field read-out's
+// packed-point buffer; the launches are cut by murb_sep_cut, so that no 32-bit counter of a workgroup can wrap.  p: the three
+// position planes (murbsep_at) or null (of bodies: idx lists them, or null for all n in order).  bins == 0: the sum-only sweep.
+int sep_call(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, const unsigned char* member,
              double* sum, int lo_exp, int sub, int bins, unsigned long long* hist, unsigned long long* out4)
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
     const unsigned long n = c->in.n;
-    const MurbFieldLayout l = murb_field_layout(n, c->field_chunks, c->field_batch);
-    const long grid_full = block_grid(c) / 5 * 4;   // field_run's: 4 workgroups per CU
-    const unsigned long batch = murb_sep_cut(l, grid_full);
-    if (batch == 0) return MURBHIP_E_INVALID;   // one group of points against the longest chunk would pass 2^32 pairs
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(batch, whole_groups(count));
+    const MurbFieldLayout l = field_layout(c);
+    const long grid_full = sweep_grid(c);
+    PointCall pc;
+    RC_TRY(point_call(c, true, l, murb_sep_cut(l, grid_full), count, of_bodies ? 0 : 3, pc));
+    if (pc.batch == 0) return MURBHIP_E_INVALID;   // one group of points against the longest chunk would pass 2^32 pairs
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     const int width = bins > 0 ? MURB_SEP_TABLE : 0;   // the table's slots: below | the bins | above, the rest above too
     const size_t pairs = (size_t)l.tiles * MURB_TILE_PAIRS, records = (size_t)l.tiles * MURB_TILE_F4;
     RC_TRY(ensure_field(sh, cap, 0));
@@ -2332,64 +2315,39 @@ int sep_call(murbhip_ctx* c, unsigned long count, const float* const (&p)[3], co
     hipLaunchKernelGGL(murb_sep_mask_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, sh.compute, (const float4*)sh.rec[c->cur],
                        member ? (const unsigned char*)sh.sep_member : nullptr, sh.sep_rec, (int)n, (unsigned int)pairs);
     RC_TRY(hip_rc(hipGetLastError()));
-    std::vector<float> host(of_bodies ? 0 : 3 * cap, 0.f);
-    std::vector<int> every;
     unsigned long long not_counted = 0;   // entries the slots outside S and the filler points left in the table's last slot
-    for (unsigned long first = 0; first < count; first += batch) {
-        const unsigned long bn = std::min<unsigned long>(batch, count - first), padded = whole_groups(bn);
-        if (!of_bodies) {
-            for (int k = 0; k < 3; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.sep_in, host.data(), 3 * cap * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const int* list = idx ? idx + first : nullptr;
-        if (of_bodies && !idx) {   // all bodies in order
-            every.resize(bn);
-            for (unsigned long e = 0; e < bn; ++e) every[e] = (int)(first + e);
-            list = every.data();
-        }
-        if (of_bodies) HIP_TRY(hipMemcpy(sh.sep_in + 3 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.sep_in;
-        pa.idx = of_bodies ? (const int*)(sh.sep_in + 3 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)padded;
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    for (const Launch ln : pc.launches()) {
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, 3, idx, of_bodies, sh.sep_in, 3, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, ln.bn, ln.padded, cap, false));
+        const MurbFieldCut cut = murb_field_cut(l, ln.padded, grid_full, false);   // a sum depends on the cut; grid * width <= sep_row
         MurbSepArgs ta{};
         ta.rec = sh.sep_rec;
         ta.pts = sh.fld_pts;
         ta.part = sh.sep_part;
         ta.rows = sh.sep_rows;
-        ta.groups = (int)(padded / MURB_FIELD_GROUP);
-        ta.chunks = l.chunks;   // the field read-out's cut: a sum depends on it
+        ta.groups = cut.groups;
+        ta.chunks = cut.chunks;
         ta.tiles = l.tiles;
-        ta.count = (int)bn;
-        ta.stride = (unsigned int)padded;   // chunks * padded <= sep_parts
+        ta.count = (int)ln.bn;
+        ta.stride = (unsigned int)ln.padded;   // chunks * padded <= sep_parts
         ta.sh = murb_sep_shift(sub);
         ta.minus4 = -4 * (murb_sep_base(lo_exp, sub) - 1);
-        const long units = (long)ta.groups * ta.chunks;
-        const unsigned grid = (unsigned)std::max(1l, std::min<long>(units, grid_full));   // grid * width <= sep_row
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfSep, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-        RC_TRY(rc);
-        if (width)
-            hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, true>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                               sh.compute, ta);
-        else
-            hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, false>), dim3(grid), dim3(kHermiteWaves * 64), 0,
-                               sh.compute, ta);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        const unsigned long threads = std::max<unsigned long>(bn, (unsigned long)width);
+        RC_TRY(timed_launch(c, sh, kProfSep, [&] {
+            if (width)
+                hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, true>), dim3((unsigned)cut.grid),
+                                   dim3(kHermiteWaves * 64), 0, sh.compute, ta);
+            else
+                hipLaunchKernelGGL((murb_sep_sweep_kernel<kHermiteR, kHermiteWaves, kKnnStage, false>), dim3((unsigned)cut.grid),
+                                   dim3(kHermiteWaves * 64), 0, sh.compute, ta);
+        }));
+        const unsigned long threads = std::max<unsigned long>(ln.bn, (unsigned long)width);
         hipLaunchKernelGGL(murb_sep_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, sh.compute, (const float*)ta.part,
-                           sh.sep_sum, (int)bn, ta.chunks, ta.stride, (const unsigned int*)sh.sep_rows, sh.sep_total, width, (int)grid);
+                           sh.sep_sum, (int)ln.bn, ta.chunks, ta.stride, (const unsigned int*)sh.sep_rows, sh.sep_total, width, (int)cut.grid);
         RC_TRY(hip_rc(hipGetLastError()));
         HIP_TRY(hipStreamSynchronize(sh.compute));
-        if (sum) HIP_TRY(hipMemcpy(sum + first, sh.sep_sum, bn * sizeof(double), hipMemcpyDeviceToHost));
-        not_counted += (unsigned long long)padded * ((unsigned long long)l.tiles * MURB_TILE_BODIES) - (unsigned long long)bn * in_set;
+        if (sum) HIP_TRY(hipMemcpy(sum + ln.first, sh.sep_sum, ln.bn * sizeof(double), hipMemcpyDeviceToHost));
+        not_counted += (unsigned long long)ln.padded * ((unsigned long long)l.tiles * MURB_TILE_BODIES) - (unsigned long long)ln.bn * in_set;
     }
     if (!width) return 0;
     std::vector<unsigned long long> total((size_t)width);
@@ -2449,13 +2407,10 @@ int list_sweep(murbhip_ctx* c, Shard& sh, const float4* pts, unsigned long npts,
     la.count = (int)npts;
     la.out_stride = (unsigned int)npts;
     la.soft2 = c->soft2;
-    int rc = 0;
-    const int sp = span_begin(c, sh, kProfList, sh.compute, &rc);   // "profile" 2: the sweep alone, a span kind of its own
-    RC_TRY(rc);
-    hipLaunchKernelGGL((murb_list_sweep_kernel<kListWaves>), dim3((unsigned)((npts + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
-                       sh.compute, la);
-    RC_TRY(span_end(sh, sp, sh.compute));
-    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(timed_launch(c, sh, kProfList, [&] {
+        hipLaunchKernelGGL((murb_list_sweep_kernel<kListWaves>), dim3((unsigned)((npts + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
+                           sh.compute, la);
+    }));
     HIP_TRY(hipStreamSynchronize(sh.compute));
     host.resize(7 * npts);
     HIP_TRY(hipMemcpy(host.data(), sh.fld_out, 7 * npts * sizeof(float), hipMemcpyDeviceToHost));
@@ -2475,67 +2430,33 @@ void list_range(const unsigned long* offsets, unsigned long lo, unsigned long hi
     }
 }
 
-// the list buffer holds `total` entries of a range: nbr_run's rule (a single list longer than "list_entries" grows it)
-int list_buffer(Shard& sh, unsigned long entries, unsigned long total, unsigned long all)
-{
-    size_t have = sh.nbr_list;
-    const size_t want = std::max(have, (size_t)std::min<unsigned long>(std::max(entries, total), all));
-    RC_TRY(grow(sh, sh.nbr_idx, have, want));
-    return grow(sh, sh.nbr_r2, sh.nbr_list, want);
-}
-
-// What murblist_of and murblist_at share once their arguments are checked.  field_run's batching ("field_batch") and pack step;
-// inside a launch the points are cut into ranges whose entries fit the list buffer (murb_nbr_cut under "list_entries"), staged
-// there and swept.  p: the six input planes (murblist_at; p[3..5] null: at rest) or all null (murblist_of: idx are the bodies,
-// or null for all n in order).
-int list_run(murbhip_ctx* c, unsigned long count, const float* const (&p)[6], const int* idx, bool of_bodies, const unsigned long* offsets,
+// What murblist_of and murblist_at share once their arguments are checked.  The launches and the packed points are the field
+// read-out's; inside a launch the points are cut into ranges whose entries fit the list buffer (murb_nbr_cut under
+// "list_entries"), staged there and swept.  p: the six input planes (murblist_at; p[3..5] null: at rest) or null (murblist_of: idx
+// are the bodies, or null for all n in order).
+int list_run(murbhip_ctx* c, unsigned long count, const float* const* p, const int* idx, bool of_bodies, const unsigned long* offsets,
              const int* entries_in, float* const (&out)[7])
 {
-    RC_TRY(murbhip_sync(c));
-    Shard& sh = c->shards[0];
-    HIP_TRY(hipSetDevice(sh.device));
-    const MurbFieldLayout l = murb_field_layout(c->in.n, c->field_chunks, c->field_batch);
-    const auto whole_groups = [](unsigned long v) { return (v + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; };
-    const size_t cap = std::min<unsigned long>(l.batch, whole_groups(count));
+    PointCall pc;
+    RC_TRY(field_call(c, true, count, 6, pc));
+    Shard& sh = *pc.sh;
+    const size_t cap = pc.cap;
     RC_TRY(ensure_field(sh, cap, 0));
     RC_TRY(list_pack(c, sh));
     const unsigned long entries = murb_nbr_entries(c->nbr_list_entries);
-    const bool has_vel = p[3] != nullptr;
-    std::vector<float> host(6 * cap, 0.f), results;
-    std::vector<int> all;
+    const bool has_vel = p && p[3];
+    std::vector<float> results;
     std::vector<unsigned int> range;
-    for (unsigned long first = 0; first < count; first += l.batch) {
-        const unsigned long bn = std::min<unsigned long>(l.batch, count - first);
+    for (const Launch ln : pc.launches()) {
+        const unsigned long first = ln.first, bn = ln.bn;
         if (offsets[first + bn] == offsets[first]) {   // empty lists alone: +0 seven times
             for (int k = 0; k < 7; ++k)
                 if (out[k]) std::fill(out[k] + first, out[k] + first + bn, 0.f);
             continue;
         }
-        if (!of_bodies) {
-            const int planes = has_vel ? 6 : 3;
-            for (int k = 0; k < planes; ++k) std::memcpy(host.data() + k * cap, p[k] + first, bn * sizeof(float));
-            HIP_TRY(hipMemcpy(sh.fld_in, host.data(), planes * cap * sizeof(float), hipMemcpyHostToDevice));
-        } else {
-            const int* list = idx ? idx + first : nullptr;
-            if (!list) {   // all bodies in order
-                all.resize(bn);
-                for (unsigned long e = 0; e < bn; ++e) all[e] = (int)(first + e);
-                list = all.data();
-            }
-            HIP_TRY(hipMemcpy(sh.fld_in + 6 * cap, list, bn * sizeof(int), hipMemcpyHostToDevice));
-        }
-        MurbFieldPackArgs pa{};
-        pa.in = of_bodies ? nullptr : sh.fld_in;
-        pa.idx = of_bodies ? (const int*)(sh.fld_in + 6 * cap) : nullptr;
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.fld_pts;
-        pa.count = (int)bn;
-        pa.padded = (int)bn;   // a wave takes one point: no group to fill up
-        pa.in_stride = (unsigned int)cap;
-        pa.has_vel = has_vel ? 1 : 0;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, sh.compute, pa);
-        RC_TRY(hip_rc(hipGetLastError()));
+        StagedPoints st;
+        RC_TRY(stage_points(pc, ln, p, has_vel ? 6 : 3, idx, of_bodies, sh.fld_in, kFieldIntPlane, st));
+        RC_TRY(pack_points(c, sh, st, sh.fld_pts, bn, bn, cap, has_vel));   // a wave takes one point: no group to fill up
         for (unsigned long lo = 0, hi; lo < bn; lo = hi) {
             hi = murb_nbr_cut(bn, offsets + first, lo, entries);
             const unsigned long total = offsets[first + hi] - offsets[first + lo];
@@ -2565,12 +2486,10 @@ inline int ac_requirements(const murbhip_ctx* c)
     return ok ? 0 : MURBHIP_E_STATE;
 }
 
-inline size_t ac_padded(const murbhip_ctx* c) { return (c->in.n + MURB_FIELD_GROUP - 1) / MURB_FIELD_GROUP * MURB_FIELD_GROUP; }
-
 // the buffers whose size the body count fixes; the caller has waited for enqueued work
 int ac_ensure(murbhip_ctx* c, Shard& sh)
 {
-    const size_t n = c->in.n, padded = ac_padded(c);
+    const size_t n = c->in.n, padded = murb_field_padded(n);
     RC_TRY(grow(sh, sh.ac_src, sh.ac_srcs, 2 * n));
     RC_TRY(grow(sh, sh.ac_in, sh.ac_ins, 2 * n));
     RC_TRY(grow(sh, sh.ac_pts, sh.ac_ptss, 2 * padded));
@@ -2608,22 +2527,18 @@ int ac_sweep(murbhip_ctx* c, Shard& sh, int buf, float* out)
     a.count = (int)c->in.n;
     a.out_stride = (unsigned int)c->in.n;
     a.soft2 = c->soft2;
-    int rc = 0;
-    const int sp = span_begin(c, sh, kProfList, sh.compute, &rc);   // "profile" 2: a list span
-    RC_TRY(rc);
-    hipLaunchKernelGGL((murb_ac_sweep_kernel<kListWaves>), dim3((unsigned)((c->in.n + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
-                       sh.compute, a);
-    RC_TRY(span_end(sh, sp, sh.compute));
-    return hip_rc(hipGetLastError());
+    return timed_launch(c, sh, kProfList, [&] {   // a list span
+        hipLaunchKernelGGL((murb_ac_sweep_kernel<kListWaves>), dim3((unsigned)((c->in.n + kListWaves - 1) / kListWaves)), dim3(kListWaves * 64), 0,
+                           sh.compute, a);
+    });
 }
 
 // The lists of all bodies at the positions `rec`, into list buffer `buf`: begin, length and entries on the device, the offsets
 // and their statistics on the host.  Waits for the stream once, after the count pass.
 int ac_rebuild(murbhip_ctx* c, Shard& sh, const float4* rec, int buf)
 {
-    const size_t n = c->in.n, padded = ac_padded(c);
-    const MurbFieldLayout l = murb_field_layout(n, c->field_chunks, 0);
-    const long grid_full = block_grid(c) / 5 * 4;   // nbr_run's: 4 workgroups per CU
+    const size_t n = c->in.n, padded = murb_field_padded(n);
+    const MurbFieldCut cut = murb_field_cut(murb_field_layout(n, c->field_chunks, 0), padded, sweep_grid(c), true);   // a list does not depend on the cut
     MurbNbrPackArgs pa{};
     pa.thr = sh.ac_in;
     pa.idx = (const int*)(sh.ac_in + n);
@@ -2635,10 +2550,10 @@ int ac_rebuild(murbhip_ctx* c, Shard& sh, const float4* rec, int buf)
     MurbNbrArgs na{};
     na.rec = rec;
     na.pts = sh.ac_pts;
-    na.groups = (int)(padded / MURB_FIELD_GROUP);
-    na.chunks = (int)std::min<long>(l.chunks, std::max<long>(1, (grid_full + na.groups - 1) / na.groups));   // a list does not depend on the cut
-    na.tiles_each = l.tiles / na.chunks;
-    na.tiles_more = l.tiles % na.chunks;
+    na.groups = cut.groups;
+    na.chunks = cut.chunks;
+    na.tiles_each = cut.tiles_each;
+    na.tiles_more = cut.tiles_more;
     na.count = (int)n;
     na.stride = (unsigned int)padded;
     na.soft2 = c->soft2;
@@ -2647,21 +2562,9 @@ int ac_rebuild(murbhip_ctx* c, Shard& sh, const float4* rec, int buf)
         RC_TRY(grow(sh, sh.ac_part, sh.ac_parts, (size_t)na.chunks * padded));
     }
     na.part = sh.ac_part;
-    const unsigned grid = (unsigned)std::max(1l, std::min<long>((long)na.groups * na.chunks, grid_full));
-    const auto sweep = [&](const MurbNbrArgs& a, bool fill) -> int {
-        int rc = 0;
-        const int sp = span_begin(c, sh, kProfNbr, sh.compute, &rc);
-        RC_TRY(rc);
-        if (fill)
-            hipLaunchKernelGGL((murb_nbr_fill_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute, a);
-        else
-            hipLaunchKernelGGL((murb_nbr_count_kernel<kHermiteR, kHermiteWaves, kKnnStage>), dim3(grid), dim3(kHermiteWaves * 64), 0, sh.compute, a);
-        RC_TRY(span_end(sh, sp, sh.compute));
-        return hip_rc(hipGetLastError());
-    };
     hipLaunchKernelGGL(murb_nbr_pack_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, sh.compute, pa);
     RC_TRY(hip_rc(hipGetLastError()));
-    RC_TRY(sweep(na, false));
+    RC_TRY(nbr_sweep(c, sh, na, cut.grid, false));
     hipLaunchKernelGGL(murb_nbr_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sh.compute, na.part, sh.ac_len[buf], (int)n,
                        na.chunks, na.stride);
     RC_TRY(hip_rc(hipGetLastError()));
@@ -2688,7 +2591,7 @@ int ac_rebuild(murbhip_ctx* c, Shard& sh, const float4* rec, int buf)
         fa.out_idx = sh.ac_idx[buf];
         fa.out_r2 = sh.ac_r2;
         fa.capacity = (unsigned int)std::min<size_t>(sh.ac_cap[buf], sh.ac_r2s);   // >= total: no place lies beyond it
-        RC_TRY(sweep(fa, true));
+        RC_TRY(nbr_sweep(c, sh, fa, cut.grid, true));
     }
     c->ac_offsets.swap(offsets);
     c->ac_longest = longest;
@@ -2743,19 +2646,14 @@ int ac_irregular_step(murbhip_ctx* c, Shard& sh, int parts, float dt)
     pa.count = (int)c->in.n;
     pa.stride = (unsigned int)c->in.slots;
     pa.dt = dt;
-    int rc = 0;
-    int sp = span_begin(c, sh, kProfAcPredict, sh.compute, &rc);   // "profile" 2: the two small launches have span kinds of their own
-    RC_TRY(rc);
-    hipLaunchKernelGGL(murb_ac_predict_kernel, dim3((unsigned)((c->in.n + 255) / 256)), dim3(256), 0, sh.compute, pa);
-    RC_TRY(span_end(sh, sp, sh.compute));
-    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(timed_launch(c, sh, kProfAcPredict, [&] {   // the two small launches have span kinds of their own
+        hipLaunchKernelGGL(murb_ac_predict_kernel, dim3((unsigned)((c->in.n + 255) / 256)), dim3(256), 0, sh.compute, pa);
+    }));
     RC_TRY(ac_sweep(c, sh, c->ac_buf, sh.ac_out));
     const MurbAcArgs a = ac_args(c, sh, parts, dt, c->ac_m + 1);
-    sp = span_begin(c, sh, kProfAcCorrect, sh.compute, &rc);
-    RC_TRY(rc);
-    hipLaunchKernelGGL(murb_ac_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
-    RC_TRY(span_end(sh, sp, sh.compute));
-    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(timed_launch(c, sh, kProfAcCorrect, [&] {
+        hipLaunchKernelGGL(murb_ac_correct_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    }));
     ac_stepped(c, dt);
     ++c->ac_m;
     return 0;
@@ -2775,12 +2673,9 @@ int ac_regular_step(murbhip_ctx* c, Shard& sh, int parts, float dt)
     RC_TRY(ac_rebuild(c, sh, sh.herm_rec, c->ac_buf ^ 1));                  // nothing of the bodies has changed where this fails
     RC_TRY(ac_sweep(c, sh, c->ac_buf ^ 1, sh.ac_out + 7 * c->in.n));        // (aIn, jIn): the new lists
     const MurbAcArgs a = ac_args(c, sh, parts, dt, c->ac_nirr);
-    int rc = 0;
-    const int sp = span_begin(c, sh, kProfAcCorrect, sh.compute, &rc);
-    RC_TRY(rc);
-    hipLaunchKernelGGL(murb_ac_regular_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
-    RC_TRY(span_end(sh, sp, sh.compute));
-    RC_TRY(hip_rc(hipGetLastError()));
+    RC_TRY(timed_launch(c, sh, kProfAcCorrect, [&] {
+        hipLaunchKernelGGL(murb_ac_regular_kernel, dim3((pairs + 255) / 256), dim3(256), 0, sh.compute, a);
+    }));
     ac_stepped(c, dt);
     c->ac_buf ^= 1;
     c->ac_m = 0;
@@ -2824,6 +2719,32 @@ inline bool all_or_none(std::initializer_list<const void*> group)
     size_t set = 0;
     for (const void* q : group) set += q != nullptr;
     return set == 0 || set == group.size();
+}
+
+// The argument checks the entry points of the point read-outs share.  Each entry point keeps the order null context, count == 0,
+// field_state, arguments, which decides the error a caller sees.
+// every listed body in [0, n); no list: all n bodies in order where the entry point takes that (count == n), refused where not
+inline bool bodies_valid(const murbhip_ctx* c, unsigned long count, const int* bodies, bool null_is_all)
+{
+    if (!bodies) return null_is_all && count == c->in.n;
+    for (unsigned long i = 0; i < count; ++i)
+        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return false;
+    return true;
+}
+// every coordinate of every plane finite; a null plane is one the caller may leave out
+inline bool planes_finite(unsigned long count, std::initializer_list<const float*> planes)
+{
+    for (const float* q : planes)
+        for (unsigned long i = 0; q && i < count; ++i)
+            if (!std::isfinite(q[i])) return false;
+    return true;
+}
+// every skip entry a body or -1 (none); no list: no point skips a body
+inline bool skips_valid(const murbhip_ctx* c, unsigned long count, const int* skip)
+{
+    for (unsigned long i = 0; skip && i < count; ++i)
+        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return false;
+    return true;
 }
 
 inline int field_state(const murbhip_ctx* c)
@@ -3388,11 +3309,8 @@ int murbfield_at(murbhip_ctx* c, unsigned long count, const float* px, const flo
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz}) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz, pvx, pvy, pvz})
-        for (unsigned long i = 0; q && i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz, pvx, pvy, pvz})) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     const float* const p[6] = {px, py, pz, pvx, pvy, pvz};
     float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
     return field_run(c, count, p, skip, false, out);
@@ -3404,12 +3322,9 @@ int murbfield_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* 
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!bodies || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    const float* const p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!bodies_valid(c, count, bodies, false) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
     float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
-    return field_run(c, count, p, bodies, true, out);
+    return field_run(c, count, nullptr, bodies, true, out);
 }
 
 int murbfield_layout(unsigned long n, long chunks_option, long batch_option, unsigned long* out4)
@@ -3431,7 +3346,7 @@ int murbfield_set_option(murbhip_ctx* c, const char* key, long value)
     if (k != "field_chunks" && k != "field_batch") return MURBHIP_E_INVALID;
     const bool chunks = k == "field_chunks";
     if (!murb_field_options_valid(chunks ? value : 0, chunks ? 0 : value)) return MURBHIP_E_INVALID;
-    (chunks ? c->field_chunks : c->field_batch) = value;   // read by the field and tidal read-outs alone
+    (chunks ? c->field_chunks : c->field_batch) = value;   // read through field_layout by every point read-out
     return 0;
 }
 
@@ -3453,11 +3368,8 @@ int murbtidal_at(murbhip_ctx* c, unsigned long count, const float* px, const flo
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !all_or_none({txx, tyy, tzz, txy, txz, tyz})) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz})
-        for (unsigned long i = 0; i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz})) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     const float* const p[3] = {px, py, pz};
     float* const out[6] = {txx, tyy, tzz, txy, txz, tyz};
     return tidal_run(c, count, p, skip, false, out);
@@ -3469,12 +3381,9 @@ int murbtidal_of(murbhip_ctx* c, unsigned long count, const int* bodies, float* 
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!bodies || !all_or_none({txx, tyy, tzz, txy, txz, tyz})) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
+    if (!bodies_valid(c, count, bodies, false) || !all_or_none({txx, tyy, tzz, txy, txz, tyz})) return MURBHIP_E_INVALID;
     float* const out[6] = {txx, tyy, tzz, txy, txz, tyz};
-    return tidal_run(c, count, p, bodies, true, out);
+    return tidal_run(c, count, nullptr, bodies, true, out);
 }
 
 // ---- include/murbknn.h
@@ -3487,11 +3396,7 @@ int knn_of_checks(murbhip_ctx* c, int k, int least, unsigned long count, const i
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 1;
     RC_TRY(field_state(c));
-    if (!knn_k_valid(k, least)) return MURBHIP_E_INVALID;
-    if (!bodies) return count == c->in.n ? 0 : MURBHIP_E_INVALID;
-    for (unsigned long i = 0; i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    return 0;
+    return knn_k_valid(k, least) && bodies_valid(c, count, bodies, true) ? 0 : MURBHIP_E_INVALID;
 }
 }  // namespace
 
@@ -3499,8 +3404,7 @@ int murbknn_of(murbhip_ctx* c, int k, unsigned long count, const int* bodies, in
 {
     const int rc = knn_of_checks(c, k, 1, count, bodies);
     if (rc != 0) return rc == 1 ? 0 : rc;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    return knn_run(c, k, count, p, bodies, true, idx, r2, nullptr, false);
+    return knn_run(c, k, count, nullptr, bodies, true, idx, r2, nullptr, false);
 }
 
 int murbknn_at(murbhip_ctx* c, int k, unsigned long count, const float* px, const float* py, const float* pz, const int* skip,
@@ -3510,11 +3414,8 @@ int murbknn_at(murbhip_ctx* c, int k, unsigned long count, const float* px, cons
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!knn_k_valid(k, 1) || !px || !py || !pz) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz})
-        for (unsigned long i = 0; i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz})) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     const float* const p[3] = {px, py, pz};
     return knn_run(c, k, count, p, skip, false, idx, r2, nullptr, false);
 }
@@ -3524,8 +3425,7 @@ int murbdensity_of(murbhip_ctx* c, int k, unsigned long count, const int* bodies
     const int rc = knn_of_checks(c, k, 2, count, bodies);
     if (rc != 0) return rc == 1 ? 0 : rc;
     if (!rho) return MURBHIP_E_INVALID;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    return knn_run(c, k, count, p, bodies, true, nullptr, nullptr, rho, false);
+    return knn_run(c, k, count, nullptr, bodies, true, nullptr, nullptr, rho, false);
 }
 
 int murbdensity_centre(murbhip_ctx* c, int k, double* out8)
@@ -3556,11 +3456,8 @@ int murbbind_of(murbhip_ctx* c, unsigned long count, const int* bodies, int* par
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!bodies && count != c->in.n) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    const float* const p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return bind_run(c, count, p, bodies, true, partner, h, false);
+    if (!bodies_valid(c, count, bodies, true)) return MURBHIP_E_INVALID;
+    return bind_run(c, count, nullptr, bodies, true, partner, h, false);
 }
 
 int murbbind_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const float* pvx,
@@ -3570,13 +3467,10 @@ int murbbind_at(murbhip_ctx* c, unsigned long count, const float* px, const floa
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz})) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz, pvx, pvy, pvz})
-        for (unsigned long i = 0; q && i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz, pvx, pvy, pvz})) return MURBHIP_E_INVALID;
     for (unsigned long i = 0; m && i < count; ++i)
         if (!std::isfinite(m[i]) || m[i] < 0.f) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     std::vector<float> gm;
     if (m) {
         gm.resize(count);
@@ -3613,11 +3507,8 @@ int murbpot_of(murbhip_ctx* c, unsigned long count, const int* bodies, const uns
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!phi || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    return pot_call(c, count, p, bodies, true, member, phi);
+    if (!phi || !bodies_valid(c, count, bodies, true)) return MURBHIP_E_INVALID;
+    return pot_call(c, count, nullptr, bodies, true, member, phi);
 }
 
 int murbpot_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const int* skip,
@@ -3627,11 +3518,8 @@ int murbpot_at(murbhip_ctx* c, unsigned long count, const float* px, const float
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !phi) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz})
-        for (unsigned long i = 0; i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz})) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     const float* const p[3] = {px, py, pz};
     return pot_call(c, count, p, skip, false, member, phi);
 }
@@ -3671,11 +3559,8 @@ int murbsep_of(murbhip_ctx* c, unsigned long count, const int* bodies, const uns
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!sep_request_valid(sum, lo_exp, sub, bins, hist, out4) || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    return sep_call(c, count, p, bodies, true, member, sum, lo_exp, sub, bins, hist, out4);
+    if (!sep_request_valid(sum, lo_exp, sub, bins, hist, out4) || !bodies_valid(c, count, bodies, true)) return MURBHIP_E_INVALID;
+    return sep_call(c, count, nullptr, bodies, true, member, sum, lo_exp, sub, bins, hist, out4);
 }
 
 int murbsep_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const unsigned char* member,
@@ -3685,9 +3570,7 @@ int murbsep_at(murbhip_ctx* c, unsigned long count, const float* px, const float
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!sep_request_valid(sum, lo_exp, sub, bins, hist, out4) || !px || !py || !pz) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz})
-        for (unsigned long i = 0; i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz})) return MURBHIP_E_INVALID;
     const float* const p[3] = {px, py, pz};
     return sep_call(c, count, p, nullptr, false, member, sum, lo_exp, sub, bins, hist, out4);
 }
@@ -3715,9 +3598,7 @@ int murbforeign_of(murbhip_ctx* c, unsigned long count, const int* bodies, const
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!label || !partner || !r2 || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!label || !partner || !r2 || !bodies_valid(c, count, bodies, true)) return MURBHIP_E_INVALID;
     return foreign_call(c, count, bodies, label, partner, r2);
 }
 
@@ -3775,13 +3656,10 @@ int murbnbr_of(murbhip_ctx* c, unsigned long count, const int* bodies, const flo
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if (!offsets || (!bodies && count != c->in.n)) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!offsets || !bodies_valid(c, count, bodies, true)) return MURBHIP_E_INVALID;
     std::vector<float> thr;
     if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    return nbr_run(c, count, p, bodies, true, thr, offsets, idx, r2, capacity);
+    return nbr_run(c, count, nullptr, bodies, true, thr, offsets, idx, r2, capacity);
 }
 
 int murbnbr_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const int* skip, const float* h,
@@ -3791,11 +3669,8 @@ int murbnbr_at(murbhip_ctx* c, unsigned long count, const float* px, const float
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !offsets) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz})
-        for (unsigned long i = 0; i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; skip && i < count; ++i)
-        if (skip[i] < -1 || (long)skip[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz})) return MURBHIP_E_INVALID;
+    if (!skips_valid(c, count, skip)) return MURBHIP_E_INVALID;
     std::vector<float> thr;
     if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
     const float* const p[3] = {px, py, pz};
@@ -3837,13 +3712,10 @@ int murblist_of(murbhip_ctx* c, unsigned long count, const int* bodies, const un
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if ((!bodies && count != c->in.n) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!bodies_valid(c, count, bodies, true) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
     if (!murb_list_valid(count, offsets, idx, c->in.n)) return MURBHIP_E_INVALID;
-    const float* const p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
-    return list_run(c, count, p, bodies, true, offsets, idx, out);
+    return list_run(c, count, nullptr, bodies, true, offsets, idx, out);
 }
 
 int murblist_at(murbhip_ctx* c, unsigned long count, const float* px, const float* py, const float* pz, const float* pvx, const float* pvy,
@@ -3854,9 +3726,7 @@ int murblist_at(murbhip_ctx* c, unsigned long count, const float* px, const floa
     if (count == 0) return 0;
     RC_TRY(field_state(c));
     if (!px || !py || !pz || !all_or_none({pvx, pvy, pvz}) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
-    for (const float* q : {px, py, pz, pvx, pvy, pvz})
-        for (unsigned long i = 0; q && i < count; ++i)
-            if (!std::isfinite(q[i])) return MURBHIP_E_INVALID;
+    if (!planes_finite(count, {px, py, pz, pvx, pvy, pvz})) return MURBHIP_E_INVALID;
     if (!murb_list_valid(count, offsets, idx, c->in.n)) return MURBHIP_E_INVALID;
     const float* const p[6] = {px, py, pz, pvx, pvy, pvz};
     float* const out[7] = {ax, ay, az, jx, jy, jz, phi};
@@ -3869,9 +3739,7 @@ int murbsplit_of(murbhip_ctx* c, unsigned long count, const int* bodies, const f
     if (!c) return MURBHIP_E_INVALID;
     if (count == 0) return 0;
     RC_TRY(field_state(c));
-    if ((!bodies && count != c->in.n) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
-    for (unsigned long i = 0; bodies && i < count; ++i)
-        if (bodies[i] < 0 || (long)bodies[i] >= (long)c->in.n) return MURBHIP_E_INVALID;
+    if (!bodies_valid(c, count, bodies, true) || !all_or_none({ax, ay, az}) || !all_or_none({jx, jy, jz})) return MURBHIP_E_INVALID;
     std::vector<float> thr;
     if (!nbr_thresholds(c, count, h, h_all, thr)) return MURBHIP_E_INVALID;
     RC_TRY(murbhip_sync(c));
@@ -3889,20 +3757,12 @@ int murbsplit_of(murbhip_ctx* c, unsigned long count, const int* bodies, const f
     const NbrConsume consume = [&](unsigned long first, unsigned long lo, unsigned long hi, size_t cap) -> int {
         const unsigned long npts = hi - lo;
         RC_TRY(grow(sh, sh.lst_pts, sh.lst_points, 2 * npts));
-        MurbFieldPackArgs pa{};
-        pa.idx = (const int*)(sh.fld_in + 6 * cap) + lo;   // the launch's bodies, as nbr_run staged them
-        pa.rec = sh.rec[c->cur];
-        pa.vel = sh.vel;
-        pa.pts = sh.lst_pts;
-        pa.count = (int)npts;
-        pa.padded = (int)npts;
-        hipLaunchKernelGGL(murb_field_pack_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, sh.compute, pa);
-        RC_TRY(hip_rc(hipGetLastError()));
+        const StagedPoints bodies_of_range{nullptr, (const int*)(sh.fld_in + kFieldIntPlane * cap) + lo};   // where stage_points left the launch's bodies
+        RC_TRY(pack_points(c, sh, bodies_of_range, sh.lst_pts, npts, npts, 0, false));
         list_range(offsets.data() + first, lo, hi, range);
         return list_sweep(c, sh, sh.lst_pts, npts, range, out, first + lo, results);
     };
-    const float* const p[3] = {nullptr, nullptr, nullptr};
-    RC_TRY(nbr_run(c, count, p, bodies, true, thr, offsets.data(), nullptr, nullptr, ~0ul, &consume));
+    RC_TRY(nbr_run(c, count, nullptr, bodies, true, thr, offsets.data(), nullptr, nullptr, ~0ul, &consume));
     for (unsigned long i = 0; counts && i < count; ++i) counts[i] = offsets[i + 1] - offsets[i];
     return 0;
 }

@@ -1,5 +1,5 @@
 """CPU: the yardstick of the field read-out (tests/helpers/field_ref.py) against the yardsticks of the sweeps, the planning
-behind murbfield_layout, the new entry points of the built libraries and the Python interface, the sweep kernel's code
+behind murbfield_layout, the launch cut of csrc/murb_field.h under g++ alone and under the sanitizers, the new entry points of the built libraries and the Python interface, the sweep kernel's code
 object, and why a skipped body must never enter an fp32 sum."""
 import ctypes as C
 import os
@@ -149,6 +149,102 @@ def test_field_layout_refusals(mh):
     for batch in (-16, 8, 17, (1 << 20) + 16):
         assert L.murbfield_layout(100, 0, batch, out) == E_INVALID, batch
     assert L.murbfield_layout(100, 0, 1 << 20, out) == 0
+
+
+# ---------------------------------------------------------------------------------- the launch cut, a stand-alone program
+CSRC = os.path.join(ROOT, "nbody-eurohpc_amd", "csrc")
+
+CUT_PROGRAM = r"""
+#include <cstdio>
+#include "murb_field.h"
+static bool same(const MurbFieldCut& k, int chunks, int tiles_each, int tiles_more, long grid)
+{
+    return k.chunks == chunks && k.tiles_each == tiles_each && k.tiles_more == tiles_more && k.grid == grid;
+}
+int main() {
+    const unsigned long bodies[] = {1, 2, 511, 513, 2049, 4096, 65536, 200000, 1000000, 4000000};
+    const long chunk_options[] = {0, 1, 2, 3, 7, 16, 61, 500, 7813};
+    const long grids[] = {1, 4, 64, 416, 1024, 1216};
+    const unsigned long paddeds[] = {16, 32, 1008, 4096, 16384, 1ul << 20};   // ascending
+    unsigned long cases = 0, cut_less = 0, uncut = 0;
+    for (const unsigned long n : bodies)
+        for (const long co : chunk_options)
+            for (const long grid_full : grids) {
+                if (!murb_field_options_valid(co, 0)) return 2;
+                const MurbFieldLayout l = murb_field_layout(n, co, 0);
+                if (l.chunks < 1 || l.chunks > l.tiles) return 3;
+                int before = l.chunks;
+                for (const unsigned long padded : paddeds) {
+                    if (murb_field_padded(padded) != padded || murb_field_padded(padded - 15) != padded || murb_field_padded(padded + 1) != padded + 16)
+                        return 4;
+                    for (const bool fill : {false, true}) {
+                        const MurbFieldCut k = murb_field_cut(l, padded, grid_full, fill);
+                        ++cases;
+                        if (k.chunks < 1 || k.chunks > l.chunks) return 10;
+                        if (k.tiles_each < 1) return 11;
+                        if (k.tiles_more < 0 || k.tiles_more >= k.chunks) return 12;
+                        if (k.tiles_each * k.chunks + k.tiles_more != l.tiles) return 13;
+                        if (k.grid < 1 || k.grid > grid_full) return 14;
+                        if (k.grid > (long)k.groups * k.chunks) return 15;
+                        if ((unsigned long)k.groups * 16 != padded) return 16;
+                        if (!fill) {
+                            if (k.chunks != l.chunks) return 20;   // a sum's bits do not depend on how many points were asked for
+                            continue;
+                        }
+                        if (k.chunks > before) return 21;          // non-increasing in padded
+                        before = k.chunks;
+                        if (k.groups >= grid_full && k.chunks != 1) return 22;
+                        const long most = (long)k.groups * l.chunks;
+                        if ((long)k.groups * k.chunks < (grid_full < most ? grid_full : most)) return 23;   // fills the grid where the layout allows
+                        cut_less += k.chunks < l.chunks;
+                        uncut += k.chunks == 1 && l.chunks > 1;
+                    }
+                }
+            }
+    std::printf("%lu %lu %lu", cases, cut_less, uncut);
+    // known answers: tiles of 512 bodies, 256 CUs x 4 workgroups
+    const MurbFieldLayout five = murb_field_layout(2049, 3, 0), many = murb_field_layout(200000, 0, 0);
+    std::printf(" %d %d %d %d", five.tiles, five.chunks, many.tiles, many.chunks);
+    std::printf(" %d", (int)same(murb_field_cut(five, 16, 1024, true), 3, 1, 2, 3));
+    std::printf(" %d", (int)same(murb_field_cut(five, 16384, 1024, true), 1, 5, 0, 1024));
+    std::printf(" %d", (int)same(murb_field_cut(many, 4096, 1024, true), 4, 97, 3, 1024));
+    std::printf(" %d\n", (int)same(murb_field_cut(many, 4096, 1024, false), 16, 24, 7, 1024));
+    return 0;
+}
+"""
+
+
+def build_and_run_cut(tmp_path, flags):
+    src, exe = tmp_path / "cut.cpp", tmp_path / "cut"
+    src.write_text(CUT_PROGRAM)
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", *flags, "-I", CSRC, str(src), "-o", str(exe)], check=True)
+    done = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert done.returncode == 0 and not done.stderr, (done.returncode, done.stderr)
+    return done.stdout.split()
+
+
+def check_cut_program(out):
+    cases, cut_less, uncut = (int(v) for v in out[:3])
+    print("cuts", cases, "fill mode below the layout's chunks", cut_less, "not cut at all", uncut)
+    assert cases == 10 * 9 * 6 * 6 * 2 and cut_less > 0 and uncut > 0
+    assert out[3:7] == ["5", "3", "391", "16"], "the layouts of the known answers"
+    assert out[7:] == ["1", "1", "1", "1"], "the known answers"
+
+
+def test_launch_cut(tmp_path):
+    """csrc/murb_field.h is plain C++: g++ compiles it on the CPU with every warning an error.  murb_field_cut over body counts
+    up to 4 000 000, chunk options up to the tile count, grids from 1 to 1216 workgroups and launches from one group to 2^20
+    points: in both modes the chunks cover every tile once (tiles_each * chunks + tiles_more == tiles, tiles_each >= 1), lie in
+    [1, the layout's], and the grid in [1, min(grid_full, groups * chunks)]; the fixed mode keeps the layout's chunks whatever the
+    launch holds; the fill mode's chunks never grow with the launch, are 1 once the groups fill the grid, and fill the grid
+    wherever the layout allows.  Four known answers."""
+    check_cut_program(build_and_run_cut(tmp_path, []))
+
+
+def test_launch_cut_under_sanitizers(tmp_path):
+    """The same stand-alone program, with its own main, built with -fsanitize=address,undefined and run directly: no report, the
+    same answers."""
+    check_cut_program(build_and_run_cut(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]))
 
 
 # -------------------------------------------------------------------------------------------------------------- entry points
